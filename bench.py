@@ -12,6 +12,14 @@ processes its own batch (weak scaling, no data-path collective).
 Prints one JSON line (rank 0).  Launch for N>1:
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line (value,
+ms_per_step, the HIP-event roofline of the timed steps).  `--full` adds what
+takes runs of its own: the post-timing self-check of every trial of the last
+batch against the default schedule (`checked`) and the CPU baselines
+(`cpu_baseline`).  `--dump-outputs DIR` writes the last timed step's outputs
+as DIR/*.npy (a fixed, seeded sample of the S/N array) so that two builds can
+be compared output for output.
 """
 import argparse
 import json
@@ -178,6 +186,42 @@ def _drop_cache(fn):
         os.close(fd)
 
 
+DUMP_SEED = 20240607
+DUMP_ROWS = 1 << 20          # sampled (trial, period) rows of a large S/N array: 1 Mi x W float32 + 8 MiB of indices
+DUMP_WHOLE_BYTES = 32 << 20  # an S/N array up to this size is written whole
+
+
+def dump_snr(torch, out_dir, snr):
+    """--dump-outputs: the S/N array the last timed step left in `snr`
+    (trials, trial periods, widths) as out_dir/snr.npy, float32.  An array
+    above DUMP_WHOLE_BYTES is sampled: DUMP_ROWS rows (fewer for many widths) of the flattened
+    (trial x period) axis, every width of each, drawn once from a generator
+    seeded DUMP_SEED (the same rows in every run of the same shape), with
+    their flat row numbers (trial * L + period) in out_dir/snr_rows.npy,
+    float64."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    B, L, W = snr.shape
+    if snr.numel() * 4 <= DUMP_WHOLE_BYTES:
+        np.save(os.path.join(out_dir, "snr.npy"), snr.cpu().numpy())
+        return
+    nrows = min(DUMP_ROWS, (56 << 20) // (4 * W + 8))    # both files within 56 MiB whatever the width count
+    rows = np.sort(np.random.RandomState(DUMP_SEED).randint(0, B * L, size=nrows, dtype=np.int64))
+    idx = torch.from_numpy(rows).to(snr.device)
+    sample = snr.reshape(B * L, W).index_select(0, idx).cpu().numpy()
+    np.save(os.path.join(out_dir, "snr.npy"), sample)
+    np.save(os.path.join(out_dir, "snr_rows.npy"), rows.astype(np.float64))
+
+
+def dump_peaks(out_dir, peaks, clusters):
+    """--dump-outputs of the cfg5 leg: the sorted peak list (one row per peak:
+    period, freq, width, ducy, iw, ip, snr, dm) and the cluster sizes, float64."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "peaks.npy"), np.asarray([tuple(p) for p in peaks], np.float64).reshape(-1, 8))
+    np.save(os.path.join(out_dir, "cluster_sizes.npy"), np.asarray([len(cl) for cl in clusters], np.float64))
+
+
 def bench_cfg5(args, torch, dist, world, rank, local, dev):
     """BASELINE configs[4] (cfg5): SIGPROC .tim DM trials of 2^23 samples @ 64 us
     searched from files to clustered peak lists, the rffa search and
@@ -253,13 +297,15 @@ def bench_cfg5(args, torch, dist, world, rank, local, dev):
         peaks = search_files(fnames, pool, chunksize=args.batch)
         # Pipeline.search's sort + Pipeline.cluster_peaks (pipeline.py:186,
         # 192-215) on the gathered list, inside the timed region
-        _, clusters = cluster_peaks(peaks, CFG5_CLUSTER_RADIUS, c["n"] * c["tsamp"])
+        ordered, clusters = cluster_peaks(peaks, CFG5_CLUSTER_RADIUS, c["n"] * c["tsamp"])
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         if world > 1:
             dist.barrier()
             elapsed = rank_max(torch, dist, elapsed, dev)
         res[mode] = (elapsed, len(peaks), len(clusters))
+    if rank == 0 and args.dump_outputs:
+        dump_peaks(args.dump_outputs, ordered, clusters)    # the last (warm) pass
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         lst = os.path.join(tmp, "files.txt")
@@ -438,6 +484,8 @@ def bench_cfg3(args, torch, dist, world, rank, local, dev):
     stats = plan.stats()
     # every trial of the last batch through the default-schedule plan at batch 1
     last = len(mine) - B * ((len(mine) - 1) // B)
+    if rank == 0 and args.dump_outputs:
+        dump_snr(torch, args.dump_outputs, snr[:last])      # the job's last batch
     checked = None if args.no_self_check else self_check(torch, dist, engine, plan, xbuf, snr, c, local, world, dev,
                                                          last)
     if rank == 0:
@@ -499,10 +547,16 @@ def main():
                          "1024-trial job of BASELINE configs[2] (strong scaling); cfg5: files -> peaks")
     ap.add_argument("--files", type=int, default=256, help="cfg5: SIGPROC files per GPU")
     ap.add_argument("--trials", type=int, default=0, help="cfg3: trials in the job (default 1024)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the post-timing self-check against "
+                         "the default schedule and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (a fixed, "
+                         "seeded sample of a large S/N array; rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-self-check", action="store_true",
-                    help="skip the post-timing S/N check against the default schedule (profiling runs: its "
-                         "launches would be counted with the timed ones)")
+                    help="with --full: skip the post-timing S/N check against the default schedule (profiling "
+                         "runs: its launches would be counted with the timed ones)")
     ap.add_argument("--one-gpu-rehearsal", action="store_true",
                     help="multi-rank code path check on a one-GPU box: every rank on cuda:0, gloo instead of "
                          "RCCL (not a measurement)")
@@ -510,6 +564,9 @@ def main():
                     help="cfg2: 1 = step k+1's deredden + normalise + downsampling ladder on a second stream "
                          "while step k's FFA passes run (two workspaces); 0 = one stream")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, print the line
+        args.no_self_check = args.no_cpu_baseline = True
     if not args.batch:
         args.batch = 32 if args.workload == "cfg3" else 16
 
@@ -632,6 +689,8 @@ def main():
     cone = engine.profile_read(0)
     ladder = engine.profile_read(1)
     stats = plan.stats()
+    if rank == 0 and args.dump_outputs:
+        dump_snr(torch, args.dump_outputs, snr)
     checked = None if args.no_self_check else self_check(torch, dist, engine, plan, xbuf, snr, c, local, world, dev,
                                                          B)
 

@@ -370,3 +370,27 @@ def test_bench_pmc_summary_matches_sources(tmp_path, monkeypatch):
     put("r06f_pmc_cone_cfg3.json", "0123", 1.0)
     s, why = bench.pmc_traffic("cfg3")
     assert s is None and why.startswith("stale")
+
+
+def test_bench_dump_snr(tmp_path, monkeypatch):
+    """bench.dump_snr (--dump-outputs): a small S/N array is written whole; a
+    large one as the same seeded rows in every run (every width of a row,
+    float32), with their flat (trial x period) row numbers beside them."""
+    import sys
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    snr = torch.arange(3 * 1001 * 6, dtype=torch.float32).reshape(3, 1001, 6)
+    bench.dump_snr(torch, str(tmp_path / "whole"), snr)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["snr.npy"]
+    assert np.array_equal(np.load(tmp_path / "whole" / "snr.npy"), snr.numpy())
+    monkeypatch.setattr(bench, "DUMP_WHOLE_BYTES", 1024)
+    monkeypatch.setattr(bench, "DUMP_ROWS", 257)
+    for d in ("a", "b"):
+        bench.dump_snr(torch, str(tmp_path / d), snr)
+    got, rows = np.load(tmp_path / "a" / "snr.npy"), np.load(tmp_path / "a" / "snr_rows.npy")
+    assert got.dtype == np.float32 and got.shape == (257, 6) and rows.dtype == np.float64 and rows.shape == (257,)
+    assert rows.min() >= 0 and rows.max() < 3 * 1001 and np.all(np.diff(rows) >= 0) and np.unique(rows).size > 200
+    assert np.array_equal(got, snr.numpy().reshape(-1, 6)[rows.astype(np.int64)])
+    assert np.array_equal(got, np.load(tmp_path / "b" / "snr.npy"))
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "snr_rows.npy"))

@@ -4,7 +4,8 @@
 # the first failure ends the script (no retries).  Output: gpurun_out/TAG/.
 #
 #   bash tools/gpu_run.sh TAG tests                 GPU parity tests + smoke
-#   bash tools/gpu_run.sh TAG bench [ARGS...]        bench.py (cfg2 headline unless --workload)
+#   bash tools/gpu_run.sh TAG bench [ARGS...]        bench.py --full (cfg2 headline unless --workload; with the
+#                                                    self-check and the CPU baselines)
 #   bash tools/gpu_run.sh TAG prof                   rocprofv3 kernel-trace summary of the cfg2 bench
 #   bash tools/gpu_run.sh TAG pmc [CFG]              PMC passes (4 counter groups) -> profiles/TAG_pmc_cone[_CFG].json
 #   bash tools/gpu_run.sh TAG configs [LIB...]       per-config table (tools/bench_configs.py) per library
@@ -132,7 +133,7 @@ do_trace() {
   for lib in "$@"; do
     local n=$(basename "$lib" .so)
     (cd /tmp && export TMPDIR=/tmp && RIPTIDE_AMD_LIB=$R/$lib timeout -k 10 400 rocprofv3 --kernel-trace -d "$O/trace_$n" \
-       -o run -f csv -- python3 "$R/bench.py" --no-cpu-baseline --steps 4 > "$O/trace_$n.log" 2>&1) \
+       -o run -f csv -- python3 "$R/bench.py" --full --no-cpu-baseline --steps 4 > "$O/trace_$n.log" 2>&1) \
       || fail "trace $n" "$O/trace_$n.log"
     grep '^{"metric"' "$O/trace_$n.log" > "$O/trace_$n.json" || fail "trace $n (no bench line)" "$O/trace_$n.log"
     echo "== $n: $(python3 -c 'import json,sys; d=json.load(open(sys.argv[1])); print(round(d["value"],2), "trials/s", d["config"]["cone_launches_per_step"], "launches", "checked", d.get("checked"))' "$O/trace_$n.json")"
@@ -259,9 +260,9 @@ do_readrate() {   # [FILES]: cold-read rate with 1 / 2 / 4 / 8 reader processes 
 
 case "$CMD" in
   tests) do_tests ;;
-  bench) do_bench bench "$@" ;;
-  bench3) do_bench bench_cfg3 --workload cfg3 "$@" ;;
-  bench5) do_bench bench_cfg5 --workload cfg5 "$@" ;;
+  bench) do_bench bench --full "$@" ;;
+  bench3) do_bench bench_cfg3 --full --workload cfg3 "$@" ;;
+  bench5) do_bench bench_cfg5 --full --workload cfg5 "$@" ;;
   prof) do_prof ;;
   pmc) do_pmc "${1:-cfg2}" ;;
   configs) do_configs "$@" ;;
@@ -282,9 +283,9 @@ case "$CMD" in
     do_pmc cfg3
     do_pmc cfg4
     do_tests
-    do_bench bench
-    do_bench bench_cfg3 --workload cfg3
-    do_bench bench_cfg5 --workload cfg5
+    do_bench bench --full
+    do_bench bench_cfg3 --full --workload cfg3
+    do_bench bench_cfg5 --full --workload cfg5
     do_readrate
     do_configs
     do_prof ;;
