@@ -177,6 +177,61 @@ LADDER_EDGE_CASE = dict(n=1 << 20, tsamp=1e-3, pmin=452.9 * 1e-3 * 16, pmax=452.
                         bmin=16, bmax=17, ducy_max=0.2)
 
 
+# ---------------------------------------------------------------- fused S/N row-shape sweep
+# (bins_min, bins_max) ranges, each astride one breakpoint of the cone
+# kernel's S/N epilogue: the slot-width variant (merge_slots), the lane-group
+# size (snr_group) and the chunk template (tests/test_gpu_snr_shapes.py;
+# tests/test_host.py checks that both sides of every breakpoint are inside).
+SNR_SHAPE_RANGES = [(2, 5), (6, 12), (30, 36), (38, 43), (62, 67), (70, 75), (126, 139), (190, 195), (236, 241),
+                    (262, 275), (318, 323), (510, 515), (542, 547), (702, 707), (1022, 1027), (1086, 1091),
+                    (1406, 1411), (2875, 2880)]
+SNR_SHAPE_TSAMP = 1e-3
+
+
+def snr_shape_sizes(bmax):
+    """The sweep's two series lengths: 2^16 samples (the low rungs take
+    several passes: the S/N runs on final tiles) and 5 bins_max + 3 (every
+    transform one whole unit of about 5 rows)."""
+    return {"tiles": 1 << 16, "whole": 5 * bmax + 3}
+
+
+def snr_shape_plan(bmin, bmax, n):
+    """Search parameters of one sweep case: the first rung has factor 1
+    (period_min = bins_min tsamp), three rungs, period_max inside the series."""
+    tsamp = SNR_SHAPE_TSAMP
+    pmin = bmin * tsamp
+    pmax = min(pmin * ((bmax + 1) / bmin) ** 3 * 0.999, 0.99 * n * tsamp)
+    return dict(n=n, tsamp=tsamp, pmin=pmin, pmax=pmax, bmin=bmin, bmax=bmax)
+
+
+# widths <= 9 (kSnrSegWmax), unsorted and not the standard ladder: the only
+# plans whose 240-264-bin rows take the segmented S/N (snr_seg_ok)
+SNR_SHAPE_NARROW = [9, 3, 1, 5, 7]
+
+
+def snr_shape_widths(bmin, bmax, ladder):
+    """The sweep's width lists (values clipped to bins_min - 1).
+    ladder: the standard one, generate_width_trials(bins_min, ducy_max=0.2).
+    mixed: unsorted, on both sides of the S/N's 12-column register window
+    and 17-column chunk, with the widest legal width.
+    all32: 32 widths, duplicates kept (every select slot of a lane).
+    narrow: SNR_SHAPE_NARROW, for the ranges that meet 240-264 bins only --
+    every other list holds a width > 12 there, which keeps those rows on the
+    window paths."""
+    def clip(ws, unique=True):
+        out = []
+        for w in ws:
+            w = max(1, min(int(w), bmin - 1))
+            if not (unique and w in out):
+                out.append(w)
+        return out
+    lists = {"ladder": clip(ladder), "mixed": clip([bmin - 1, 13, 1, 18, 5, 12, 17, 2, 3]),
+             "all32": clip(range(1, 33), unique=False)}
+    if bmin <= 264 and bmax >= 240:
+        lists["narrow"] = clip(SNR_SHAPE_NARROW)
+    return lists
+
+
 # ---------------------------------------------------------------- cfg5: rffa beam of SIGPROC files
 # BASELINE.json configs[4] at reduced trial count: 2^23-sample SIGPROC .tim
 # DM trials @ 64 us (537 s, "SUPERB-like"), refdm = 10 k, searched with

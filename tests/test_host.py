@@ -91,7 +91,7 @@ def test_ladder_path_choice(lib):
     assert _ladder(lib, 1 << 20, inputs.LADDER_EDGE_CASE)[0] == 1
     over = dict(inputs.LADDER_EDGE_CASE, pmin=inputs.LADDER_EDGE_CASE["pmin"] * 510.5 / 509.5125)
     over["pmax"] = over["pmin"] * 1.125 ** 2 * 0.999
-    assert _ladder(lib, 1 << 20, over)[0] in (0, 2)
+    assert _ladder(lib, 1 << 20, over)[0] == 2         # the hybrid path: one rung fused, one per-rung
     # every rung past the margin: nothing for the fused kernel
     assert _ladder(lib, 1 << 22, dict(tsamp=64e-6, pmin=40.0, pmax=100.0, bmin=960, bmax=1040))[0] == 0
 
@@ -165,6 +165,103 @@ def test_schedule_refuses_blocks_over_2gib(lib):
     assert rc == 1 and b"2 GiB" in lib.rt_last_error()
     n = (1 << 29) - 4096 * 260                 # every block below 2 GiB
     assert lib.rt_schedule_check(n, 1e-3, 2, 0.24, 0.25, 240, 240, *args) == 0, lib.rt_last_error()
+
+
+def test_snr_shape_sweep_schedules(lib):
+    """Every schedule of the fused S/N row-shape sweep (inputs.SNR_SHAPE_RANGES,
+    tests/test_gpu_snr_shapes.py) passes the host planner's validation, at
+    both sizes: 2^16 samples, where the low rungs take several passes (more
+    work items than transforms: the S/N runs on final tiles), and
+    5 bins_max + 3 samples, where every transform is one whole unit; and every
+    bins value of the range has a transform."""
+    for bmin, bmax in inputs.SNR_SHAPE_RANGES:
+        for kind, n in inputs.snr_shape_sizes(bmax).items():
+            c = inputs.snr_shape_plan(bmin, bmax, n)
+            assert c["pmin"] == bmin * c["tsamp"] and c["pmax"] <= 0.99 * n * c["tsamp"]
+            u = [ctypes.c_uint64() for _ in range(4)]
+            d = [ctypes.c_double() for _ in range(2)]
+            rc = lib.rt_schedule_check(n, c["tsamp"], 10, c["pmin"], c["pmax"], bmin, bmax,
+                                       *(ctypes.byref(x) for x in u[:3]), ctypes.byref(d[0]), ctypes.byref(d[1]),
+                                       ctypes.byref(u[3]))
+            assert rc == 0, (bmin, bmax, kind, lib.rt_last_error())
+            transforms, items = u[0].value, u[1].value
+            assert transforms >= bmax - bmin + 1
+            assert (items > transforms) if kind == "tiles" else (items == transforms), (bmin, bmax, kind)
+            _, foldbins = _grid(lib, c)
+            assert set(range(bmin, bmax + 1)) <= set(foldbins.tolist()), (bmin, bmax, kind)
+
+
+# Restatement of the row-shape tables the fused S/N is specialised by:
+# merge_slots and snr_group (riptide_amd/csrc/common.hpp), the short rows'
+# 4-lane groups and the chunk templates snr_epilogue picks
+# (riptide_amd/csrc/ffa_kernels.hip: kSnrShortG, snr_rows<5|9|17, G>, the
+# one-wave-per-row loop past 64 x 17 bins), and snr_seg_ok's 240-264 bins.
+def _merge_slots(p):
+    if p <= 32:
+        return "pack2"
+    s = (p + 63) // 64
+    for top in (1, 2, 3, 4, 5, 8, 11, 16, 22, 45):
+        if s <= top:
+            return top
+    return 0
+
+
+def _snr_group(p):
+    if p <= 32:
+        return 4
+    G = 8
+    while G < 64 and (((p + G - 1) // G) | 1) > 17:
+        G <<= 1
+    return G
+
+
+def _row_class(p):
+    G = _snr_group(p)
+    c = (p + G - 1) // G
+    if p <= 32 or c < 17:
+        c |= 1
+    chunk = 5 if c <= 5 else 9 if c <= 9 else 17 if c <= 17 else "loop"
+    return _merge_slots(p), G, chunk if G < 16 or chunk == "loop" else 17, 240 <= p <= 264
+
+
+def test_snr_shape_sweep_covers_breakpoints():
+    """The sweep's ranges hold both sides of every breakpoint of the row-shape
+    tables: p | p + 1 take different instantiations (by the restatement
+    above) and one range contains both, so a later edit of the table that
+    drops a class fails here."""
+    ranges = inputs.SNR_SHAPE_RANGES
+    assert len(ranges) == len(set(ranges)) == 18
+    edges = {32: "pack2 -> 1 slot, G 4 -> 8", 40: "<5,8> -> <9,8>", 64: "1 -> 2 slots", 72: "<9,8> -> <17,8>",
+             128: "2 -> 3 slots", 136: "G 8 -> 16", 192: "3 -> 4 slots", 239: "window -> segmented",
+             264: "segmented ends", 272: "G 16 -> 32", 320: "5 -> 8 slots", 512: "8 -> 11 slots",
+             544: "G 32 -> 64", 704: "11 -> 16 slots", 1024: "16 -> 22 slots", 1088: "chunks -> very-wide loop",
+             1408: "22 -> 45 slots"}
+    for p, what in edges.items():
+        assert _row_class(p) != _row_class(p + 1), (p, what)
+        assert any(lo <= p and p + 1 <= hi for lo, hi in ranges), (p, what)
+    # every breakpoint of the restated tables is in the list but two, which
+    # the BASELINE-shaped tests hold: 20 | 21 (snr_rows<5,4> -> <9,4>: cfg4's
+    # 16-32 bins, test_periodogram_golden[cfg4] and test_full_config_every_row)
+    # and 256 | 257 (4 -> 5 slots: the 240-260 bins of cfg1-3)
+    found = {p for p in range(2, 2880) if _row_class(p) != _row_class(p + 1)}
+    assert found - {20, 256} == set(edges)
+    # the segmented form needs widths <= 9 (snr_seg_ok): the ranges that meet
+    # 240-264 bins, and only they, carry such a list
+    for lo, hi in ranges:
+        lists = inputs.snr_shape_widths(lo, hi, [1, 2, 3])
+        assert ("narrow" in lists) == (lo <= 264 and hi >= 240)
+        assert "narrow" not in lists or (max(lists["narrow"]) <= 9 and lists["narrow"] != sorted(lists["narrow"]))
+    assert sum("narrow" in inputs.snr_shape_widths(lo, hi, [1]) for lo, hi in ranges) == 2
+    assert _merge_slots(2880) == 45 and _merge_slots(2881) == 0
+    # the short rows: the 8 | 9-bin edge of the short-row merge (pack_stride),
+    # the shortest (2) and the widest (2880) rows the engine accepts
+    for p in (2, 2880):
+        assert any(lo <= p <= hi for lo, hi in ranges), p
+    assert any(lo <= 8 and 9 <= hi for lo, hi in ranges)
+    # every class of the tables is met by some bins value of the sweep
+    swept = {_row_class(p)[:3] for lo, hi in ranges for p in range(lo, hi + 1)}
+    swept |= {_row_class(p)[:3] for p in list(range(16, 33)) + list(range(240, 266))}   # BASELINE-shaped tests
+    assert {_row_class(p)[:3] for p in range(2, 2881)} == swept
 
 
 def test_periodogram_length_errors(lib):
