@@ -207,6 +207,56 @@ int rt_threshold_select_device(const float* d_snrs, size_t batch, size_t snr_str
                                size_t num_widths, const double* d_logf, const double* d_coeffs, size_t ncoef,
                                double smin, uint32_t* d_counts, uint32_t* d_idx, size_t cap, void* stream);
 
+/* ------------------------- candidate folding ------------------------------ */
+/* riptide/folding.py:19-81 (what TimeSeries.fold returns) for a batch of
+ * candidates, bit-identical to the reference's arithmetic: the series
+ * downsampled by `factor`, cut into m = floor(size / factor) / bins whole
+ * periods, scaled by (float)pow(m * factor, -0.5), then
+ *   subints == 1 or m == 1        the float32 sum over the m rows: bins floats
+ *   subints == 0 (None) or == m   the (m, bins) rows themselves
+ *   any other subints             the rows downsampled along their first axis
+ *                                 by m / subints: floor(m / (m / subints)) rows,
+ *                                 which is subints - 1 for some (m, subints)
+ *                                 pairs, as in the reference.
+ * Candidates of one call may fold different series (rows of d_data). */
+typedef struct rt_fold_spec {
+    double   factor;    /* period / bins / tsamp, must be > 1 and <= size */
+    uint64_t out_off;   /* float offset of this candidate's result in d_out */
+    uint32_t series;    /* row of d_data */
+    uint32_t bins;      /* >= 2 */
+    uint32_t subints;   /* 0 = None */
+    uint32_t reserved;
+} rt_fold_spec;
+
+/* Host only, no device: the whole periods m and the rows of the result
+ * (*rows == 0: a 1-D profile of `bins` floats).  RT_EINVAL as below. */
+int rt_fold_shape(size_t size, double factor, size_t bins, size_t subints, size_t* m, size_t* rows);
+/* Host only: device workspace bytes of a call with these specs (the
+ * descriptor tables and the row arrays of the candidates whose result is not
+ * the row array itself).  Validates factor, bins, m and subints. */
+int rt_fold_workspace_bytes(size_t size, const rt_fold_spec* specs, size_t nspecs, size_t* bytes);
+/* Fold `nspecs` candidates of the `nseries` device-resident series (series r
+ * at d_data + r * data_stride) into d_out.  Stream-ordered, no host
+ * synchronisation.  `specs` is host memory and is read before the call
+ * returns: the descriptor tables are built in a pinned staging buffer that the
+ * library owns and reuses only after the stream has passed the copy, so the
+ * caller may free or overwrite `specs` at once.  The staging buffers and
+ * their events live for the rest of the process (a few KiB each, as many as
+ * calls were ever in flight at once); they are not released when the library
+ * is unloaded.  d_data, d_out and
+ * d_workspace must stay valid until the stream has run the call.
+ * RT_EINVAL (nothing is launched) for: a factor outside (1, size], bins < 2,
+ * m == 0, subints > m, series >= nseries, a result range past out_floats or
+ * overlapping another spec's, a workspace below rt_fold_workspace_bytes.
+ * nspecs == 0 is RT_OK. */
+int rt_fold_device(const float* d_data, size_t size, size_t data_stride, size_t nseries,
+                   const rt_fold_spec* specs, size_t nspecs, float* d_out, size_t out_floats,
+                   void* d_workspace, size_t workspace_bytes, void* stream);
+/* Host-buffer form: uploads the `nseries` contiguous series of x once, folds
+ * every candidate, copies out_floats floats back.  Synchronous. */
+int rt_fold(const float* x, size_t size, size_t nseries, const rt_fold_spec* specs, size_t nspecs,
+            float* out, size_t out_floats);
+
 /* --------------------------- file input (device) --------------------------- */
 /* 8-bit SIGPROC samples (riptide/time_series.py:352-357) to float32 in device
  * memory: d_raw holds n bytes, int8 when is_signed else uint8; exact as

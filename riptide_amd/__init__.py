@@ -18,8 +18,11 @@ from .libffa import boxcar_snr, downsample, ffa1, ffa2, ffafreq, ffaprd, generat
 from .running_medians import fast_running_median, running_median
 from .search import ffa_search
 from .time_series import TimeSeries
+from .peak_cluster import PeakCluster
+from .candidate import Candidate, build_candidates
 
 __all__ = [
+    "Candidate", "PeakCluster", "build_candidates",
     "TimeSeries", "Periodogram", "Metadata", "ffa_search", "ffa1", "ffa2", "ffafreq", "ffaprd",
     "generate_signal", "downsample", "boxcar_snr", "find_peaks", "running_median",
     "fast_running_median", "generate_width_trials", "cluster1d", "Peak",

@@ -916,6 +916,172 @@ void run_deredden_normalise(const float* d_in, size_t size, size_t batch, size_t
     }
 }
 
+// ---- candidate folding (folding.py:19-81)
+// m and the mode / result rows of one candidate; throws as the header lists.
+struct FoldShape {
+    uint64_t m = 0;
+    uint32_t mode = kFoldRows;
+    uint64_t rows = 0;      // result rows (0: a 1-D profile)
+    double vf = 0.0;
+};
+
+FoldShape fold_shape(size_t size, double f, size_t bins, size_t subints)
+{
+    if (!((f > 1.0) & (f <= (double)size)))
+        throw std::invalid_argument("Downsampling factor must verify: 1 < f <= size");
+    if (bins < 2) throw std::invalid_argument("fold: bins must be >= 2");
+    if (bins > 0xFFFFFFFFull) throw std::invalid_argument("fold: too many bins");
+    FoldShape s;
+    s.m = downsampled_size(size, f) / bins;
+    if (!s.m) throw std::invalid_argument("fold: no whole period fits in the data");
+    if (s.m > 0xFFFFFFFFull) throw std::invalid_argument("fold: too many periods");
+    if (subints > s.m) throw std::invalid_argument("fold: subints exceeds the number of whole periods");
+    if (subints == 1 || s.m == 1) {
+        s.mode = kFoldProfile;
+    } else if (subints == 0 || subints == s.m) {
+        s.rows = s.m;
+    } else {
+        s.mode = kFoldVertical;
+        s.vf = (double)s.m / (double)subints;
+        s.rows = downsampled_size(s.m, s.vf);
+    }
+    return s;
+}
+
+// The launch plan of one call: the rows table (every candidate), the subints
+// table (those whose result is not the row array) and the workspace layout
+// [both tables | row arrays of the subints candidates].
+struct FoldPlan {
+    std::vector<FoldCand> rows, sub;
+    uint32_t rows_blocks = 0, sub_blocks = 0;
+    size_t table_bytes = 0, ws_bytes = 0;
+};
+
+FoldPlan fold_plan(size_t size, const rt_fold_spec* specs, size_t nspecs)
+{
+    FoldPlan P;
+    if (!nspecs) return P;
+    if (!specs) throw std::invalid_argument("fold: null specs");
+    uint64_t rb = 0, sb = 0, ws_floats = 0;
+    P.rows.reserve(nspecs);
+    for (size_t i = 0; i < nspecs; ++i) {
+        const rt_fold_spec& sp = specs[i];
+        const FoldShape sh = fold_shape(size, sp.factor, sp.bins, sp.subints);
+        FoldCand c{};
+        c.f = sp.factor;
+        c.vf = sh.vf;
+        c.n_rows_out = sh.m * (uint64_t)sp.bins;
+        c.out_off = sp.out_off;
+        c.scale = (float)std::pow((double)sh.m * sp.factor, -0.5);
+        c.bins = sp.bins;
+        c.m = (uint32_t)sh.m;
+        c.mode = sh.mode;
+        c.sub_rows = sh.mode == kFoldProfile ? 1u : (uint32_t)sh.rows;
+        c.rows_in_ws = sh.mode != kFoldRows;
+        c.rows_off = c.rows_in_ws ? ws_floats : sp.out_off;
+        const uint32_t o = ds_per_block(sp.factor);
+        c.staged = o >= 32;
+        c.per_block = c.staged ? o : 256u;
+        c.first_block = (uint32_t)rb;
+        rb += (c.n_rows_out + c.per_block - 1) / c.per_block;
+        if (rb > 0x7FFFFFFFull) throw std::invalid_argument("fold: too many outputs for one call");
+        P.rows.push_back(c);
+        if (c.rows_in_ws) {
+            ws_floats += c.n_rows_out;
+            FoldCand d = c;
+            d.first_block = (uint32_t)sb;
+            sb += ((uint64_t)c.sub_rows * c.bins + 255) / 256;
+            P.sub.push_back(d);
+        }
+    }
+    P.rows_blocks = (uint32_t)rb;
+    P.sub_blocks = (uint32_t)sb;
+    P.table_bytes = align_up((P.rows.size() + P.sub.size()) * sizeof(FoldCand), 256);
+    P.ws_bytes = P.table_bytes + ws_floats * sizeof(float);
+    return P;
+}
+
+size_t fold_result_floats(const FoldCand& c)
+{
+    return c.mode == kFoldRows ? c.n_rows_out : (size_t)c.sub_rows * c.bins;
+}
+
+// series indices, result ranges inside out_floats and disjoint
+void fold_check_ranges(const FoldPlan& P, const rt_fold_spec* specs, size_t nseries, size_t out_floats)
+{
+    std::vector<std::pair<uint64_t, uint64_t>> rng;
+    rng.reserve(P.rows.size());
+    for (size_t i = 0; i < P.rows.size(); ++i) {
+        if (specs[i].series >= nseries) throw std::invalid_argument("fold: series index out of range");
+        const uint64_t lo = P.rows[i].out_off, len = fold_result_floats(P.rows[i]);
+        if (lo > out_floats || len > out_floats - lo)
+            throw std::invalid_argument("fold: result range exceeds the output buffer");
+        rng.emplace_back(lo, lo + len);
+    }
+    std::sort(rng.begin(), rng.end());
+    for (size_t i = 1; i < rng.size(); ++i)
+        if (rng[i].first < rng[i - 1].second) throw std::invalid_argument("fold: result ranges overlap");
+}
+
+// Pinned staging buffers of the descriptor tables.  A buffer belongs to the
+// call that filled it until the stream has passed the copy out of it (its
+// event); later calls reuse the buffers whose event has completed.
+struct FoldStage {
+    void* h = nullptr;
+    size_t bytes = 0;
+    hipEvent_t ev = nullptr;
+    int device = 0;
+    bool pending = false;
+};
+std::mutex g_fold_mu;
+std::vector<FoldStage*> g_fold_stages;
+
+FoldStage* fold_stage_acquire(size_t bytes)   // g_fold_mu held
+{
+    int device = 0;
+    ck(hipGetDevice(&device), "hipGetDevice");
+    for (FoldStage* st : g_fold_stages) {
+        if (st->device != device || st->bytes < bytes) continue;
+        if (st->pending && hipEventQuery(st->ev) != hipSuccess) continue;
+        st->pending = false;
+        return st;
+    }
+    std::unique_ptr<FoldStage> st(new FoldStage());
+    st->device = device;
+    st->bytes = std::max<size_t>(bytes, 4096);
+    ck(hipHostMalloc(&st->h, st->bytes, hipHostMallocDefault), "hipHostMalloc");
+    if (hipEventCreateWithFlags(&st->ev, hipEventDisableTiming) != hipSuccess) {
+        (void)hipHostFree(st->h);
+        throw HipError("hipEventCreate failed");
+    }
+    g_fold_stages.push_back(st.get());
+    return st.release();
+}
+
+void run_fold(const FoldPlan& P, const rt_fold_spec* specs, const float* d_data, size_t size, size_t data_stride,
+              float* d_out, void* d_ws, hipStream_t s)
+{
+    const size_t nr = P.rows.size(), ns = P.sub.size();
+    FoldCand* d_rows = (FoldCand*)d_ws;
+    FoldCand* d_sub = d_rows + nr;
+    float* rows_ws = (float*)((char*)d_ws + P.table_bytes);
+    {
+        std::lock_guard<std::mutex> lk(g_fold_mu);
+        FoldStage* st = fold_stage_acquire((nr + ns) * sizeof(FoldCand));
+        FoldCand* h = (FoldCand*)st->h;
+        for (size_t i = 0; i < nr; ++i) {
+            h[i] = P.rows[i];
+            h[i].src_off = (uint64_t)specs[i].series * data_stride;
+        }
+        for (size_t i = 0; i < ns; ++i) h[nr + i] = P.sub[i];
+        ck(hipMemcpyAsync(d_rows, h, (nr + ns) * sizeof(FoldCand), hipMemcpyHostToDevice, s), "fold table H2D");
+        st->pending = true;
+        ck(hipEventRecord(st->ev, s), "hipEventRecord");
+    }
+    ck(launch_fold_rows(d_data, size, d_rows, (uint32_t)nr, P.rows_blocks, d_out, rows_ws, s), "fold_rows");
+    ck(launch_fold_subints(d_sub, (uint32_t)ns, P.sub_blocks, d_out, rows_ws, s), "fold_subints");
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -1128,6 +1294,61 @@ int rt_downsample_rows(const float* x, size_t rows, size_t size, double f, float
                                     (uint32_t)rows, c.stream),
            "downsample");
         d2h(out, dz, rows * n * 4, c.stream);
+        sync(c.stream);
+        return RT_OK;
+    });
+}
+
+int rt_fold_shape(size_t size, double factor, size_t bins, size_t subints, size_t* m, size_t* rows)
+{
+    return guarded([&] {
+        const FoldShape s = fold_shape(size, factor, bins, subints);
+        if (m) *m = s.m;
+        if (rows) *rows = s.rows;
+        return RT_OK;
+    });
+}
+
+int rt_fold_workspace_bytes(size_t size, const rt_fold_spec* specs, size_t nspecs, size_t* bytes)
+{
+    return guarded([&] {
+        const size_t need = fold_plan(size, specs, nspecs).ws_bytes;
+        if (bytes) *bytes = need;
+        return RT_OK;
+    });
+}
+
+int rt_fold_device(const float* d_data, size_t size, size_t data_stride, size_t nseries, const rt_fold_spec* specs,
+                   size_t nspecs, float* d_out, size_t out_floats, void* d_ws, size_t ws_bytes, void* stream)
+{
+    return guarded([&] {
+        if (!nspecs) return RT_OK;
+        const FoldPlan P = fold_plan(size, specs, nspecs);
+        fold_check_ranges(P, specs, nseries, out_floats);
+        if (data_stride < size) throw std::invalid_argument("fold: data_stride is shorter than the series");
+        if (ws_bytes < P.ws_bytes) throw std::invalid_argument("workspace too small");
+        if (!d_data || !d_out || !d_ws) throw std::invalid_argument("fold: null device pointer");
+        run_fold(P, specs, d_data, size, data_stride, d_out, d_ws, (hipStream_t)stream);
+        return RT_OK;
+    });
+}
+
+int rt_fold(const float* x, size_t size, size_t nseries, const rt_fold_spec* specs, size_t nspecs, float* out,
+            size_t out_floats)
+{
+    return guarded([&] {
+        if (!nspecs) return RT_OK;
+        const FoldPlan P = fold_plan(size, specs, nspecs);
+        fold_check_ranges(P, specs, nseries, out_floats);
+        if (!x || !out) throw std::invalid_argument("fold: null buffer");
+        std::lock_guard<std::mutex> lk(g_mu);
+        Context& c = context();
+        float* dx = dev<float>(c, 0, nseries * size);
+        float* dz = dev<float>(c, 1, out_floats);
+        void* dw = c.buf[2].get(P.ws_bytes);
+        h2d(dx, x, nseries * size * 4, c.stream);
+        run_fold(P, specs, dx, size, size, dz, dw, c.stream);
+        d2h(out, dz, out_floats * 4, c.stream);
         sync(c.stream);
         return RT_OK;
     });

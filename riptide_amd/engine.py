@@ -199,6 +199,44 @@ def deredden_normalise(data, width_samples, min_points=101, deredden=True, norma
     return out[0] if squeeze else out
 
 
+def fold_device(data, tsamp, specs, stream=None):
+    """folding.fold for a batch of candidates of device-resident series
+    (rt_fold_device): data float32 [N] or [B, N], specs a list of
+    (series, period, bins, subints).  Returns one device tensor per spec,
+    (bins,) or (rows, bins), all views of one output allocation, bit-identical
+    to folding.fold of the same series.  Stream-ordered, no host
+    synchronisation.  Raises folding.fold's ValueErrors."""
+    import torch
+    from .folding import pack_fold_specs
+    if data.dim() == 1:
+        data = data.unsqueeze(0)
+    if data.dim() != 2 or data.dtype != torch.float32 or data.device.type != "cuda" or data.stride(1) != 1:
+        raise ValueError("data must be float32 [B, N] device rows with unit stride")
+    specs = list(specs)
+    if not specs:
+        return []
+    B, N = data.shape
+    for series, _, bins, _ in specs:
+        if not 0 <= int(series) < B:
+            raise ValueError(f"series index {series} outside the {B} rows of data")
+        if int(bins) < 2:
+            raise ValueError("the device fold needs bins >= 2")
+    table, shapes, total = pack_fold_specs(N, N * float(tsamp), float(tsamp), specs)
+    need = ctypes.c_size_t()
+    _check(_L.rt_fold_workspace_bytes(N, _lib.ptr(table), len(specs), ctypes.byref(need)))
+    s = stream if stream is not None else torch.cuda.current_stream(data.device)
+    with torch.cuda.device(data.device), torch.cuda.stream(s):
+        out = torch.empty(total, dtype=torch.float32, device=data.device)
+        workspace = torch.empty(max(need.value, 1), dtype=torch.uint8, device=data.device)
+        _check(_L.rt_fold_device(_lib.ptr(data), N, data.stride(0), B, _lib.ptr(table), len(specs), _lib.ptr(out),
+                                 total, _lib.ptr(workspace), workspace.numel(), _stream_handle(s)))
+    results = []
+    for k, shape in enumerate(shapes):
+        o = int(table["out_off"][k])
+        results.append(out[o:o + int(np.prod(shape))].view(*shape))
+    return results
+
+
 def profile_enable(on=True):
     _check(_L.rt_profile_enable(int(bool(on))))
 

@@ -62,3 +62,84 @@ def fold(ts, period, bins, subints=None):
     if subints is None or subints == m:
         return folded
     return downsample_vertical(folded, m / subints)
+
+
+# rt_fold_spec (include/riptide_amd.h)
+FOLD_SPEC = np.dtype([("factor", "<f8"), ("out_off", "<u8"), ("series", "<u4"), ("bins", "<u4"),
+                      ("subints", "<u4"), ("reserved", "<u4")], align=True)
+
+
+def check_fold_args(length, tsamp, period, bins, subints):
+    """fold()'s argument checks, with its messages, for a series of `length`
+    seconds: (downsampling factor, subints as int or None)."""
+    if period > length:
+        raise ValueError("Period exceeds data length")
+    tbin = period / bins
+    if not tbin > tsamp:
+        raise ValueError("Bin width is shorter than sampling time")
+    if subints is not None:
+        subints = int(subints)
+        if not subints >= 1:
+            raise ValueError("subints must be >= 1 or None")
+        full_periods = length / period
+        if subints > full_periods:
+            raise ValueError(f"subints ({subints}) exceeds the number of signal periods that fit in the data "
+                             f"({full_periods})")
+    return tbin / tsamp, subints
+
+
+def fold_shape(nsamp, factor, bins, subints):
+    """Shape of fold()'s result, from the engine (rt_fold_shape, host only)."""
+    import ctypes
+    L = _lib.load()
+    m, rows = ctypes.c_size_t(), ctypes.c_size_t()
+    _lib.check(L.rt_fold_shape(int(nsamp), float(factor), int(bins), int(subints or 0), ctypes.byref(m),
+                               ctypes.byref(rows)))
+    return (rows.value, int(bins)) if rows.value else (int(bins),)
+
+
+def pack_fold_specs(nsamp, length, tsamp, specs):
+    """rt_fold_spec table and result shapes of (series, period, bins, subints)
+    specs, results packed back to back: (table, shapes, total floats)."""
+    table = np.zeros(len(specs), dtype=FOLD_SPEC)
+    shapes, off = [], 0
+    for k, (series, period, bins, subints) in enumerate(specs):
+        bins = int(bins)
+        factor, subints = check_fold_args(length, tsamp, period, bins, subints)
+        shape = fold_shape(nsamp, factor, bins, subints)
+        table[k] = (factor, off, int(series), bins, subints or 0, 0)
+        shapes.append(shape)
+        off += int(np.prod(shape))
+    return table, shapes, off
+
+
+def fold_many(ts, specs):
+    """fold(ts, period, bins, subints) for every (period, bins, subints) of
+    `specs`, bit-identical to a loop of fold(): the series is uploaded once
+    and every candidate is folded by one batched device call (rt_fold), where
+    the loop pays two uploads and two synchronisations per candidate.  A spec
+    with bins == 1 (numpy sums a one-column array pairwise, an order the
+    kernels do not reproduce) is served by fold().
+
+    One difference from the loop: a period so close to the series length
+    that it passes fold()'s checks and still leaves no whole period
+    (floor(nsamp / factor) < bins, m == 0) raises ValueError here, as
+    rt_fold's contract demands; fold() fails there too, but with the
+    ZeroDivisionError of (0 * factor) ** -0.5."""
+    specs = [(p, int(b), s) for p, b, s in specs]
+    results = [None] * len(specs)
+    dev = [k for k, (_, b, _) in enumerate(specs) if b != 1]
+    for k, (p, b, s) in enumerate(specs):
+        if b == 1:
+            results[k] = fold(ts, p, b, s)
+    if not dev:
+        return results
+    data = np.ascontiguousarray(ts.data, dtype=np.float32)
+    table, shapes, total = pack_fold_specs(data.size, ts.length, ts.tsamp, [(0,) + specs[k] for k in dev])
+    out = np.empty(total, dtype=np.float32)
+    L = _lib.load()
+    _lib.check(L.rt_fold(_lib.ptr(data), data.size, 1, _lib.ptr(table), len(dev), _lib.ptr(out), out.size))
+    for j, k in enumerate(dev):
+        o = int(table["out_off"][j])
+        results[k] = out[o:o + int(np.prod(shapes[j]))].reshape(shapes[j]).copy()
+    return results

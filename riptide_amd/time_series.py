@@ -70,6 +70,13 @@ class TimeSeries:
         else:
             return TimeSeries(downsample(self.data, factor), factor * self.tsamp, metadata=self.metadata)
 
+    def fold(self, period, bins, subints=None):
+        """Fold at `period` seconds into `bins` phase bins: (subints, bins), or
+        (bins,) for a single sub-integration; None = one sub-integration per
+        whole period (time_series.py:147-168)."""
+        from .folding import fold
+        return fold(self, period, bins, subints=subints)
+
     @classmethod
     def generate(cls, length, tsamp, period, phi0=0.5, ducy=0.02, amplitude=10.0, stdnoise=1.0):
         """Noisy von Mises pulse train (time_series.py:170-218)."""
