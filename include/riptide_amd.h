@@ -112,6 +112,18 @@ int rt_schedule_check(size_t size, double tsamp, size_t num_widths, double perio
                       uint64_t* launches, double* alg_bytes_per_trial, double* moved_bytes_per_trial,
                       uint64_t* cells_per_trial);
 
+/* Host-only: the pass schedule rt_plan_create builds for these parameters and
+ * boxcar widths (built and validated as in rt_schedule_check), with its final
+ * launches -- the ones that end in the fused S/N -- counted by S/N kind: the
+ * row-group form and the segmented form (rows of 240-264 bins, widths <= 9,
+ * <= 64 rows per unit) run separate kernel instances, so no launch mixes them.
+ * *launches = all cone launches; bins_kinds[b] for b < bins_cap gets bit 0 if
+ * a final unit of b phase bins runs in a row-group launch, bit 1 if one runs
+ * in a segmented launch.  Every output pointer may be NULL. */
+int rt_schedule_final_kinds(size_t size, double tsamp, const uint64_t* widths, size_t num_widths, double period_min,
+                            double period_max, size_t bins_min, size_t bins_max, uint64_t* launches,
+                            uint64_t* rows_launches, uint64_t* seg_launches, uint8_t* bins_kinds, size_t bins_cap);
+
 /* Host-only: the downsampling-ladder kernel a periodogram plan of these
  * parameters runs (periodogram.hpp:162-168 restated per rung): *fused = 1
  * for the one-read fused ladder (32-bit sample indices: series below 2^29

@@ -13,7 +13,10 @@ extern "C" {
  * device carries one unit that breaks the cone kernel's budget, so the kernel
  * refuses it and raises the plan's error flag -- exercises rt_plan_check and
  * the host-buffer API's error path
- * (tests/test_gpu_e2e.py::test_plan_device_error_flag). */
+ * (tests/test_gpu_e2e.py::test_plan_device_error_flag).  on == 2: instead,
+ * the plan's first segmented-S/N final unit is marked a row-group one, a
+ * unit of another kind than its launch's kernel instance, which the kernel
+ * refuses the same way (tests/test_gpu_snr_kinds.py). */
 int rt_test_corrupt_next_plans(int on);
 
 #ifdef __cplusplus

@@ -51,6 +51,8 @@ _SIGNATURES = {
     "rt_ffa_schedule_check": (_c_i, [_c_sz, _c_sz, _pu64]),
     "rt_schedule_check": (_c_i, [_c_sz, _c_d, _c_sz, _c_d, _c_d, _c_sz, _c_sz, _pu64, _pu64, _pu64, _pd, _pd,
                                  _pu64]),
+    "rt_schedule_final_kinds": (_c_i, [_c_sz, _c_d, _vp, _c_sz, _c_d, _c_d, _c_sz, _c_sz, _pu64, _pu64, _pu64, _vp,
+                                       _c_sz]),
     "rt_plan_create": (_c_i, [_c_sz, _c_d, _vp, _c_sz, _c_d, _c_d, _c_sz, _c_sz, _vp]),
     "rt_plan_destroy": (None, [_vp]),
     "rt_plan_shape": (_c_i, [_vp, _psz, _psz]),

@@ -288,10 +288,18 @@ struct DevicePlan {
         // whole-node unit more merge levels than any kernel instance runs,
         // after the host validation, so the kernel's own check refuses it and
         // sets the error flag (exercises rt_plan_check)
-        if (g_test_corrupt.load(std::memory_order_relaxed))
+        if (g_test_corrupt.load(std::memory_order_relaxed) == 1)
             for (UnitDesc& d : u)
                 if (d.mode == kModeWhole) {
                     d.levels = kMaxLevels + 1;
+                    break;
+                }
+        // ... or (2) mark the first segmented-S/N final unit as a row-group
+        // one: a unit of the other kind than its launch's kernel instance
+        if (g_test_corrupt.load(std::memory_order_relaxed) == 2)
+            for (UnitDesc& d : u)
+                if (d.dst == kSelSnrSeg) {
+                    d.dst = kSelSnr;
                     break;
                 }
 #endif
@@ -341,7 +349,7 @@ void cone_launch(const DevicePlan& P, const Launch& L, ConeArgs a, uint32_t batc
         r.moved = L.moved_bytes * batch;
         ck(hipEventRecord(r.a, s), "hipEventRecord");
     }
-    ck(launch_cone(a, L.smax, L.rw, L.wide_snr != 0, L.snr != 0, s), "cone_kernel");
+    ck(launch_cone(a, L.smax, L.rw, L.wide_snr != 0, L.snr, s), "cone_kernel");
     if (prof) {
         ck(hipEventRecord(r.b, s), "hipEventRecord");
         std::lock_guard<std::mutex> lk(g_prof.mu);
@@ -1515,36 +1523,45 @@ int rt_ladder_check(size_t size, double tsamp, double pmin, double pmax, size_t 
     });
 }
 
+// The exec plan rt_plan_create would build for these parameters (host only):
+// wmax = the widest boxcar (0: unknown, as rt_schedule_check has no widths).
+static void schedule_plan(size_t size, double tsamp, size_t nw, uint32_t wmax, double pmin, double pmax, size_t bmin,
+                          size_t bmax, ExecPlan& ex)
+{
+    PgramParams prm;
+    prm.size = size;
+    prm.tsamp = tsamp;
+    prm.pmin = pmin;
+    prm.pmax = pmax;
+    prm.bmin = bmin;
+    prm.bmax = bmax;
+    const std::string msg = check_pgram_args(prm);
+    if (!msg.empty()) throw std::invalid_argument(msg);
+    PgramPlan pg;
+    build_pgram_plan(prm, pg);
+    std::vector<FfaXform> xf;
+    for (const Step& s : pg.steps) {
+        if (!s.rows_eval) continue;
+        FfaXform X{};
+        X.p = s.bins;
+        X.m = s.rows;
+        X.rows_eval = s.rows_eval;
+        X.snr_row = s.out_row;
+        xf.push_back(X);
+    }
+    // build_exec_plan validates the schedule (validate_exec_plan: tiles
+    // inside nodes, LDS / register budgets, final pass covers every row,
+    // no launch of mixed S/N kinds)
+    build_exec_plan(xf, true, (uint32_t)nw, scratch_budget_floats(), ex, wmax, cosched_banks());
+}
+
 int rt_schedule_check(size_t size, double tsamp, size_t nw, double pmin, double pmax, size_t bmin, size_t bmax,
                       uint64_t* transforms, uint64_t* items, uint64_t* launches, double* alg_bytes,
                       double* moved_bytes, uint64_t* cells)
 {
     return guarded([&] {
-        PgramParams prm;
-        prm.size = size;
-        prm.tsamp = tsamp;
-        prm.pmin = pmin;
-        prm.pmax = pmax;
-        prm.bmin = bmin;
-        prm.bmax = bmax;
-        const std::string msg = check_pgram_args(prm);
-        if (!msg.empty()) throw std::invalid_argument(msg);
-        PgramPlan pg;
-        build_pgram_plan(prm, pg);
-        std::vector<FfaXform> xf;
-        for (const Step& s : pg.steps) {
-            if (!s.rows_eval) continue;
-            FfaXform X{};
-            X.p = s.bins;
-            X.m = s.rows;
-            X.rows_eval = s.rows_eval;
-            X.snr_row = s.out_row;
-            xf.push_back(X);
-        }
         ExecPlan ex;
-        // build_exec_plan validates the schedule (validate_exec_plan: tiles
-        // inside nodes, LDS / register budgets, final pass covers every row)
-        build_exec_plan(xf, true, (uint32_t)nw, scratch_budget_floats(), ex, 0, cosched_banks());
+        schedule_plan(size, tsamp, nw, 0, pmin, pmax, bmin, bmax, ex);
         uint64_t a = 0;
         double alg = 0, mv = 0;
         for (const Launch& L : ex.launches) {
@@ -1558,6 +1575,35 @@ int rt_schedule_check(size_t size, double tsamp, size_t nw, double pmin, double 
         *alg_bytes = alg;
         *moved_bytes = mv;
         *cells = a;
+        return RT_OK;
+    });
+}
+
+int rt_schedule_final_kinds(size_t size, double tsamp, const uint64_t* widths, size_t nw, double pmin, double pmax,
+                            size_t bmin, size_t bmax, uint64_t* launches, uint64_t* rows_launches,
+                            uint64_t* seg_launches, uint8_t* bins_kinds, size_t bins_cap)
+{
+    return guarded([&] {
+        if (nw > (size_t)kMaxWidths) throw std::invalid_argument("at most 32 trial widths are supported");
+        check_widths(widths, nw, bmin);
+        uint32_t wmax = 0;
+        for (size_t i = 0; i < nw; ++i) wmax = std::max(wmax, (uint32_t)widths[i]);
+        ExecPlan ex;
+        schedule_plan(size, tsamp, nw, wmax, pmin, pmax, bmin, bmax, ex);
+        uint64_t nr = 0, ns = 0;
+        if (bins_kinds) std::fill(bins_kinds, bins_kinds + bins_cap, (uint8_t)0);
+        for (const Launch& L : ex.launches) {
+            if (L.snr == kSnrNone) continue;
+            ++(L.snr == kSnrSeg ? ns : nr);
+            if (!bins_kinds) continue;
+            for (uint32_t i = L.first; i < L.first + L.count; ++i) {
+                const uint32_t p = ex.xf[ex.items[i].xform].p;
+                if (p < bins_cap) bins_kinds[p] |= (uint8_t)(L.snr == kSnrSeg ? 2 : 1);
+            }
+        }
+        if (launches) *launches = ex.launches.size();
+        if (rows_launches) *rows_launches = nr;
+        if (seg_launches) *seg_launches = ns;
         return RT_OK;
     });
 }
@@ -1822,7 +1868,7 @@ int rt_plan_stats(const rt_plan* P, uint64_t* transforms, uint64_t* items, uint6
 #ifdef RT_TEST_HOOKS
 int rt_test_corrupt_next_plans(int on)
 {
-    g_test_corrupt.store(on ? 1 : 0, std::memory_order_relaxed);
+    g_test_corrupt.store(on == 2 ? 2 : (on ? 1 : 0), std::memory_order_relaxed);
     return RT_OK;
 }
 #endif

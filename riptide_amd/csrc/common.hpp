@@ -93,6 +93,15 @@ RT_HD inline bool snr_seg_ok(int p, int wmax, int rows)
     return p >= 8 * kSnrSegCols - 24 && p <= 8 * kSnrSegCols && wmax >= 1 && wmax <= kSnrSegWmax && rows >= 1 &&
            rows <= kSnrSegRows;
 }
+// The one rule for a final unit's S/N form, on the host (the planner keys its
+// final launches by it) and on the device (the segmented instance's check of
+// the units it is given): the segmented form for a unit of a 4/5-slot variant
+// with at least one merge level (its output level is written at the segment
+// stride by the last merge step) whose rows pass snr_seg_ok.
+RT_HD inline bool snr_seg_unit(int smax, int levels, int p, int wmax, int rows)
+{
+    return (smax == 4 || smax == 5) && levels > 0 && snr_seg_ok(p, wmax, rows);
+}
 constexpr int kStageRegs = 45 * 8 / kConeWaves;   // merge: staged values per lane (rows x slots)
 constexpr int kMaxSlots = 45;               // merge: 64-bin slots per row (p <= 2880)
 constexpr int kMaxRowsPerWave = 24;         // merge: staged rows per wave
@@ -259,7 +268,15 @@ enum : uint32_t {
     kConeDiagNoFill = 1u << 23,  // diagnostics only (wrong results): metadata DMA only, no bottom-level fill
     kConeDefaultFeatures = 15u  // every feature bit above
 };
-enum : uint8_t { kSelLeaves = 0, kSelPing = 1, kSelPong = 2, kSelSnr = 3 };
+// kSelSnr / kSelSnrSeg: a final unit, its output level goes to the fused S/N
+// in its row-group (snr_epilogue) or segmented (snr_segments) form -- the
+// planner's decision (plan.cpp snr_kind_of), carried by the unit record
+enum : uint8_t { kSelLeaves = 0, kSelPing = 1, kSelPong = 2, kSelSnr = 3, kSelSnrSeg = 4 };
+RT_HD inline bool is_snr_dst(int dst) { return dst == kSelSnr || dst == kSelSnrSeg; }
+// S/N kind of a cone launch (Launch::snr) and of its kernel instance
+// (cone_kernel's SNR argument): merge-only, final with the row-group S/N,
+// final with the segmented S/N
+enum : uint32_t { kSnrNone = 0, kSnrRows = 1, kSnrSeg = 2 };
 
 // One workgroup of one pass.
 struct ConeItem {
@@ -270,7 +287,7 @@ struct ConeItem {
     uint8_t levels;       // merge levels evaluated by this item
     uint8_t mode;         // kModeWhole / kModeTile
     uint8_t src;          // kSelLeaves / kSelPing / kSelPong
-    uint8_t dst;          // kSelPing / kSelPong / kSelSnr
+    uint8_t dst;          // kSelPing / kSelPong / kSelSnr / kSelSnrSeg
     uint32_t pad;
 };
 static_assert(sizeof(ConeItem) == 28, "ConeItem layout");

@@ -2839,9 +2839,13 @@ __device__ __forceinline__ void snr_epilogue(const ConeArgs& a, const UnitView& 
 // two workgroups per CU: a unit's DMA is waited for at its start, the CU's
 // other workgroup filling the wait.
 //   begin(u) [DMA] | wait | merge(u) | store or S/N(u)
-// SNR: the launch's units all end in the fused S/N (final passes) -- or none
-// does (the merge-only passes store their output level): separate instances,
-// so a merge-only launch carries no S/N code and no S/N register floor.
+// SNR (kSnrNone / kSnrRows / kSnrSeg): the launch's units all end in the
+// fused S/N (final passes), all in its row-group form (snr_epilogue) or all in
+// its segmented form (snr_segments) -- or none does (the merge-only passes
+// store their output level): separate instances, so a merge-only launch
+// carries no S/N code and no S/N register floor, and a final launch only its
+// own form's (the planner keys final launches by the form, plan.cpp
+// final_snr_kind; the segmented form exists for the 4/5-slot instances).
 // WIDE: final units whose S/N takes the widths past its register window as
 // plain LDS windows (snr_wide_ok; a separate instantiation, so the plans
 // without such widths run code without it)
@@ -2853,9 +2857,13 @@ template <int SMAX> constexpr bool kTrialLoop = false;   // A/B build: one trial
 template <int SMAX> constexpr bool kTrialLoop = SMAX >= 4;
 #endif
 
-template <int SMAX, int RWT, bool WIDE, bool SNR>
+template <int SMAX, int RWT, bool WIDE, uint32_t SNR>
 __global__ __launch_bounds__(kConeBlock, kConeWavesPerSimd) void cone_kernel(ConeArgs a)
 {
+    constexpr bool FIN = SNR != kSnrNone;   // a final launch
+    constexpr bool SEG = SNR == kSnrSeg;    // ... of the segmented S/N
+    static_assert(SNR <= kSnrSeg && (!WIDE || SNR == kSnrRows), "S/N kind");
+    static_assert(!SEG || (resolved_slots(SMAX) && RWT == 0), "the segmented S/N: 4/5-slot instances");
     constexpr int RW = RWT ? RWT : merge_rows_per_wave(SMAX);   // register rows per wave
     __shared__ __attribute__((aligned(16))) float data[kLdsBufFloats + kLdsPadFloats];
     __shared__ __attribute__((aligned(16))) uint32_t aux[kAuxWords + kLutPad];   // the host blob (+ roll table)
@@ -2901,10 +2909,17 @@ __global__ __launch_bounds__(kConeBlock, kConeWavesPerSimd) void cone_kernel(Con
     float* const buf = data;
     // the launch kind is the unit's (the planner splits final and merge-only
     // launches; validate_exec_plan)
-    ok = ok && ((U.dst == kSelSnr) == SNR);
+    // -- a final launch's instance also the unit's S/N form: a unit planned
+    // for the segmented form runs the row-group one where the feature bit is
+    // off at run time (launch_cone picks the instance by the same rule)
+    {
+        const uint32_t ukind = U.dst == kSelSnrSeg ? ((a.flags & kConeSnrSeg) ? kSnrSeg : kSnrRows)
+                                                   : (U.dst == kSelSnr ? kSnrRows : kSnrNone);
+        ok = ok && ukind == SNR;
+    }
     // a final pass's per-width S/N constants, published by the barrier below
     // (the S/N row passes have no barrier of their own)
-    if (SNR && tid < (int)a.num_widths) snr_width_consts(wl[tid], p, whb + 2 * tid);
+    if (FIN && tid < (int)a.num_widths) snr_width_consts(wl[tid], p, whb + 2 * tid);
     // the roll table of a 4-slot unit (past its blob's LDS part, which the
     // DMA may still be writing), published by the barrier below
     if constexpr (SMAX == 4)
@@ -2922,6 +2937,11 @@ __global__ __launch_bounds__(kConeBlock, kConeWavesPerSimd) void cone_kernel(Con
     lds_barrier();
     RT_MARK(1);
     RT_MARK(2);
+    // the segmented instance runs only the units of its form (snr_seg_unit,
+    // the planner's rule: <= 64 output rows in segment slots, widths <= 9),
+    // with the slot tables whose last step writes those slots
+    if constexpr (SEG)
+        ok = ok && C.slots && snr_seg_unit(SMAX, L, p, wl[kMaxWidths], rows_at(C, 0));
     if (!ok) {
         if (tid == 0 && a.error_flag) atomicOr(a.error_flag, 1);
         return;
@@ -2929,7 +2949,7 @@ __global__ __launch_bounds__(kConeBlock, kConeWavesPerSimd) void cone_kernel(Con
     // merge levels, deepest first; a non-final pass stores its output level
     // straight from registers (st), a final pass keeps it in LDS for the S/N
     // epilogue
-    constexpr bool st = !SNR;
+    constexpr bool st = !FIN;
     const bool st_regs = st && (a.flags & kConeStoreFromRegs);
     const uint32_t o0 = (uint32_t)(U.node_start + U.s0) * (uint32_t)p * 4u;
     const int n0 = rows_at(C, 0);
@@ -2937,20 +2957,17 @@ __global__ __launch_bounds__(kConeBlock, kConeWavesPerSimd) void cone_kernel(Con
     // epilogue's lane groups (two rows of 16 lanes per 32-lane LDS group, odd
     // chunk strides) then read and write on distinct banks (at stride p they
     // collided on up to 10 of 32 banks)
-    int qout = p;
-    // the segmented S/N (snr_segments): rows of 240-264 bins, widths <= 9,
-    // <= 64 rows in slots of kSnrSegStride floats (feature bit kConeSnrSeg)
-    // (not in the WIDE instances: widths past kSnrWin exclude it, and their
-    // code stays free of its registers)
-    const bool seg_snr = SNR && !WIDE && resolved_slots(SMAX) && (a.flags & kConeSnrSeg) && L > 0 && C.slots &&
-                         snr_seg_ok(p, wl[kMaxWidths], n0);
+    // (the segmented S/N, snr_segments: rows of 240-264 bins, widths <= 9,
+    // <= 64 rows in slots of kSnrSegStride floats -- a compile-time constant
+    // in its instance, which holds none of the strides selected below)
+    int qout = SEG ? kSnrSegStride : p;
     // short rows keep their blob's LDS part at the end of the level buffer,
     // which a final pass's output level (at the S/N stride) and its S/N's
     // dummy words may overwrite: every trial's fill then re-DMAs it -- unless
     // the output level at the short-row S/N stride ends below the blob (set
     // below: that stride takes the S/N's whole-chunk path, which writes no
     // dummy words, only the rows [0, n0 q) and their wrapped extensions)
-    bool blob_clobbered = SMAX == kPack2 && SNR;
+    bool blob_clobbered = SMAX == kPack2 && FIN;
     // short rows in (row, segment) tasks: every level above the fill at the
     // odd stride pack_stride(p)
     if constexpr (SMAX == kPack2) {
@@ -2959,7 +2976,7 @@ __global__ __launch_bounds__(kConeBlock, kConeWavesPerSimd) void cone_kernel(Con
         // unit's rows fit (over the blob: the blob is dead once the last
         // merge step has read its table, a barrier before the level's
         // write-back)
-        if (SNR && L > 0 && p >= kPackSeg && (a.flags & kConeSnrStride)) {
+        if (FIN && L > 0 && p >= kPackSeg && (a.flags & kConeSnrStride)) {
             const int qf = snr_short_stride(p);
             if (n0 * qf <= kLdsDataFloats) qout = qf;
             // the blob survives the S/N: loaded once per workgroup, not per
@@ -2968,15 +2985,13 @@ __global__ __launch_bounds__(kConeBlock, kConeWavesPerSimd) void cone_kernel(Con
             if (qout == qf && n0 * qf + U.run_off <= kLdsBufFloats) blob_clobbered = false;
         }
     }
-    if constexpr (SMAX <= 5 && SMAX != kPack2) {
+    if constexpr (SMAX <= 5 && SMAX != kPack2 && !SEG) {
         // = 16 (mod 32) and >= p + kSnrMaxChunk (room for the S/N's whole-
         // chunk prefix writes and its wrapped prefix extension), else >=
         // p + kSnrWin (the extension only)
         const int qa = p + kSnrMaxChunk + ((16 - ((p + kSnrMaxChunk) & 31)) & 31);
         const int qb = p + kSnrWin + ((16 - ((p + kSnrWin) & 31)) & 31);
-        if (seg_snr) {
-            qout = kSnrSegStride;
-        } else if (!st && L > 0 && C.slots && (a.flags & kConeFuse2) && (a.flags & kConeSnrStride)) {
+        if (!st && L > 0 && C.slots && (a.flags & kConeFuse2) && (a.flags & kConeSnrStride)) {
             qout = n0 * qa <= kLdsDataFloats ? qa : (n0 * qb <= kLdsDataFloats ? qb : p);
             // widths past the register window: a stride with room for their
             // plain-LDS windows (snr_wide_stride), = 16 (mod 32) where that
@@ -3009,7 +3024,7 @@ __global__ __launch_bounds__(kConeBlock, kConeWavesPerSimd) void cone_kernel(Con
         };
         if (L > 0 && !(a.flags & kConeDiagNoMerge))
             merge_levels<SMAX, RW>(C, buf, p, L, tid, st_regs, rs, o0, a.flags, buf + kLdsBufFloats + 4 + (tid & 63),
-                                   qout, seg_snr ? 8 * kSnrSegCols - p : 0, fill_next);
+                                   qout, SEG ? 8 * kSnrSegCols - p : 0, fill_next);
         RT_MARK(3);
         // the output level: dense rows from the buffer start, or (no merge
         // level) the single bottom row where the DMA left it
@@ -3022,17 +3037,14 @@ __global__ __launch_bounds__(kConeBlock, kConeWavesPerSimd) void cone_kernel(Con
                         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(obase[r * qst + j]), rs,
                                                               (int)(o0 + (uint32_t)(r * p + j) * 4u), 0, kStoreCpol);
             }
-        } else if constexpr (SNR) {
-            if (seg_snr) {
-                if constexpr (resolved_slots(SMAX) && !WIDE)
-                    if (!(a.flags & kConeDiagNoSnr)) snr_segments<SMAX>(a, C.U, buf, wl, n0, tid, whb);
-            } else {
+        } else if constexpr (SEG) {
+            if (!(a.flags & kConeDiagNoSnr)) snr_segments<SMAX>(a, C.U, buf, wl, n0, tid, whb);
+        } else if constexpr (FIN) {
 #ifdef RT_STAMPS
-                if (!(a.flags & kConeDiagNoSnr)) snr_epilogue<SMAX, WIDE>(a, C.U, obase, qout, wl, n0, tid, whb, tl);
+            if (!(a.flags & kConeDiagNoSnr)) snr_epilogue<SMAX, WIDE>(a, C.U, obase, qout, wl, n0, tid, whb, tl);
 #else
-                if (!(a.flags & kConeDiagNoSnr)) snr_epilogue<SMAX, WIDE>(a, C.U, obase, qout, wl, n0, tid, whb, nullptr);
+            if (!(a.flags & kConeDiagNoSnr)) snr_epilogue<SMAX, WIDE>(a, C.U, obase, qout, wl, n0, tid, whb, nullptr);
 #endif
-            }
         }
 #ifdef RT_STAMPS
         lds_barrier();
@@ -3053,7 +3065,7 @@ __global__ __launch_bounds__(kConeBlock, kConeWavesPerSimd) void cone_kernel(Con
             for (int i = 0; i < kStampMarks; ++i) e[1 + i] = tl[i];
             e[1 + kStampMarks] = (unsigned long long)p | ((unsigned long long)L << 16) |
                                  ((unsigned long long)U.mode << 24) | ((unsigned long long)rows_at(C, 0) << 32) |
-                                 ((unsigned long long)(U.dst == kSelSnr) << 48);
+                                 ((unsigned long long)is_snr_dst(U.dst) << 48);
         }
 #endif
         if (!kTrialLoop<SMAX> || !more) break;
@@ -3062,7 +3074,7 @@ __global__ __launch_bounds__(kConeBlock, kConeWavesPerSimd) void cone_kernel(Con
         if (!next_issued) fill_next();
         // a final unit's output level (at the S/N stride) may have covered the
         // zero row: rewritten for the next trial (its first step reads it)
-        if constexpr (resolved_slots(SMAX) && SNR)
+        if constexpr (resolved_slots(SMAX) && FIN)
             if (U.zero_row)
                 for (int j = tid; j < 64 * SMAX; j += kConeBlock) data[U.zero_row + j] = -0.0f;
         ++k;
@@ -3088,25 +3100,34 @@ __global__ __launch_bounds__(kConeBlock, kConeWavesPerSimd) void cone_kernel(Con
 // workgroup slots busy to the end of the launch (measured: 10.37 vs 11.55 ms
 // per cfg2 trial against a persistent grid, round 1).
 template <int SMAX, int RW = 0>
-static hipError_t launch_kind(const ConeArgs& args, dim3 g, dim3 b, bool wide_snr, bool snr, hipStream_t s)
+static hipError_t launch_kind(const ConeArgs& args, dim3 g, dim3 b, bool wide_snr, uint32_t snr, hipStream_t s)
 {
-    if (!snr) {
+    if (snr == kSnrNone) {
         if (wide_snr) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((cone_kernel<SMAX, RW, false, false>), g, b, 0, s, args);
+        hipLaunchKernelGGL((cone_kernel<SMAX, RW, false, kSnrNone>), g, b, 0, s, args);
+    } else if (snr == kSnrSeg) {
+        // the segmented S/N: 4/5-slot units only, never with wide widths
+        if (wide_snr || !resolved_slots(SMAX) || RW != 0) return hipErrorInvalidValue;
+        if constexpr (resolved_slots(SMAX) && RW == 0) hipLaunchKernelGGL((cone_kernel<SMAX, 0, false, kSnrSeg>), g, b, 0, s, args);
+    } else if (snr != kSnrRows) {
+        return hipErrorInvalidValue;
     } else if (wide_snr && SMAX >= 3 && SMAX <= 5 && RW == 0) {
         // (the register-row-class instances have no WIDE form: their S/N
         // reads the wide widths through the general per-width path)
-        if constexpr (SMAX >= 3 && SMAX <= 5 && RW == 0) hipLaunchKernelGGL((cone_kernel<SMAX, 0, true, true>), g, b, 0, s, args);
+        if constexpr (SMAX >= 3 && SMAX <= 5 && RW == 0) hipLaunchKernelGGL((cone_kernel<SMAX, 0, true, kSnrRows>), g, b, 0, s, args);
     } else {
-        hipLaunchKernelGGL((cone_kernel<SMAX, RW, false, true>), g, b, 0, s, args);
+        hipLaunchKernelGGL((cone_kernel<SMAX, RW, false, kSnrRows>), g, b, 0, s, args);
     }
     return hipSuccess;
 }
 
-hipError_t launch_cone(const ConeArgs& args_in, uint32_t smax, uint32_t rw, bool wide_snr, bool snr, hipStream_t s)
+hipError_t launch_cone(const ConeArgs& args_in, uint32_t smax, uint32_t rw, bool wide_snr, uint32_t snr, hipStream_t s)
 {
     if (!args_in.num_items || !args_in.batch) return hipSuccess;
     ConeArgs args = args_in;
+    // a segmented launch with the feature bit off at run time (A/B): its
+    // units run the row-group S/N (cone_kernel's unit-kind check agrees)
+    if (snr == kSnrSeg && !(args.flags & kConeSnrSeg)) snr = kSnrRows;
 #ifdef RT_NO_TRIAL_LOOP
     args.trials_per_wg = 1;
 #else

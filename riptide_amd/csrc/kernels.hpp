@@ -64,8 +64,8 @@ inline uint32_t ds_fused_margin(const DsRung* rungs, size_t num_rungs)
     return m < kDsFusedMargin ? m : kDsFusedMargin;
 }
 // smax: merge_slots() bucket covering every transform of the launch
-hipError_t launch_cone(const ConeArgs& args, uint32_t smax, uint32_t rw, bool wide_snr, bool snr,
-                       hipStream_t s);   // grid (num_items, batch); rw, wide_snr, snr: the Launch's
+hipError_t launch_cone(const ConeArgs& args, uint32_t smax, uint32_t rw, bool wide_snr, uint32_t snr,
+                       hipStream_t s);   // grid (num_items, batch); rw, wide_snr, snr (kSnrNone / kSnrRows / kSnrSeg): the Launch's
 hipError_t launch_ffa_level(const float* in, float* out, const uint2* d_nodes, uint32_t num_nodes,
                             uint32_t rows, uint32_t p, hipStream_t s);
 

@@ -310,6 +310,21 @@ static bool seg_snr(const FfaXform& X, int smax, bool snr_epilogue, uint32_t max
     return true;
 }
 
+// S/N kind of a transform's final pass (common.hpp kSnrRows / kSnrSeg): the
+// segmented form where the plan allows it (seg_snr) and every unit of the
+// pass passes the unit rule (snr_seg_unit: a merge level, <= kSnrSegRows
+// output rows -- final tiles are capped to that, a whole unit may exceed it),
+// so a transform's final units all run in one launch.
+static uint32_t final_snr_kind(const FfaXform& X, int smax, uint32_t max_width, const std::vector<ConeItem>& items)
+{
+    if (!seg_snr(X, smax, true, max_width)) return kSnrRows;
+    for (const ConeItem& it : items) {
+        const int rows = it.mode == kModeTile ? (int)(it.s1 - it.s0) : (int)it.node_size;
+        if (!snr_seg_unit(smax, it.levels, (int)X.p, (int)max_width, rows)) return kSnrRows;
+    }
+    return kSnrSeg;
+}
+
 static uint32_t final_tile_cap(const FfaXform& X, int smax, bool snr_epilogue, uint32_t max_width)
 {
     if (seg_snr(X, smax, snr_epilogue, max_width)) return kSnrSegRows;
@@ -325,6 +340,7 @@ void build_exec_plan(const std::vector<FfaXform>& xforms, bool snr_epilogue, uin
     if (banks != 1 && banks != 2) throw std::invalid_argument("scratch banks: 1 or 2");
     out = ExecPlan();
     out.xf = xforms;
+    out.max_width = max_width;
     for (const FfaXform& X : xforms) {
         if (!merge_slots(X.p)) throw std::invalid_argument("phase bins too large for the LDS cone kernel");
         if ((uint64_t)X.m * X.p * 4u >= kMaxBlockBytes)
@@ -365,11 +381,12 @@ void build_exec_plan(const std::vector<FfaXform>& xforms, bool snr_epilogue, uin
         std::sort(buckets.begin(), buckets.end());
         buckets.erase(std::unique(buckets.begin(), buckets.end()), buckets.end());
         for (uint32_t k = 0; k < gpasses; ++k) {
-            // merge-only and final (fused S/N) units in separate launches, so
-            // each runs a kernel instance without the other's code
-            for (const int bucket : buckets) for (int fin = 0; fin < 2; ++fin) {
+            // merge-only and final (fused S/N) units in separate launches, the
+            // final ones by S/N kind (row-group, segmented), so each runs a
+            // kernel instance without the others' code
+            for (const int bucket : buckets) for (uint32_t kind = kSnrNone; kind <= kSnrSeg; ++kind) {
                 Launch L;
-                L.snr = (uint32_t)fin;
+                L.snr = kind;
                 L.smax = (uint32_t)bucket;
                 L.first = (uint32_t)out.items.size();
                 L.group = group;
@@ -381,8 +398,10 @@ void build_exec_plan(const std::vector<FfaXform>& xforms, bool snr_epilogue, uin
                     const FfaXform& X = out.xf[i];
                     const uint8_t src = k == 0 ? kSelLeaves : (((P - k) % 2 == 0) ? kSelPing : kSelPong);
                     const bool last = (k == P - 1);
-                    if ((last && snr_epilogue) != (fin == 1)) continue;
-                    const uint8_t dst = last ? (snr_epilogue ? kSelSnr : kSelPing)
+                    const uint32_t xkind =
+                        (last && snr_epilogue) ? final_snr_kind(X, bucket, max_width, sp[k].items) : (uint32_t)kSnrNone;
+                    if (xkind != kind) continue;
+                    const uint8_t dst = last ? (snr_epilogue ? (kind == kSnrSeg ? kSelSnrSeg : kSelSnr) : kSelPing)
                                              : (((P - 1 - k) % 2 == 0) ? kSelPing : kSelPong);
                     for (ConeItem it : sp[k].items) {
                         it.src = src;
@@ -1004,9 +1023,17 @@ void validate_exec_plan(const ExecPlan& ex, bool snr_epilogue)
             if (resolved_slots((int)L.smax) && it.levels > 0 &&
                 (it.pad == kNoBlob || ex.blob[it.pad + kHdrSlotWords] == 0))
                 throw std::runtime_error("schedule: 4/5-slot unit without row-slot tables");
-            // the launch's kernel instance is the unit's kind (final: fused S/N)
-            if ((it.dst == kSelSnr) != (L.snr != 0)) throw std::runtime_error("schedule: unit in a launch of the other kind");
-            if (L.wide_snr && !L.snr) throw std::runtime_error("schedule: wide S/N on a merge-only launch");
+            // the launch's kernel instance is the unit's kind (merge-only, or
+            // final with the row-group or the segmented S/N): no launch mixes them
+            const uint32_t ukind = it.dst == kSelSnrSeg ? kSnrSeg : (it.dst == kSelSnr ? kSnrRows : kSnrNone);
+            if (L.snr > kSnrSeg || ukind != L.snr) throw std::runtime_error("schedule: unit in a launch of the other kind");
+            if (L.wide_snr && L.snr != kSnrRows) throw std::runtime_error("schedule: wide S/N on a launch without the row-group S/N");
+            // a segmented unit is one the segmented instance can run (the
+            // rule the kernel checks again: snr_seg_unit)
+            if (ukind == kSnrSeg &&
+                !snr_seg_unit((int)L.smax, it.levels, (int)X.p, (int)ex.max_width,
+                              it.mode == kModeTile ? (int)(it.s1 - it.s0) : (int)it.node_size))
+                throw std::runtime_error("schedule: segmented S/N on a unit outside its shapes");
             // the launch's kernel instance stages enough register rows for every level
             const int rw = L.rw ? (int)L.rw : merge_rows_per_wave((int)L.smax);
             if (it.pad != kNoBlob) {
@@ -1016,7 +1043,7 @@ void validate_exec_plan(const ExecPlan& ex, bool snr_epilogue)
             if (rows > kConeWaves * rw * row_pack((int)L.smax) || rows > lds_row_capacity(X.p, (int)L.smax))
                 throw std::runtime_error("schedule: unit rows exceed its kernel instance's register rows");
             if (L.pass == last_pass[it.xform]) {
-                if (it.node_start != 0 || (snr_epilogue ? it.dst != kSelSnr : it.dst == kSelSnr))
+                if (it.node_start != 0 || snr_epilogue != is_snr_dst(it.dst))
                     throw std::runtime_error("schedule: bad final pass");
                 covered[it.xform] += it.s1 - it.s0;
             }

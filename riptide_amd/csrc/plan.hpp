@@ -54,7 +54,9 @@ struct Launch {
     uint32_t smax = 0;               // cone kernel variant: merge_slots() of every transform in the launch
     uint32_t rw = 0;                 // register rows per wave of the variant (0: merge_rows_per_wave(smax))
     uint32_t wide_snr = 0;           // final units whose S/N reads wide widths as plain LDS windows (WIDE variant)
-    uint32_t snr = 0;                // 1: every unit ends in the fused S/N (a final pass); 0: none does
+    // S/N kind of every unit (common.hpp): kSnrNone, a merge-only pass;
+    // kSnrRows / kSnrSeg, a final pass with the row-group / segmented fused S/N
+    uint32_t snr = 0;
     double alg_bytes = 0;            // 4mp read + (4mp | 4*rows_eval*W) write
     double moved_bytes = 0;          // bytes the items actually read + write (cone overlap incl.)
     uint64_t cells = 0;              // sum m*p of the transforms in this launch
@@ -67,6 +69,7 @@ struct ExecPlan {
     std::vector<uint32_t> blob;      // host-built metadata of every tile item (build_tile_blob)
     uint64_t scratch_floats = 0;     // per ping/pong buffer, per trial (all banks)
     uint32_t max_passes = 0;
+    uint32_t max_width = 0;          // the widest boxcar the plan was built for (0: unknown; the final units' S/N kind)
     // scratch banks: 2 = odd transform groups use a second copy of the
     // scratch (offset bank_floats), so two groups can run at once on two
     // streams (capi.cpp run_cone_launches: co-scheduling)

@@ -6,6 +6,9 @@
 // trusts.  No device call.  Usage:
 //   sched_check pgram N TSAMP PMIN PMAX BMIN BMAX NWIDTHS
 //   sched_check ffa ROWS COLS
+//   sched_check kinds N TSAMP PMIN PMAX BMIN BMAX WIDTH...
+// (kinds: the plan built for these boxcar widths, its final launches by S/N
+// kind -- rt_schedule_final_kinds -- and the bins of the final units of each).
 // Prints one line of results; exit status 0 iff every call returned RT_OK.
 #include <cstdio>
 #include <cstdlib>
@@ -49,6 +52,42 @@ int main(int argc, char** argv)
                     (unsigned long long)rungs);
         return 0;
     }
+    if (argc >= 9 && !std::strcmp(argv[1], "kinds")) {
+        const size_t n = std::strtoull(argv[2], nullptr, 10);
+        const double tsamp = std::atof(argv[3]), pmin = std::atof(argv[4]), pmax = std::atof(argv[5]);
+        const size_t bmin = std::strtoull(argv[6], nullptr, 10), bmax = std::strtoull(argv[7], nullptr, 10);
+        std::vector<uint64_t> widths;
+        for (int i = 8; i < argc; ++i) widths.push_back(std::strtoull(argv[i], nullptr, 10));
+        uint64_t launches = 0, nrows = 0, nseg = 0;
+        std::vector<uint8_t> kinds(bmax + 2, 0);
+        if (rt_schedule_final_kinds(n, tsamp, widths.data(), widths.size(), pmin, pmax, bmin, bmax, &launches, &nrows, &nseg,
+                                    kinds.data(), kinds.size())) {
+            std::printf("kinds: %s\n", rt_last_error());
+            return 1;
+        }
+        std::printf("kinds launches=%llu final_row_group=%llu final_segmented=%llu", (unsigned long long)launches,
+                    (unsigned long long)nrows, (unsigned long long)nseg);
+        // bins ranges of the final units of each kind
+        for (int k = 1; k <= 2; ++k) {
+            std::printf(k == 1 ? " row_group_bins=" : " segmented_bins=");
+            bool any = false;
+            for (size_t b = 0; b < kinds.size();) {
+                if (!(kinds[b] & k)) {
+                    ++b;
+                    continue;
+                }
+                size_t e = b;
+                while (e + 1 < kinds.size() && (kinds[e + 1] & k)) ++e;
+                if (e > b) std::printf("%s%zu-%zu", any ? "," : "", b, e);
+                else std::printf("%s%zu", any ? "," : "", b);
+                any = true;
+                b = e + 1;
+            }
+            if (!any) std::printf("none");
+        }
+        std::printf("\n");
+        return 0;
+    }
     if (argc >= 4 && !std::strcmp(argv[1], "ffa")) {
         uint64_t launches = 0;
         if (rt_ffa_schedule_check(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), &launches)) {
@@ -58,6 +97,7 @@ int main(int argc, char** argv)
         std::printf("ffa launches=%llu\n", (unsigned long long)launches);
         return 0;
     }
-    std::fprintf(stderr, "usage: sched_check pgram N TSAMP PMIN PMAX BMIN BMAX NWIDTHS | ffa ROWS COLS\n");
+    std::fprintf(stderr, "usage: sched_check pgram N TSAMP PMIN PMAX BMIN BMAX NWIDTHS | kinds N TSAMP PMIN PMAX BMIN BMAX "
+                         "WIDTH... | ffa ROWS COLS\n");
     return 2;
 }

@@ -40,7 +40,7 @@ int main(int argc, char** argv)
     double rows = 0, rows_fit = 0, rows_whole = 0, rows_noblob = 0, units = 0;
     std::map<int, double> hist;
     for (const ConeItem& it : ex.items) {
-        if (it.dst != kSelSnr) continue;
+        if (!is_snr_dst(it.dst)) continue;
         const int p = (int)ex.xf[it.xform].p;
         const int n0 = it.mode == kModeTile ? (int)(it.s1 - it.s0) : (int)it.node_size;
         const double r = n0;
