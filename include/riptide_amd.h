@@ -269,6 +269,59 @@ int rt_fold_device(const float* d_data, size_t size, size_t data_stride, size_t 
 int rt_fold(const float* x, size_t size, size_t nseries, const rt_fold_spec* specs, size_t nspecs,
             float* out, size_t out_floats);
 
+/* --------------------------- harmonic flagging ----------------------------- */
+/* riptide/pipeline/harmonic_testing.py (hdiag, htest) and the pair loop of
+ * Pipeline.flag_harmonics (pipeline/pipeline.py:217-249).  A cluster is its
+ * centre's (freq, snr, ducy, dm) in fp64; F is the postulated fundamental, H
+ * the postulated harmonic.  Every value is computed with the reference's own
+ * sequence of fp64 operations; the closest fraction is exactly
+ * Fraction(fast.freq / slow.freq).limit_denominator(denom_max).
+ * Supported range (RT_EINVAL outside it, nothing is launched): finite
+ * positive freq and ducy, tobs > 0, 1 <= denom_max <= 1024, and every
+ * frequency ratio below 2^40. */
+typedef struct rt_htest_params {
+    double   tobs;                 /* integration time, s */
+    double   band;                 /* abs(fmin ** -2 - fmax ** -2), computed by the caller */
+    double   phase_distance_max;
+    double   dm_distance_max;
+    double   snr_distance_max;
+    uint32_t denom_max;
+} rt_htest_params;
+
+/* Host only, no device: hdiag for the npairs pairs (F = cluster pi[k], H =
+ * cluster pj[k]) of n clusters: the fraction H.freq / F.freq as num / den and
+ * the three distances.  Bit-identical to the reference on the same machine
+ * (the square root of num * den is libm's pow(x, 0.5), CPython's int ** 0.5). */
+int rt_hdiag_host(const double* freq, const double* snr, const double* ducy, const double* dm, size_t n,
+                  const int32_t* pi, const int32_t* pj, size_t npairs, const rt_htest_params* params,
+                  int64_t* num, int64_t* den, double* phase_distance, double* dm_distance, double* snr_distance);
+/* The same outputs computed by the device (host buffers, synchronous).  num,
+ * den, phase_distance and dm_distance equal rt_hdiag_host's bit for bit;
+ * snr_distance uses the device's sqrt and is within
+ * 8 * 2^-52 * max(|F.snr|, |H.snr|) of it. */
+int rt_hdiag_pairs(const double* freq, const double* snr, const double* ducy, const double* dm, size_t n,
+                   const int32_t* pi, const int32_t* pj, size_t npairs, const rt_htest_params* params,
+                   int64_t* num, int64_t* den, double* phase_distance, double* dm_distance, double* snr_distance);
+/* Flag the harmonics among n clusters given in rank order (decreasing S/N):
+ * the reference's loop over itertools.combinations, which skips a pair when
+ * either member is already a harmonic.  parent[j] = rank of j's fundamental
+ * or -1; hnum[j] / hden[j] = H.freq / F.freq for a flagged j, 0 / 0 otherwise.
+ * The device tests every pair (i, j > i) tile by tile of block_rows rows
+ * (0 = default) into a bit matrix; the host re-decides with rt_hdiag_host's
+ * arithmetic each pair whose S/N distance is within the guard band of its
+ * bound, then resolves the rows in rank order.  The result equals the host
+ * loop's and does not depend on block_rows.  Device and pinned workspace: two
+ * tiles of at most 4 MiB of words + 32 KiB of pair list each, plus 32 n bytes
+ * of inputs on the device.  n <= 2^24; n <= 1 is RT_OK and tests nothing. */
+int rt_flag_harmonics(const double* freq, const double* snr, const double* ducy, const double* dm, size_t n,
+                      const rt_htest_params* params, size_t block_rows, int32_t* parent, int64_t* hnum,
+                      int64_t* hden);
+/* Counters of this thread's last rt_flag_harmonics: tiles run, pairs the host
+ * re-decided from the near lists, rows decided wholly on the host because
+ * their tile's near list overflowed, and the pair kernel's summed time in
+ * milliseconds (HIP events).  Any pointer may be NULL. */
+int rt_flag_harmonics_stats(uint64_t* tiles, uint64_t* near_pairs, uint64_t* host_rows, double* kernel_ms);
+
 /* --------------------------- file input (device) --------------------------- */
 /* 8-bit SIGPROC samples (riptide/time_series.py:352-357) to float32 in device
  * memory: d_raw holds n bytes, int8 when is_signed else uint8; exact as

@@ -77,6 +77,11 @@ _SIGNATURES = {
     "rt_threshold_select_device": (_c_i, [_vp, _c_sz, _c_sz, _c_sz, _c_sz, _vp, _vp, _c_sz, _c_d, _vp, _vp, _c_sz,
                                           _vp]),
     "rt_ladder_check": (_c_i, [_c_sz, _c_d, _c_d, _c_d, _c_sz, _c_sz, ctypes.POINTER(_c_i), _pu64]),
+    # freq, snr, ducy, dm, n, pi, pj, npairs, params, num, den, phase, dm, snr distances
+    "rt_hdiag_host": (_c_i, [_vp, _vp, _vp, _vp, _c_sz, _vp, _vp, _c_sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rt_hdiag_pairs": (_c_i, [_vp, _vp, _vp, _vp, _c_sz, _vp, _vp, _c_sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rt_flag_harmonics": (_c_i, [_vp, _vp, _vp, _vp, _c_sz, _vp, _c_sz, _vp, _vp, _vp]),
+    "rt_flag_harmonics_stats": (_c_i, [_pu64, _pu64, _pu64, _pd]),
 }
 
 EXPORTED = tuple(_SIGNATURES)

@@ -5,6 +5,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "harmonic.hpp"
 
 namespace rt {
 
@@ -141,5 +142,19 @@ hipError_t launch_fold_rows(const float* data, uint64_t n_in, const FoldCand* d_
                             uint32_t total_blocks, float* out, float* rows_ws, hipStream_t s);
 hipError_t launch_fold_subints(const FoldCand* d_cands, uint32_t num_cands, uint32_t total_blocks, float* out,
                                const float* rows_ws, hipStream_t s);
+
+// harmonic_kernels.hip
+// One tile of the harmonic pair matrix: rows [i0, i0 + rows) of the n ranked
+// clusters, wpr = ceil(n / 64) 64-bit words per row, bit j of row i =
+// htest(i, j) for j > i.  *near_count (zeroed by the caller) counts the pairs
+// the host must decide; the first near_cap of them are listed as (i, j).
+hipError_t launch_harmonic_pairs(const double* freq, const double* snr, const double* ducy, const double* dm,
+                                 uint32_t n, uint32_t i0, uint32_t rows, uint32_t wpr, const HParams& P,
+                                 uint64_t* words, uint2* near_list, uint32_t near_cap, uint32_t* near_count,
+                                 hipStream_t s);
+hipError_t launch_harmonic_diag(const double* freq, const double* snr, const double* ducy, const double* dm,
+                                const int32_t* pi, const int32_t* pj, uint64_t npairs, const HParams& P, int64_t* num,
+                                int64_t* den, double* phase_distance, double* dm_distance, double* snr_distance,
+                                hipStream_t s);
 
 }  // namespace rt
