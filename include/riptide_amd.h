@@ -134,6 +134,32 @@ int rt_schedule_final_kinds(size_t size, double tsamp, const uint64_t* widths, s
 int rt_ladder_check(size_t size, double tsamp, double period_min, double period_max, size_t bins_min,
                     size_t bins_max, int* fused, uint64_t* rungs);
 
+/* Host-only, no device: where a plan of these parameters puts its ladder.
+ * One record per rung that feeds a transform, in ladder order (the rungs
+ * rt_ladder_check counts): a trial's leaf buffer holds rung i as n floats at
+ * float offset leaf_off (16-byte aligned slots; the floats between a rung's
+ * end and the next slot are never written), trial b's buffer at b *
+ * leaf_floats floats from the start of the workspace.  fused = 1: the fused
+ * ladder kernel writes the rung, 0: the per-rung kernel does.
+ * Writes min(*count, cap) records (rungs may be NULL when cap == 0); *mode is
+ * rt_ladder_check's *fused; *margin the samples the fused kernel stages past
+ * each span (ceil(f) + 2 of its widest rung, rounded up to 64, at most 512;
+ * 0 when it does not run).  Every output pointer may be NULL.
+ * This is the layout rt_plan_create builds, from the same code, with one
+ * exception: the environment variable RIPTIDE_AMD_PER_RUNG_LADDER, which
+ * only rt_plan_create honours, sends every rung to the per-rung kernel
+ * (mode 0) and leaves f, n, leaf_off and leaf_floats as reported here. */
+typedef struct rt_ladder_rung {
+    double   f;          /* downsampling factor (1: the series itself) */
+    uint64_t n;          /* samples of the rung, rt_downsampled_size(size, f) */
+    uint64_t leaf_off;   /* float offset in a trial's leaf buffer */
+    uint32_t fused;
+    uint32_t reserved;
+} rt_ladder_rung;
+int rt_ladder_layout(size_t size, double tsamp, double period_min, double period_max, size_t bins_min,
+                     size_t bins_max, rt_ladder_rung* rungs, size_t cap, uint64_t* count, uint64_t* leaf_floats,
+                     int* mode, uint32_t* margin);
+
 /* The pass schedule rt_ffa2 runs for one rows x cols transform, built and
  * validated on the host only (validate_exec_plan: tiles, LDS budgets, unit
  * blobs, DMA segments, row slots); no device needed.  *launches may be NULL. */

@@ -77,6 +77,9 @@ _SIGNATURES = {
     "rt_threshold_select_device": (_c_i, [_vp, _c_sz, _c_sz, _c_sz, _c_sz, _vp, _vp, _c_sz, _c_d, _vp, _vp, _c_sz,
                                           _vp]),
     "rt_ladder_check": (_c_i, [_c_sz, _c_d, _c_d, _c_d, _c_sz, _c_sz, ctypes.POINTER(_c_i), _pu64]),
+    # the six search parameters, rungs (rt_ladder_rung[cap]), cap, count, leaf_floats, mode, margin
+    "rt_ladder_layout": (_c_i, [_c_sz, _c_d, _c_d, _c_d, _c_sz, _c_sz, _vp, _c_sz, _pu64, _pu64,
+                                ctypes.POINTER(_c_i), ctypes.POINTER(ctypes.c_uint32)]),
     # freq, snr, ducy, dm, n, pi, pj, npairs, params, num, den, phase, dm, snr distances
     "rt_hdiag_host": (_c_i, [_vp, _vp, _vp, _vp, _c_sz, _vp, _vp, _c_sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rt_hdiag_pairs": (_c_i, [_vp, _vp, _vp, _vp, _c_sz, _vp, _vp, _c_sz, _vp, _vp, _vp, _vp, _vp, _vp]),

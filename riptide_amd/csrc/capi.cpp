@@ -598,6 +598,7 @@ struct rt_plan {
     // margin) / kLadderHybrid (the rungs that fit take the fused kernel, the
     // wider ones the per-rung kernel: rungs_w, first_block within the subset)
     int ds_mode = 0;
+    uint32_t ds_margin = 0;  // the fused kernel's staged margin (ds_fused_margin of rungs_f)
     std::vector<DsRung> rungs_f, rungs_w;
     DsRung* d_rungs_f = nullptr;
     DsRung* d_rungs_w = nullptr;
@@ -624,6 +625,11 @@ constexpr uint64_t kDsFusedMaxSize = 1ull << 29;
 constexpr int kLadderPerRung = 0, kLadderFused = 1, kLadderHybrid = 2;
 
 bool rung_fusable(const DsRung& d) { return d.identity || std::ceil(d.f) + 2.0 <= (double)kDsFusedMargin; }
+// whether the fused kernel (not the per-rung one) writes rung d of a plan in ladder mode `mode`
+bool rung_in_fused(int mode, const DsRung& d)
+{
+    return mode == kLadderFused || (mode == kLadderHybrid && rung_fusable(d));
+}
 
 // The ladder's kernels for a plan's rungs: every rung in the fused kernel;
 // or, when some rungs' windows exceed its margin (cfg5's long range: factors
@@ -677,6 +683,25 @@ std::vector<DsRung> used_rungs(const PgramPlan& pg)
     return out;
 }
 
+// A plan's whole ladder: the used rungs, the kernels they run in
+// (ladder_split) and the fused kernel's margin (0: it does not run).  What
+// make_plan uploads and run_ladder launches, and what rt_ladder_check and
+// rt_ladder_layout report, all come from here.
+struct LadderPlan {
+    std::vector<DsRung> rungs, rungs_f, rungs_w;
+    int mode = kLadderPerRung;
+    uint32_t margin = 0;
+};
+
+LadderPlan plan_ladder(const PgramPlan& pg)
+{
+    LadderPlan l;
+    l.rungs = used_rungs(pg);
+    l.mode = ladder_split(pg.prm.size, l.rungs, &l.rungs_f, &l.rungs_w);
+    if (l.mode != kLadderPerRung) l.margin = ds_fused_margin(l.rungs_f.data(), l.rungs_f.size());
+    return l;
+}
+
 rt_plan* make_plan(size_t size, double tsamp, const uint64_t* widths, size_t nw, double pmin, double pmax,
                    size_t bmin, size_t bmax)
 {
@@ -719,12 +744,20 @@ rt_plan* make_plan(size_t size, double tsamp, const uint64_t* widths, size_t nw,
         ck(hipMalloc(&P->d_flag, sizeof(int)), "hipMalloc");
         ck(hipMemset(P->d_flag, 0, sizeof(int)), "hipMemset");
         // downsample ladder over the rungs that feed at least one transform
-        P->rungs = used_rungs(P->pg);
+        LadderPlan ladder = plan_ladder(P->pg);
+        if (std::getenv("RIPTIDE_AMD_PER_RUNG_LADDER")) {   // every rung in the per-rung kernel (A/B runs, tests)
+            ladder.mode = kLadderPerRung;
+            ladder.margin = 0;
+            ladder.rungs_f.clear();
+            ladder.rungs_w.clear();
+        }
+        P->rungs = std::move(ladder.rungs);
+        P->rungs_f = std::move(ladder.rungs_f);
+        P->rungs_w = std::move(ladder.rungs_w);
+        P->ds_mode = ladder.mode;
+        P->ds_margin = ladder.margin;
         P->ds_blocks = 0;
         for (const DsRung& d : P->rungs) P->ds_blocks += (uint32_t)((d.n + d.per_block - 1) / d.per_block);
-        P->ds_mode = std::getenv("RIPTIDE_AMD_PER_RUNG_LADDER")
-                         ? kLadderPerRung
-                         : ladder_split(prm.size, P->rungs, &P->rungs_f, &P->rungs_w);
         for (const DsRung& d : P->rungs_w) P->ds_blocks_w += (uint32_t)((d.n + d.per_block - 1) / d.per_block);
         auto upload = [](DsRung*& dst, const std::vector<DsRung>& src) {
             ck(hipMalloc(&dst, std::max<size_t>(1, src.size()) * sizeof(DsRung)), "hipMalloc");
@@ -786,7 +819,7 @@ void run_ladder(const rt_plan* P, const float* d_data, size_t batch, size_t data
     }
     if (P->ds_mode != kLadderPerRung)
         ck(launch_downsample_fused(d_data, P->pg.prm.size, data_stride, P->d_rungs_f, (uint32_t)P->rungs_f.size(),
-                                   ds_fused_margin(P->rungs_f.data(), P->rungs_f.size()), leaves, P->pg.leaf_floats,
+                                   P->ds_margin, leaves, P->pg.leaf_floats,
                                    (uint32_t)batch, s),
            "downsample_fused");
     if (P->ds_mode == kLadderHybrid)
@@ -802,7 +835,7 @@ void run_ladder(const rt_plan* P, const float* d_data, size_t batch, size_t data
         // fused: the series is read once for its rungs; per-rung: once per rung
         double bytes = P->ds_mode != kLadderPerRung ? 4.0 * P->pg.prm.size : 0.0;
         for (const DsRung& d : P->rungs) {
-            const bool fused = P->ds_mode == kLadderFused || (P->ds_mode == kLadderHybrid && rung_fusable(d));
+            const bool fused = rung_in_fused(P->ds_mode, d);
             bytes += 4.0 * (double)d.n + (fused ? 0.0 : (d.identity ? 4.0 * d.n : 4.0 * P->pg.prm.size));
         }
         r.alg = r.moved = bytes * batch;
@@ -1785,9 +1818,44 @@ int rt_ladder_check(size_t size, double tsamp, double pmin, double pmax, size_t 
         if (!msg.empty()) throw std::invalid_argument(msg);
         PgramPlan pg;
         build_pgram_plan(prm, pg);
-        const std::vector<DsRung> r = used_rungs(pg);
-        if (fused) *fused = ladder_split(size, r, nullptr, nullptr);
-        if (rungs) *rungs = r.size();
+        const LadderPlan l = plan_ladder(pg);
+        if (fused) *fused = l.mode;
+        if (rungs) *rungs = l.rungs.size();
+        return RT_OK;
+    });
+}
+
+int rt_ladder_layout(size_t size, double tsamp, double pmin, double pmax, size_t bmin, size_t bmax,
+                     rt_ladder_rung* rungs, size_t cap, uint64_t* count, uint64_t* leaf_floats, int* mode,
+                     uint32_t* margin)
+{
+    return guarded([&] {
+        PgramParams prm;
+        prm.size = size;
+        prm.tsamp = tsamp;
+        prm.pmin = pmin;
+        prm.pmax = pmax;
+        prm.bmin = bmin;
+        prm.bmax = bmax;
+        const std::string msg = check_pgram_args(prm);
+        if (!msg.empty()) throw std::invalid_argument(msg);
+        if (cap && !rungs) throw std::invalid_argument("rt_ladder_layout: rungs is NULL");
+        PgramPlan pg;
+        build_pgram_plan(prm, pg);
+        const LadderPlan l = plan_ladder(pg);
+        for (size_t i = 0; i < l.rungs.size() && i < cap; ++i) {
+            const DsRung& d = l.rungs[i];
+            rt_ladder_rung o{};
+            o.f = d.f;
+            o.n = d.n;
+            o.leaf_off = d.out_off;
+            o.fused = rung_in_fused(l.mode, d);
+            rungs[i] = o;
+        }
+        if (count) *count = l.rungs.size();
+        if (leaf_floats) *leaf_floats = pg.leaf_floats;
+        if (mode) *mode = l.mode;
+        if (margin) *margin = l.margin;
         return RT_OK;
     });
 }

@@ -1,7 +1,7 @@
 // Host-only schedule checker, built with AddressSanitizer + UBSan by
 // `make -C riptide_amd/csrc asan`: drives the host
 // planner and the C ABI's host-only entry points -- rt_periodogram_grid,
-// rt_schedule_check, rt_ffa_schedule_check, rt_ladder_check -- which build
+// rt_schedule_check, rt_ffa_schedule_check, rt_ladder_check, rt_ladder_layout -- which build
 // every unit blob, DMA segment table and row-slot table the cone kernel
 // trusts.  No device call.  Usage:
 //   sched_check pgram N TSAMP PMIN PMAX BMIN BMAX NWIDTHS
@@ -47,6 +47,25 @@ int main(int argc, char** argv)
             std::printf("ladder: %s\n", rt_last_error());
             return 1;
         }
+        // the ladder's layout, first its size alone, then every rung's record
+        uint64_t nr = 0, leaf = 0;
+        int mode = -1;
+        uint32_t margin = 0;
+        if (rt_ladder_layout(n, tsamp, pmin, pmax, bmin, bmax, nullptr, 0, &nr, nullptr, nullptr, nullptr)) {
+            std::printf("ladder layout: %s\n", rt_last_error());
+            return 1;
+        }
+        std::vector<rt_ladder_rung> lr(nr);
+        if (rt_ladder_layout(n, tsamp, pmin, pmax, bmin, bmax, lr.data(), lr.size(), &nr, &leaf, &mode, &margin) ||
+            nr != rungs || mode != fused) {
+            std::printf("ladder layout: %s\n", rt_last_error());
+            return 1;
+        }
+        for (const rt_ladder_rung& r : lr)
+            if (r.leaf_off + r.n > leaf) {
+                std::printf("ladder layout: a rung ends past the leaf buffer\n");
+                return 1;
+            }
         std::printf("pgram L=%zu transforms=%llu items=%llu launches=%llu alg=%.6e moved=%.6e fused=%d rungs=%llu\n", L,
                     (unsigned long long)xf, (unsigned long long)items, (unsigned long long)launches, alg, moved, fused,
                     (unsigned long long)rungs);

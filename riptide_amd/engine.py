@@ -20,6 +20,33 @@ def _stream_handle(stream=None):
     return ctypes.c_void_p(s.cuda_stream)
 
 
+# rt_ladder_rung (include/riptide_amd.h)
+LADDER_RUNG_DTYPE = np.dtype([("f", np.float64), ("n", np.uint64), ("leaf_off", np.uint64), ("fused", np.uint32),
+                              ("reserved", np.uint32)])
+
+
+def ladder_layout(size, tsamp, period_min, period_max, bins_min, bins_max):
+    """Where a plan of these search parameters puts its downsampling ladder
+    (rt_ladder_layout; host only, no device): a dict of
+      rungs        one record per rung that feeds a transform (LADDER_RUNG_DTYPE):
+                   factor f, length n, float offset leaf_off of the rung in a
+                   trial's leaf buffer, fused = 1 if the fused kernel writes it
+      leaf_floats  floats of one trial's leaf buffer (trial b's starts b *
+                   leaf_floats floats into the workspace)
+      mode         0 per-rung kernel, 1 fused, 2 both (rt_ladder_check)
+      margin       samples the fused kernel stages past each span (0: not run)
+    RIPTIDE_AMD_PER_RUNG_LADDER, which only plan creation honours, is not
+    reflected: such a plan has the same offsets and mode 0."""
+    args = (int(size), float(tsamp), float(period_min), float(period_max), int(bins_min), int(bins_max))
+    count, leaf = ctypes.c_uint64(), ctypes.c_uint64()
+    mode, margin = ctypes.c_int(), ctypes.c_uint32()
+    _check(_L.rt_ladder_layout(*args, None, 0, ctypes.byref(count), None, None, None))
+    rungs = np.zeros(count.value, dtype=LADDER_RUNG_DTYPE)
+    _check(_L.rt_ladder_layout(*args, _lib.ptr(rungs), rungs.size, ctypes.byref(count), ctypes.byref(leaf),
+                               ctypes.byref(mode), ctypes.byref(margin)))
+    return {"rungs": rungs, "leaf_floats": leaf.value, "mode": mode.value, "margin": margin.value}
+
+
 class PeriodogramPlan:
     """Compiled periodogram plan for series of `size` samples: downsampling
     ladder, trial grid and the cone-kernel pass schedule (host-built once,
@@ -64,6 +91,10 @@ class PeriodogramPlan:
         b = ctypes.c_size_t()
         _check(_L.rt_plan_workspace_bytes(self._h, int(batch), ctypes.byref(b)))
         return b.value
+
+    def ladder_layout(self):
+        """ladder_layout() of this plan's own search parameters."""
+        return ladder_layout(self.size, self.tsamp, self.period_min, self.period_max, self.bins_min, self.bins_max)
 
     def stats(self):
         u = [ctypes.c_uint64() for _ in range(4)]

@@ -290,3 +290,49 @@ def cfg5_trial(k, n=None):
         data = x.astype(np.float32)
         hdr.update(nbits=32)
     return data, hdr
+
+
+# ---------------------------------------------------------------- downsampling ladder against the oracle
+# Search-parameter sets whose ladders (periodogram.hpp:135-168: rung r has
+# factor f_r = pmin / (tsamp bmin) ((bmax + 1) / bmin)^r and is used while
+# n / f_r >= bmin) reach, between them, every path of the two ladder kernels
+# (tests/test_gpu_ladder.py compares every rung's leaf with oracle.downsample;
+# tests/test_host.py::test_ladder_oracle_cases_cover_the_kernel asserts the
+# coverage listed here through rt_ladder_layout).  LADDER_SPAN is the fused
+# kernel's staged span (kDsPairSpan); a block owns LADDER_SPAN - margin window
+# starts, margin = ceil(f_max) + 2 rounded up to 64.
+LADDER_SPAN = 4864
+
+
+def _ladder_case(name, n, tsamp, f0, bmin, bmax, rungs, pmin_scale=1.0):
+    """`rungs` rungs from factor f0 * pmin_scale on, period_max just inside
+    the last one's range."""
+    pmin = f0 * bmin * tsamp * pmin_scale
+    return dict(name=name, n=n, tsamp=tsamp, pmin=pmin, pmax=f0 * bmin * tsamp * ((bmax + 1) / bmin) ** rungs * 0.999,
+                bmin=bmin, bmax=bmax)
+
+
+LADDER_ORACLE_CASES = [
+    # the identity rung and floor(f) = 1 ... 11 (one template instance each), odd length, margin 64
+    _ladder_case("f1to11", 20011, 1e-3, 1.0, 16, 17, 22),
+    # floor(f) >= 12, f = 12.3 ... 91 and 13.0 ... 97: floor(f) mod 8 takes every
+    # residue between the two (the 8-wide loop, the 2-wide loop and the odd
+    # read of output_large, each taken and not); margin 128, lengths one less
+    # and one more than four spans of 4864 - 128
+    _ladder_case("f12up_a", 4 * (LADDER_SPAN - 128) - 1, 1e-3, 12.3, 16, 17, 18),
+    _ladder_case("f12up_b", 4 * (LADDER_SPAN - 128) + 1, 1e-3, 12.3 * 1.06, 16, 17, 18),
+    # exactly integral factors 2, 4 ... 256 (fract(start) == 0, wmax == 0, window
+    # starts on the span boundaries); 2^15 samples, a multiple of every
+    # factor: each rung's last window ends at n and is clipped to n - 1
+    _ladder_case("pow2", 1 << 15, 2.0 ** -10, 2.0, 16, 31, 8),
+    # the same factors a 2^-40 part below the integers: floor(f) = 1, 3, 7, 15 ... 255
+    _ladder_case("pow2_below", 30001, 2.0 ** -10, 2.0, 16, 31, 8, pmin_scale=1.0 - 2.0 ** -40),
+    # the margin's edge, f = 452.9 and 509.5125 (ceil(f) + 2 == 512), at 2^15 samples
+    dict(LADDER_EDGE_CASE, name="margin512", n=1 << 15),
+    # hybrid: f = 300, 393.75 fused (margin 448), 516.8 and 678.3 past the
+    # margin in the per-rung kernel, whose blocks are renumbered from 0: the
+    # f = 516.8 rung has 261 outputs, two blocks of 256 unstaged windows
+    _ladder_case("hybrid", 135001, 1e-3, 300.0, 16, 20, 4),
+    # shorter than one span: the one block of the fused kernel is its tail block
+    _ladder_case("short", 4099, 1e-3, 1.37, 16, 17, 18),
+]

@@ -91,9 +91,124 @@ def test_ladder_path_choice(lib):
     assert _ladder(lib, 1 << 20, inputs.LADDER_EDGE_CASE)[0] == 1
     over = dict(inputs.LADDER_EDGE_CASE, pmin=inputs.LADDER_EDGE_CASE["pmin"] * 510.5 / 509.5125)
     over["pmax"] = over["pmin"] * 1.125 ** 2 * 0.999
-    assert _ladder(lib, 1 << 20, over)[0] == 2         # the hybrid path: one rung fused, one per-rung
+    # ladder_split: the f = 453.8 rung stays fusable, so the fused list is not
+    # empty and the plan is hybrid (2), never all per-rung (0): one rung fused,
+    # the f = 510.5 one (ceil(f) + 2 == 513) in the per-rung kernel
+    assert _ladder(lib, 1 << 20, over)[0] == 2
+    lay = _layout(1 << 20, over)
+    assert lay["mode"] == 2 and lay["margin"] == 512
+    assert [int(f) for f in lay["rungs"]["f"]] == [453, 510] and lay["rungs"]["fused"].tolist() == [1, 0]
     # every rung past the margin: nothing for the fused kernel
     assert _ladder(lib, 1 << 22, dict(tsamp=64e-6, pmin=40.0, pmax=100.0, bmin=960, bmax=1040))[0] == 0
+
+
+def _layout(n, c):
+    from riptide_amd import engine
+    return engine.ladder_layout(n, c["tsamp"], c["pmin"], c["pmax"], c["bmin"], c["bmax"])
+
+
+def test_ladder_layout_matches_the_planner(lib):
+    """rt_ladder_layout agrees with rt_ladder_check and with the ladder of
+    periodogram.hpp:135-168 restated here: factors f_r = pmin / (tsamp bmin)
+    ((bmax + 1) / bmin)^r, lengths floor(n / f), slots in ladder order that do
+    not overlap, each starting on a multiple of four floats."""
+    cases = [(c["n"], c) for c in inputs.PGRAM_CASES + inputs.LADDER_ORACLE_CASES]
+    cases.append((inputs.CFG5["n"], dict(tsamp=inputs.CFG5["tsamp"], pmin=2.0, pmax=120.0, bmin=960, bmax=1040)))
+    for n, c in cases:
+        lay = _layout(n, c)
+        rungs = lay["rungs"]
+        assert (lay["mode"], rungs.size) == _ladder(lib, n, c)
+        assert rungs.size > 0 and np.all(rungs["reserved"] == 0)
+        ini, geo = c["pmin"] / (c["tsamp"] * c["bmin"]), (c["bmax"] + 1.0) / c["bmin"]
+        ladder = ini * geo ** np.arange(400.0)
+        for r in rungs:
+            assert np.any(np.abs(ladder - r["f"]) <= 4e-16 * r["f"]), r["f"]
+            assert r["n"] == int(np.floor(n / r["f"])) >= c["bmin"]
+        assert np.all(np.diff(rungs["f"]) > 0)
+        assert rungs["leaf_off"][0] == 0 and np.all(rungs["leaf_off"] % 4 == 0)
+        ends = (rungs["leaf_off"] + rungs["n"] + 3) // 4 * 4
+        # (a rung whose transforms all lie past period_max keeps its slot and is not listed)
+        assert np.all(ends[:-1] <= rungs["leaf_off"][1:]) and ends[-1] <= lay["leaf_floats"]
+        if c in inputs.LADDER_ORACLE_CASES:
+            assert np.array_equal(ends[:-1], rungs["leaf_off"][1:]) and ends[-1] == lay["leaf_floats"]
+        fused = rungs["fused"].astype(bool)
+        if lay["mode"] == 0:
+            assert not fused.any() and lay["margin"] == 0
+        else:
+            wide = np.ceil(rungs["f"]) + 2 > 512
+            assert np.array_equal(fused, ~wide) and (lay["mode"] == 2) == bool(wide.any())
+            fmax = rungs["f"][fused & (rungs["f"] != 1.0)].max(initial=0.0)
+            assert lay["margin"] == min(512, (int(max(2.0, np.ceil(fmax) + 2)) + 63) // 64 * 64)
+    # a truncated list: the count is the whole ladder's, only `cap` records are written
+    c = inputs.LADDER_ORACLE_CASES[0]
+    two = np.zeros(3, dtype=_layout(c["n"], c)["rungs"].dtype)
+    count = ctypes.c_uint64()
+    from riptide_amd._lib import ptr
+    assert lib.rt_ladder_layout(c["n"], c["tsamp"], c["pmin"], c["pmax"], c["bmin"], c["bmax"], ptr(two), 2,
+                                ctypes.byref(count), None, None, None) == 0
+    assert count.value == 22 and two["f"][1] == 1.125 and two["n"][2] == 0
+    assert lib.rt_ladder_layout(c["n"], c["tsamp"], 0.0, c["pmax"], c["bmin"], c["bmax"], None, 0, None, None, None,
+                                None) == 1
+
+
+def test_ladder_oracle_cases_cover_the_kernel():
+    """inputs.LADDER_ORACLE_CASES (tests/test_gpu_ladder.py) really holds the
+    classes the ladder kernels branch on, by the plans' own layout: a
+    condition on the case list -- if a class goes missing, the list is what
+    to fix."""
+    src = open(os.path.join(REPO, "riptide_amd", "csrc", "ffa_kernels.hip")).read()
+    assert int(re.search(r"^#define RT_DS_PAIRS (\d+)$", src, re.M).group(1)) == inputs.LADDER_SPAN
+    names = [c["name"] for c in inputs.LADDER_ORACLE_CASES]
+    assert len(set(names)) == len(names)
+    lays = {c["name"]: _layout(c["n"], c) for c in inputs.LADDER_ORACLE_CASES}
+    small, large, integral, identity, blocks, clipped = set(), set(), [], 0, {}, 0
+    for c in inputs.LADDER_ORACLE_CASES:
+        lay = lays[c["name"]]
+        assert 4000 <= c["n"] <= 140000
+        assert lay["mode"] in (1, 2)
+        blocks[c["name"]] = -(-c["n"] // (inputs.LADDER_SPAN - lay["margin"]))
+        for r in lay["rungs"][lay["rungs"]["fused"] == 1]:
+            f = float(r["f"])
+            if f == 1.0:
+                identity += 1
+            elif f < 12:
+                small.add(int(f))
+            else:
+                large.add(int(f))
+            if f > 1.0 and f == int(f):
+                integral.append(int(f))
+            # the last window's end, computed as the kernels do, reaches n: min(floor(end), n - 1) clips it
+            clipped += f > 1.0 and float(r["n"] - 1) * f + f >= c["n"]
+    # (a) every template instance of the fused kernel, and the identity rung
+    assert small == set(range(1, 12)) and identity >= 1
+    # (b) floor(f) >= 12 at every residue mod 8: output_large's 8-wide loop
+    # leaves (F - 2) mod 8 samples, which take the 2-wide loop zero to three
+    # times and the odd single read or not; one and several turns of the 8-wide loop
+    assert {F % 8 for F in large} == set(range(8))
+    assert any(F < 18 for F in large) and any(F >= 26 for F in large)
+    # (c) exactly integral factors, powers of two up to 256, below and above
+    # the F = 12 switch; and their neighbours one part in 2^40 below
+    assert set(integral) >= {2, 4, 8, 16, 32, 64, 128, 256}
+    below = lays["pow2_below"]["rungs"]["f"]
+    assert [int(f) for f in below] == [1, 3, 7, 15, 31, 63, 127, 255]
+    assert np.all(np.ceil(below) - below < 1e-9) and np.all(np.ceil(below) - below > 0)
+    # (d) both fused modes, the widest margin, a hybrid whose per-rung part
+    # has several rungs, blocks beyond each rung's first and unstaged windows
+    assert {lay["mode"] for lay in lays.values()} == {1, 2}
+    edge = lays["margin512"]
+    assert edge["mode"] == 1 and edge["margin"] == 512 and np.ceil(edge["rungs"]["f"].max()) + 2 == 512
+    hyb = lays["hybrid"]
+    wide = hyb["rungs"][hyb["rungs"]["fused"] == 0]
+    assert hyb["mode"] == 2 and wide.size >= 2 and (hyb["rungs"]["fused"] == 1).sum() >= 1
+    assert wide["f"].min() > 124 and wide["n"][0] > 256          # ds_per_block(f) < 32: 256 unstaged outputs per block
+    # (e) first, interior and tail blocks everywhere but in the short case, which is one tail block
+    assert blocks.pop("short") == 1 and min(blocks.values()) >= 3, blocks
+    assert lays["short"]["rungs"].size >= 10 and inputs.LADDER_ORACLE_CASES[-1]["n"] < inputs.LADDER_SPAN
+    spans = {c["name"]: inputs.LADDER_SPAN - lays[c["name"]]["margin"] for c in inputs.LADDER_ORACLE_CASES}
+    rem = {c["n"] % spans[c["name"]] - (spans[c["name"]] if c["n"] % spans[c["name"]] > 1 else 0)
+           for c in inputs.LADDER_ORACLE_CASES}
+    assert {-1, 1} <= rem                     # one less and one more than a multiple of the span
+    assert any(c["n"] % 2 for c in inputs.LADDER_ORACLE_CASES) and clipped >= 8
 
 
 def test_version(lib):
