@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "capi_common.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
 
@@ -26,39 +27,11 @@ using namespace rt;
 
 namespace {
 
-thread_local std::string g_err;
 thread_local int g_device = 0;
-
-int fail(int code, const std::string& msg)
-{
-    g_err = msg;
-    return code;
-}
-
-struct HipError : std::runtime_error {
-    using std::runtime_error::runtime_error;
-};
 
 inline void ck(hipError_t e, const char* what)
 {
     if (e != hipSuccess) throw HipError(std::string(what) + ": " + hipGetErrorString(e));
-}
-
-// Exception barrier for every entry point.
-template <class F>
-int guarded(F&& f)
-{
-    try {
-        return f();
-    } catch (const std::invalid_argument& e) {
-        return fail(RT_EINVAL, e.what());
-    } catch (const HipError& e) {
-        return fail(RT_EHIP, e.what());
-    } catch (const std::exception& e) {
-        return fail(RT_EINTERNAL, e.what());
-    } catch (...) {
-        return fail(RT_EINTERNAL, "unknown error");
-    }
 }
 
 // ---- per-device context for host-buffer calls: stream + grow-only buffers
@@ -119,25 +92,6 @@ void d2h(void* h, const void* d, size_t bytes, hipStream_t s)
 void sync(hipStream_t s) { ck(hipStreamSynchronize(s), "hipStreamSynchronize"); }
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-// Per-trial scratch budget (floats per ping/pong buffer) of one transform group.
-// Tuning knob for experiments: RIPTIDE_AMD_SCRATCH_MFLOATS (millions of floats).
-uint64_t scratch_budget_floats()
-{
-    if (const char* e = std::getenv("RIPTIDE_AMD_SCRATCH_MFLOATS")) {
-        const double v = std::atof(e);
-        if (v > 0) return (uint64_t)(v * 1e6);
-    }
-    return 96ull << 20;   // 384 MiB per ping/pong buffer and trial: ~94 launches per cfg2 plan (sweep_schedule.py)
-}
-
-// Scratch banks of a periodogram plan: 2 (RIPTIDE_AMD_COSCHED=1) runs its
-// transform groups co-scheduled on two streams (run_cone_launches)
-uint32_t cosched_banks()
-{
-    const char* e = std::getenv("RIPTIDE_AMD_COSCHED");
-    return e && e[0] == '1' ? 2u : 1u;
-}
 
 // ---- profiling of cone / downsample launches
 struct ProfRec {
@@ -575,12 +529,6 @@ void ffa_device(const float* d_in, size_t rows, size_t cols, float* d_out, float
     (void)hipFree(d_nodes);
 }
 
-void check_widths(const uint64_t* w, size_t nw, size_t bins)
-{
-    for (size_t i = 0; i < nw; ++i)
-        if (!(w[i] > 0 && w[i] < bins)) throw std::invalid_argument("trial widths must be all > 0 and < columns");
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -591,18 +539,13 @@ struct rt_plan {
     DevicePlan dp;
     std::vector<uint32_t> widths;
     uint32_t* d_widths = nullptr;
-    std::vector<DsRung> rungs;
+    // the ladder (plan.hpp plan_ladder), the device copies of its rung lists
+    // and the per-rung kernel's blocks over `rungs` / `rungs_w`
+    LadderPlan ladder;
     DsRung* d_rungs = nullptr;
-    uint32_t ds_blocks = 0;
-    // kLadderPerRung / kLadderFused (every rung fits the fused ladder's
-    // margin) / kLadderHybrid (the rungs that fit take the fused kernel, the
-    // wider ones the per-rung kernel: rungs_w, first_block within the subset)
-    int ds_mode = 0;
-    uint32_t ds_margin = 0;  // the fused kernel's staged margin (ds_fused_margin of rungs_f)
-    std::vector<DsRung> rungs_f, rungs_w;
     DsRung* d_rungs_f = nullptr;
     DsRung* d_rungs_w = nullptr;
-    uint32_t ds_blocks_w = 0;
+    uint32_t ds_blocks = 0, ds_blocks_w = 0;
     int* d_flag = nullptr;   // sticky device error flag of the cone kernel (rt_plan_check reads and clears it)
     ~rt_plan()
     {
@@ -616,157 +559,44 @@ struct rt_plan {
 
 namespace {
 
-// The fused ladder (downsample_fused_kernel) indexes samples and outputs in
-// 32 bits and stages up to kDsFusedMargin floats past each span: series of 2^29
-// samples or more, rungs whose window (ceil(f) + 2) exceeds the margin, and
-// more rungs than its per-block table take the per-rung kernel (64-bit
-// indices) instead.
-constexpr uint64_t kDsFusedMaxSize = 1ull << 29;
-constexpr int kLadderPerRung = 0, kLadderFused = 1, kLadderHybrid = 2;
-
-bool rung_fusable(const DsRung& d) { return d.identity || std::ceil(d.f) + 2.0 <= (double)kDsFusedMargin; }
-// whether the fused kernel (not the per-rung one) writes rung d of a plan in ladder mode `mode`
-bool rung_in_fused(int mode, const DsRung& d)
-{
-    return mode == kLadderFused || (mode == kLadderHybrid && rung_fusable(d));
-}
-
-// The ladder's kernels for a plan's rungs: every rung in the fused kernel;
-// or, when some rungs' windows exceed its margin (cfg5's long range: factors
-// up to ~1950), the others in the fused kernel and those in the per-rung
-// kernel (hybrid, `f` / `w` the two subsets, w's first_block renumbered);
-// or all per-rung (series of 2^29 samples or more: 32-bit indices; more
-// fusable rungs than the fused kernel's per-block table).
-int ladder_split(size_t size, const std::vector<DsRung>& rungs, std::vector<DsRung>* f, std::vector<DsRung>* w)
-{
-    if ((uint64_t)size >= kDsFusedMaxSize) return kLadderPerRung;
-    std::vector<DsRung> a, b;
-    uint32_t blocks = 0;
-    for (const DsRung& d : rungs) {
-        if (rung_fusable(d)) {
-            a.push_back(d);
-        } else {
-            DsRung e = d;
-            e.first_block = blocks;
-            blocks += (uint32_t)((e.n + e.per_block - 1) / e.per_block);
-            b.push_back(e);
-        }
-    }
-    if (a.empty() || a.size() > kDsMaxRungs || ds_fused_margin(a.data(), a.size()) == 0) return kLadderPerRung;
-    if (f) *f = a;
-    if (w) *w = b;
-    return b.empty() ? kLadderFused : kLadderHybrid;
-}
-
-// The rungs of a periodogram that feed at least one transform, in the
-// ladder kernels' form.
-std::vector<DsRung> used_rungs(const PgramPlan& pg)
-{
-    std::vector<bool> used(pg.rungs.size(), false);
-    for (const Step& s : pg.steps)
-        if (s.rows_eval) used[s.rung] = true;
-    std::vector<DsRung> out;
-    uint32_t blocks = 0;
-    for (size_t r = 0; r < pg.rungs.size(); ++r) {
-        if (!used[r]) continue;
-        const Rung& R = pg.rungs[r];
-        DsRung d{};
-        d.f = R.f;
-        d.n = R.n;
-        d.out_off = R.leaf_off;
-        d.first_block = blocks;
-        d.identity = R.f == 1.0;
-        ds_configure(d);
-        blocks += (uint32_t)((R.n + d.per_block - 1) / d.per_block);
-        out.push_back(d);
-    }
-    return out;
-}
-
-// A plan's whole ladder: the used rungs, the kernels they run in
-// (ladder_split) and the fused kernel's margin (0: it does not run).  What
-// make_plan uploads and run_ladder launches, and what rt_ladder_check and
-// rt_ladder_layout report, all come from here.
-struct LadderPlan {
-    std::vector<DsRung> rungs, rungs_f, rungs_w;
-    int mode = kLadderPerRung;
-    uint32_t margin = 0;
-};
-
-LadderPlan plan_ladder(const PgramPlan& pg)
-{
-    LadderPlan l;
-    l.rungs = used_rungs(pg);
-    l.mode = ladder_split(pg.prm.size, l.rungs, &l.rungs_f, &l.rungs_w);
-    if (l.mode != kLadderPerRung) l.margin = ds_fused_margin(l.rungs_f.data(), l.rungs_f.size());
-    return l;
-}
-
 rt_plan* make_plan(size_t size, double tsamp, const uint64_t* widths, size_t nw, double pmin, double pmax,
                    size_t bmin, size_t bmax)
 {
-    PgramParams prm;
-    prm.size = size;
-    prm.tsamp = tsamp;
-    prm.pmin = pmin;
-    prm.pmax = pmax;
-    prm.bmin = bmin;
-    prm.bmax = bmax;
-    const std::string msg = check_pgram_args(prm);
-    if (!msg.empty()) throw std::invalid_argument(msg);
-    if (nw > (size_t)kMaxWidths) throw std::invalid_argument("at most 32 trial widths are supported");
-    check_widths(widths, nw, bmin);
+    const PgramParams prm = checked_params(size, tsamp, pmin, pmax, bmin, bmax);
+    const uint32_t wmax = checked_plan_widths(widths, nw, bmin);
     if (lds_row_capacity((uint32_t)bmax) < 3) throw std::invalid_argument("bins_max too large for the LDS FFA engine");
+    // everything the host decides (plan.hpp); the rest of this function only uploads it
+    HostPlan hp;
+    plan_periodogram(prm, (uint32_t)nw, wmax, scratch_budget_floats(), cosched_banks(), hp);
+    if (std::getenv("RIPTIDE_AMD_PER_RUNG_LADDER")) {   // every rung in the per-rung kernel (A/B runs, tests)
+        hp.ladder.mode = kLadderPerRung;
+        hp.ladder.margin = 0;
+        hp.ladder.rungs_f.clear();
+        hp.ladder.rungs_w.clear();
+    }
     auto* P = new rt_plan();
     try {
-        build_pgram_plan(prm, P->pg);
+        P->pg = std::move(hp.pg);
+        P->dp.ex = std::move(hp.ex);
+        P->ladder = std::move(hp.ladder);
         P->widths.assign(widths, widths + nw);
         ck(hipMalloc(&P->d_widths, std::max<size_t>(1, nw) * sizeof(uint32_t)), "hipMalloc");
         if (nw)
             ck(hipMemcpy(P->d_widths, P->widths.data(), nw * sizeof(uint32_t), hipMemcpyHostToDevice), "upload widths");
-        std::vector<FfaXform> xf;
-        for (const Step& s : P->pg.steps) {
-            if (!s.rows_eval) continue;   // nothing of this transform reaches the output
-            FfaXform X{};
-            X.p = s.bins;
-            X.m = s.rows;
-            X.rows_eval = s.rows_eval;
-            X.rung = s.rung;
-            X.src_off = P->pg.rungs[s.rung].leaf_off;
-            X.snr_row = s.out_row;
-            X.stdnoise = s.stdnoise;
-            xf.push_back(X);
-        }
-        // scratch budget per ping/pong buffer and trial (scratch_budget_floats)
-        const uint32_t wmax = P->widths.empty() ? 0u : *std::max_element(P->widths.begin(), P->widths.end());
-        build_exec_plan(xf, true, (uint32_t)nw, scratch_budget_floats(), P->dp.ex, wmax, cosched_banks());
         P->dp.upload();
         ck(hipMalloc(&P->d_flag, sizeof(int)), "hipMalloc");
         ck(hipMemset(P->d_flag, 0, sizeof(int)), "hipMemset");
-        // downsample ladder over the rungs that feed at least one transform
-        LadderPlan ladder = plan_ladder(P->pg);
-        if (std::getenv("RIPTIDE_AMD_PER_RUNG_LADDER")) {   // every rung in the per-rung kernel (A/B runs, tests)
-            ladder.mode = kLadderPerRung;
-            ladder.margin = 0;
-            ladder.rungs_f.clear();
-            ladder.rungs_w.clear();
-        }
-        P->rungs = std::move(ladder.rungs);
-        P->rungs_f = std::move(ladder.rungs_f);
-        P->rungs_w = std::move(ladder.rungs_w);
-        P->ds_mode = ladder.mode;
-        P->ds_margin = ladder.margin;
-        P->ds_blocks = 0;
-        for (const DsRung& d : P->rungs) P->ds_blocks += (uint32_t)((d.n + d.per_block - 1) / d.per_block);
-        for (const DsRung& d : P->rungs_w) P->ds_blocks_w += (uint32_t)((d.n + d.per_block - 1) / d.per_block);
+        const LadderPlan& l = P->ladder;
+        for (const DsRung& d : l.rungs) P->ds_blocks += (uint32_t)((d.n + d.per_block - 1) / d.per_block);
+        for (const DsRung& d : l.rungs_w) P->ds_blocks_w += (uint32_t)((d.n + d.per_block - 1) / d.per_block);
         auto upload = [](DsRung*& dst, const std::vector<DsRung>& src) {
             ck(hipMalloc(&dst, std::max<size_t>(1, src.size()) * sizeof(DsRung)), "hipMalloc");
             if (!src.empty())
                 ck(hipMemcpy(dst, src.data(), src.size() * sizeof(DsRung), hipMemcpyHostToDevice), "upload rungs");
         };
-        upload(P->d_rungs, P->rungs);
-        if (P->ds_mode != kLadderPerRung) upload(P->d_rungs_f, P->rungs_f);
-        if (P->ds_mode == kLadderHybrid) upload(P->d_rungs_w, P->rungs_w);
+        upload(P->d_rungs, l.rungs);
+        if (l.mode != kLadderPerRung) upload(P->d_rungs_f, l.rungs_f);
+        if (l.mode == kLadderHybrid) upload(P->d_rungs_w, l.rungs_w);
     } catch (...) {
         delete P;
         throw;
@@ -817,25 +647,25 @@ void run_ladder(const rt_plan* P, const float* d_data, size_t batch, size_t data
         }
         ck(hipEventRecord(r.a, s), "hipEventRecord");
     }
-    if (P->ds_mode != kLadderPerRung)
-        ck(launch_downsample_fused(d_data, P->pg.prm.size, data_stride, P->d_rungs_f, (uint32_t)P->rungs_f.size(),
-                                   P->ds_margin, leaves, P->pg.leaf_floats,
-                                   (uint32_t)batch, s),
+    const LadderPlan& l = P->ladder;
+    if (l.mode != kLadderPerRung)
+        ck(launch_downsample_fused(d_data, P->pg.prm.size, data_stride, P->d_rungs_f, (uint32_t)l.rungs_f.size(),
+                                   l.margin, leaves, P->pg.leaf_floats, (uint32_t)batch, s),
            "downsample_fused");
-    if (P->ds_mode == kLadderHybrid)
-        ck(launch_downsample_ladder(d_data, P->pg.prm.size, data_stride, P->d_rungs_w, (uint32_t)P->rungs_w.size(),
+    if (l.mode == kLadderHybrid)
+        ck(launch_downsample_ladder(d_data, P->pg.prm.size, data_stride, P->d_rungs_w, (uint32_t)l.rungs_w.size(),
                                     P->ds_blocks_w, leaves, P->pg.leaf_floats, (uint32_t)batch, s),
            "downsample_ladder");
-    if (P->ds_mode == kLadderPerRung)
-        ck(launch_downsample_ladder(d_data, P->pg.prm.size, data_stride, P->d_rungs, (uint32_t)P->rungs.size(),
+    if (l.mode == kLadderPerRung)
+        ck(launch_downsample_ladder(d_data, P->pg.prm.size, data_stride, P->d_rungs, (uint32_t)l.rungs.size(),
                                     P->ds_blocks, leaves, P->pg.leaf_floats, (uint32_t)batch, s),
            "downsample_ladder");
     if (prof) {
         ck(hipEventRecord(r.b, s), "hipEventRecord");
         // fused: the series is read once for its rungs; per-rung: once per rung
-        double bytes = P->ds_mode != kLadderPerRung ? 4.0 * P->pg.prm.size : 0.0;
-        for (const DsRung& d : P->rungs) {
-            const bool fused = rung_in_fused(P->ds_mode, d);
+        double bytes = l.mode != kLadderPerRung ? 4.0 * P->pg.prm.size : 0.0;
+        for (const DsRung& d : l.rungs) {
+            const bool fused = rung_in_fused(l.mode, d);
             bytes += 4.0 * (double)d.n + (fused ? 0.0 : (d.identity ? 4.0 * d.n : 4.0 * P->pg.prm.size));
         }
         r.alg = r.moved = bytes * batch;
@@ -1303,8 +1133,6 @@ void flag_harmonics(const HInputs& in, size_t n, const HParams& P, size_t block_
 // ---------------------------------------------------------------------------
 extern "C" {
 
-const char* rt_last_error(void) { return g_err.c_str(); }
-
 const char* rt_version(void) { return "riptide_amd 0.1.0 (gfx950)"; }
 
 int rt_set_device(int device)
@@ -1664,26 +1492,6 @@ int rt_flag_harmonics_stats(uint64_t* tiles, uint64_t* near_pairs, uint64_t* hos
     return RT_OK;
 }
 
-int rt_periodogram_length(size_t size, double tsamp, double pmin, double pmax, size_t bmin, size_t bmax,
-                          size_t* length)
-{
-    return guarded([&] {
-        PgramParams prm;
-        prm.size = size;
-        prm.tsamp = tsamp;
-        prm.pmin = pmin;
-        prm.pmax = pmax;
-        prm.bmin = bmin;
-        prm.bmax = bmax;
-        const std::string msg = check_pgram_args(prm);
-        if (!msg.empty()) throw std::invalid_argument(msg);
-        PgramPlan pg;
-        build_pgram_plan(prm, pg);
-        *length = pg.length;
-        return RT_OK;
-    });
-}
-
 int rt_periodogram(const float* data, size_t size, double tsamp, const uint64_t* widths, size_t nw, double pmin,
                    double pmax, size_t bmin, size_t bmax, double* periods, uint32_t* foldbins, float* snrs)
 {
@@ -1763,184 +1571,6 @@ int rt_deredden_normalise(const float* x, size_t size, size_t ws, size_t minpts,
         run_deredden_normalise(dx, size, 1, size, g, deredden != 0, normalise != 0, dz, size, w, c.stream);
         d2h(out, dz, size * 4, c.stream);
         sync(c.stream);
-        return RT_OK;
-    });
-}
-
-int rt_periodogram_grid(size_t size, double tsamp, double pmin, double pmax, size_t bmin, size_t bmax,
-                        double* periods, uint32_t* foldbins)
-{
-    return guarded([&] {
-        PgramParams prm;
-        prm.size = size;
-        prm.tsamp = tsamp;
-        prm.pmin = pmin;
-        prm.pmax = pmax;
-        prm.bmin = bmin;
-        prm.bmax = bmax;
-        const std::string msg = check_pgram_args(prm);
-        if (!msg.empty()) throw std::invalid_argument(msg);
-        PgramPlan pg;
-        build_pgram_plan(prm, pg);
-        fill_grid(pg, periods, foldbins);
-        return RT_OK;
-    });
-}
-
-int rt_ffa_schedule_check(size_t rows, size_t cols, uint64_t* launches)
-{
-    return guarded([&] {
-        if (!rows || !cols || rows > 0xFFFFFFFFull || cols > 0xFFFFFFFFull || !merge_slots((uint32_t)cols))
-            throw std::invalid_argument("rt_ffa_schedule_check: bad shape");
-        FfaXform X{};
-        X.p = (uint32_t)cols;
-        X.m = (uint32_t)rows;
-        X.rows_eval = (uint32_t)rows;
-        ExecPlan ex;
-        build_exec_plan({X}, false, 0, ~0ull, ex);   // validates
-        if (launches) *launches = ex.launches.size();
-        return RT_OK;
-    });
-}
-
-int rt_ladder_check(size_t size, double tsamp, double pmin, double pmax, size_t bmin, size_t bmax, int* fused,
-                    uint64_t* rungs)
-{
-    return guarded([&] {
-        PgramParams prm;
-        prm.size = size;
-        prm.tsamp = tsamp;
-        prm.pmin = pmin;
-        prm.pmax = pmax;
-        prm.bmin = bmin;
-        prm.bmax = bmax;
-        const std::string msg = check_pgram_args(prm);
-        if (!msg.empty()) throw std::invalid_argument(msg);
-        PgramPlan pg;
-        build_pgram_plan(prm, pg);
-        const LadderPlan l = plan_ladder(pg);
-        if (fused) *fused = l.mode;
-        if (rungs) *rungs = l.rungs.size();
-        return RT_OK;
-    });
-}
-
-int rt_ladder_layout(size_t size, double tsamp, double pmin, double pmax, size_t bmin, size_t bmax,
-                     rt_ladder_rung* rungs, size_t cap, uint64_t* count, uint64_t* leaf_floats, int* mode,
-                     uint32_t* margin)
-{
-    return guarded([&] {
-        PgramParams prm;
-        prm.size = size;
-        prm.tsamp = tsamp;
-        prm.pmin = pmin;
-        prm.pmax = pmax;
-        prm.bmin = bmin;
-        prm.bmax = bmax;
-        const std::string msg = check_pgram_args(prm);
-        if (!msg.empty()) throw std::invalid_argument(msg);
-        if (cap && !rungs) throw std::invalid_argument("rt_ladder_layout: rungs is NULL");
-        PgramPlan pg;
-        build_pgram_plan(prm, pg);
-        const LadderPlan l = plan_ladder(pg);
-        for (size_t i = 0; i < l.rungs.size() && i < cap; ++i) {
-            const DsRung& d = l.rungs[i];
-            rt_ladder_rung o{};
-            o.f = d.f;
-            o.n = d.n;
-            o.leaf_off = d.out_off;
-            o.fused = rung_in_fused(l.mode, d);
-            rungs[i] = o;
-        }
-        if (count) *count = l.rungs.size();
-        if (leaf_floats) *leaf_floats = pg.leaf_floats;
-        if (mode) *mode = l.mode;
-        if (margin) *margin = l.margin;
-        return RT_OK;
-    });
-}
-
-// The exec plan rt_plan_create would build for these parameters (host only):
-// wmax = the widest boxcar (0: unknown, as rt_schedule_check has no widths).
-static void schedule_plan(size_t size, double tsamp, size_t nw, uint32_t wmax, double pmin, double pmax, size_t bmin,
-                          size_t bmax, ExecPlan& ex)
-{
-    PgramParams prm;
-    prm.size = size;
-    prm.tsamp = tsamp;
-    prm.pmin = pmin;
-    prm.pmax = pmax;
-    prm.bmin = bmin;
-    prm.bmax = bmax;
-    const std::string msg = check_pgram_args(prm);
-    if (!msg.empty()) throw std::invalid_argument(msg);
-    PgramPlan pg;
-    build_pgram_plan(prm, pg);
-    std::vector<FfaXform> xf;
-    for (const Step& s : pg.steps) {
-        if (!s.rows_eval) continue;
-        FfaXform X{};
-        X.p = s.bins;
-        X.m = s.rows;
-        X.rows_eval = s.rows_eval;
-        X.snr_row = s.out_row;
-        xf.push_back(X);
-    }
-    // build_exec_plan validates the schedule (validate_exec_plan: tiles
-    // inside nodes, LDS / register budgets, final pass covers every row,
-    // no launch of mixed S/N kinds)
-    build_exec_plan(xf, true, (uint32_t)nw, scratch_budget_floats(), ex, wmax, cosched_banks());
-}
-
-int rt_schedule_check(size_t size, double tsamp, size_t nw, double pmin, double pmax, size_t bmin, size_t bmax,
-                      uint64_t* transforms, uint64_t* items, uint64_t* launches, double* alg_bytes,
-                      double* moved_bytes, uint64_t* cells)
-{
-    return guarded([&] {
-        ExecPlan ex;
-        schedule_plan(size, tsamp, nw, 0, pmin, pmax, bmin, bmax, ex);
-        uint64_t a = 0;
-        double alg = 0, mv = 0;
-        for (const Launch& L : ex.launches) {
-            alg += L.alg_bytes;
-            mv += L.moved_bytes;
-            if (L.pass == 0) a += L.cells;
-        }
-        *transforms = ex.xf.size();
-        *items = ex.items.size();
-        *launches = ex.launches.size();
-        *alg_bytes = alg;
-        *moved_bytes = mv;
-        *cells = a;
-        return RT_OK;
-    });
-}
-
-int rt_schedule_final_kinds(size_t size, double tsamp, const uint64_t* widths, size_t nw, double pmin, double pmax,
-                            size_t bmin, size_t bmax, uint64_t* launches, uint64_t* rows_launches,
-                            uint64_t* seg_launches, uint8_t* bins_kinds, size_t bins_cap)
-{
-    return guarded([&] {
-        if (nw > (size_t)kMaxWidths) throw std::invalid_argument("at most 32 trial widths are supported");
-        check_widths(widths, nw, bmin);
-        uint32_t wmax = 0;
-        for (size_t i = 0; i < nw; ++i) wmax = std::max(wmax, (uint32_t)widths[i]);
-        ExecPlan ex;
-        schedule_plan(size, tsamp, nw, wmax, pmin, pmax, bmin, bmax, ex);
-        uint64_t nr = 0, ns = 0;
-        if (bins_kinds) std::fill(bins_kinds, bins_kinds + bins_cap, (uint8_t)0);
-        for (const Launch& L : ex.launches) {
-            if (L.snr == kSnrNone) continue;
-            ++(L.snr == kSnrSeg ? ns : nr);
-            if (!bins_kinds) continue;
-            for (uint32_t i = L.first; i < L.first + L.count; ++i) {
-                const uint32_t p = ex.xf[ex.items[i].xform].p;
-                if (p < bins_cap) bins_kinds[p] |= (uint8_t)(L.snr == kSnrSeg ? 2 : 1);
-            }
-        }
-        if (launches) *launches = ex.launches.size();
-        if (rows_launches) *rows_launches = nr;
-        if (seg_launches) *seg_launches = ns;
         return RT_OK;
     });
 }
@@ -2184,19 +1814,13 @@ int rt_diag_timeline(uint64_t* out, uint64_t cap, uint64_t* count)
 int rt_plan_stats(const rt_plan* P, uint64_t* transforms, uint64_t* items, uint64_t* launches, double* alg,
                   double* moved, uint64_t* cells)
 {
-    *transforms = P->dp.ex.xf.size();
-    *items = P->dp.ex.items.size();
-    *launches = P->dp.ex.launches.size();
-    double a = 0, m = 0;
-    uint64_t c = 0;
-    for (const Launch& L : P->dp.ex.launches) {
-        a += L.alg_bytes;
-        m += L.moved_bytes;
-        if (L.pass == 0) c += L.cells;
-    }
-    *alg = a;
-    *moved = m;
-    *cells = c;
+    const ExecTotals t = exec_totals(P->dp.ex);
+    *transforms = t.transforms;
+    *items = t.items;
+    *launches = t.launches;
+    *alg = t.alg_bytes;
+    *moved = t.moved_bytes;
+    *cells = t.cells;
     return RT_OK;
 }
 

@@ -1,0 +1,44 @@
+// Shared by the C ABI's translation units (capi.cpp, host_api.cpp): the
+// thread's error text and the entry points' exception barrier.  No HIP header.
+#pragma once
+#include <stdexcept>
+#include <string>
+
+#include "riptide_amd.h"
+
+namespace rt {
+
+inline std::string& last_error()   // rt_last_error's text, per thread
+{
+    thread_local std::string err;
+    return err;
+}
+
+inline int fail(int code, const std::string& msg)
+{
+    last_error() = msg;
+    return code;
+}
+
+struct HipError : std::runtime_error {   // a failed HIP runtime call (capi.cpp ck): RT_EHIP
+    using std::runtime_error::runtime_error;
+};
+
+// Exception barrier for every entry point.
+template <class F>
+int guarded(F&& f)
+{
+    try {
+        return f();
+    } catch (const std::invalid_argument& e) {
+        return fail(RT_EINVAL, e.what());
+    } catch (const HipError& e) {
+        return fail(RT_EHIP, e.what());
+    } catch (const std::exception& e) {
+        return fail(RT_EINTERNAL, e.what());
+    } catch (...) {
+        return fail(RT_EINTERNAL, "unknown error");
+    }
+}
+
+}  // namespace rt

@@ -16,6 +16,7 @@
 // The last pass of a transform fuses the boxcar S/N scan (snr.hpp:37-65) on the
 // rows it produced, so the transform output never returns to HBM.
 #pragma once
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 
@@ -230,6 +231,54 @@ RT_HD inline int lds_row_capacity(uint32_t p, int smax)
 }
 
 RT_HD inline int lds_row_capacity(uint32_t p) { return lds_row_capacity(p, merge_slots(p)); }
+
+// ---- downsampling ladder (ffa_kernels.hip downsample_ladder_kernel /
+// downsample_fused_kernel; planned on the host: plan.hpp plan_ladder)
+constexpr uint32_t kDsSpanFloats = 4096;   // LDS input stage of the ladder kernels (16 KiB)
+constexpr uint32_t kDsFusedMargin = 512;   // fused ladder: staged floats past the span (rungs with ceil(f) + 2 <= margin)
+constexpr uint32_t kDsMaxRungs = 256;      // fused ladder: rungs per plan (per-block rung ranges in LDS)
+
+struct DsRung {
+    double f;
+    uint64_t n;          // output samples of this rung
+    uint64_t out_off;    // float offset in the per-trial leaf buffer
+    uint32_t first_block;
+    uint32_t identity;   // f == 1: plain copy
+    uint32_t per_block;  // outputs per block (input span of a block <= kDsSpanFloats)
+    uint32_t staged;     // 0: f too large to stage a block's span in LDS, read global memory
+};
+
+// Outputs per block of the ladder kernel for factor f (0: cannot stage).
+inline uint32_t ds_per_block(double f)
+{
+    const double o = std::floor((double)(kDsSpanFloats - 4) / (f + 1.0)) - 1.0;
+    if (o < 1.0) return 0;
+    return o > 256.0 ? 256u : (uint32_t)o;
+}
+
+// A block stages its span in LDS when that leaves it >= 32 outputs (f below
+// ~123); a wider rung's block of 256 outputs reads each window from global
+// memory (a staged block of 1-31 outputs left 225-255 of its threads idle
+// behind one span load: cfg5's long range, f up to ~1950).
+inline void ds_configure(DsRung& r)
+{
+    const uint32_t o = r.identity ? 256u : ds_per_block(r.f);
+    r.staged = o >= 32;
+    r.per_block = r.staged ? o : 256u;
+}
+
+// The fused ladder's margin for a plan's rungs: ceil(f) + 2 of the largest
+// non-identity rung, rounded up to 64 samples (0: a rung needs more than
+// kDsFusedMargin -- not fusable).
+inline uint32_t ds_fused_margin(const DsRung* rungs, size_t num_rungs)
+{
+    double need = 2.0;
+    for (size_t i = 0; i < num_rungs; ++i)
+        if (!rungs[i].identity) need = std::fmax(need, std::ceil(rungs[i].f) + 2.0);
+    if (need > (double)kDsFusedMargin) return 0;
+    const uint32_t m = ((uint32_t)need + 63u) & ~63u;
+    return m < kDsFusedMargin ? m : kDsFusedMargin;
+}
 
 // One FFA transform of a plan ((rung, bins) step of periodogram.hpp:153-199).
 struct FfaXform {

@@ -1,0 +1,152 @@
+// The C ABI's host-only entry points: what the planner decides for a set of
+// search parameters, read back without a device.  Each is checked_params ->
+// planner (plan.hpp) -> copy out; rt_plan_create (capi.cpp) uploads the same
+// plan_periodogram result.  No HIP header (`make asan` builds this file as is).
+#include "riptide_amd.h"
+
+#include <algorithm>
+#include <stdexcept>
+
+#include "capi_common.hpp"
+#include "plan.hpp"
+
+using namespace rt;
+
+namespace {
+
+PgramPlan pgram_plan(size_t size, double tsamp, double pmin, double pmax, size_t bmin, size_t bmax)
+{
+    PgramPlan pg;
+    build_pgram_plan(checked_params(size, tsamp, pmin, pmax, bmin, bmax), pg);
+    return pg;
+}
+
+// The host plan rt_plan_create builds for these parameters: wmax = the
+// widest boxcar (0: unknown, as rt_schedule_check has no widths).
+HostPlan host_plan(size_t size, double tsamp, size_t nw, uint32_t wmax, double pmin, double pmax, size_t bmin,
+                   size_t bmax)
+{
+    HostPlan hp;
+    plan_periodogram(checked_params(size, tsamp, pmin, pmax, bmin, bmax), (uint32_t)nw, wmax, scratch_budget_floats(),
+                     cosched_banks(), hp);
+    return hp;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* rt_last_error(void) { return last_error().c_str(); }
+
+int rt_periodogram_length(size_t size, double tsamp, double pmin, double pmax, size_t bmin, size_t bmax,
+                          size_t* length)
+{
+    return guarded([&] {
+        *length = pgram_plan(size, tsamp, pmin, pmax, bmin, bmax).length;
+        return RT_OK;
+    });
+}
+
+int rt_periodogram_grid(size_t size, double tsamp, double pmin, double pmax, size_t bmin, size_t bmax,
+                        double* periods, uint32_t* foldbins)
+{
+    return guarded([&] {
+        fill_grid(pgram_plan(size, tsamp, pmin, pmax, bmin, bmax), periods, foldbins);
+        return RT_OK;
+    });
+}
+
+int rt_ffa_schedule_check(size_t rows, size_t cols, uint64_t* launches)
+{
+    return guarded([&] {
+        if (!rows || !cols || rows > 0xFFFFFFFFull || cols > 0xFFFFFFFFull || !merge_slots((uint32_t)cols))
+            throw std::invalid_argument("rt_ffa_schedule_check: bad shape");
+        FfaXform X{};
+        X.p = (uint32_t)cols;
+        X.m = (uint32_t)rows;
+        X.rows_eval = (uint32_t)rows;
+        ExecPlan ex;
+        build_exec_plan({X}, false, 0, ~0ull, ex);   // validates
+        if (launches) *launches = ex.launches.size();
+        return RT_OK;
+    });
+}
+
+int rt_ladder_check(size_t size, double tsamp, double pmin, double pmax, size_t bmin, size_t bmax, int* fused,
+                    uint64_t* rungs)
+{
+    return guarded([&] {
+        const LadderPlan l = plan_ladder(pgram_plan(size, tsamp, pmin, pmax, bmin, bmax));
+        if (fused) *fused = l.mode;
+        if (rungs) *rungs = l.rungs.size();
+        return RT_OK;
+    });
+}
+
+int rt_ladder_layout(size_t size, double tsamp, double pmin, double pmax, size_t bmin, size_t bmax,
+                     rt_ladder_rung* rungs, size_t cap, uint64_t* count, uint64_t* leaf_floats, int* mode,
+                     uint32_t* margin)
+{
+    return guarded([&] {
+        const PgramPlan pg = pgram_plan(size, tsamp, pmin, pmax, bmin, bmax);
+        if (cap && !rungs) throw std::invalid_argument("rt_ladder_layout: rungs is NULL");
+        const LadderPlan l = plan_ladder(pg);
+        for (size_t i = 0; i < l.rungs.size() && i < cap; ++i) {
+            const DsRung& d = l.rungs[i];
+            rt_ladder_rung o{};
+            o.f = d.f;
+            o.n = d.n;
+            o.leaf_off = d.out_off;
+            o.fused = rung_in_fused(l.mode, d);
+            rungs[i] = o;
+        }
+        if (count) *count = l.rungs.size();
+        if (leaf_floats) *leaf_floats = pg.leaf_floats;
+        if (mode) *mode = l.mode;
+        if (margin) *margin = l.margin;
+        return RT_OK;
+    });
+}
+
+int rt_schedule_check(size_t size, double tsamp, size_t nw, double pmin, double pmax, size_t bmin, size_t bmax,
+                      uint64_t* transforms, uint64_t* items, uint64_t* launches, double* alg_bytes,
+                      double* moved_bytes, uint64_t* cells)
+{
+    return guarded([&] {
+        const ExecTotals t = exec_totals(host_plan(size, tsamp, nw, 0, pmin, pmax, bmin, bmax).ex);
+        *transforms = t.transforms;
+        *items = t.items;
+        *launches = t.launches;
+        *alg_bytes = t.alg_bytes;
+        *moved_bytes = t.moved_bytes;
+        *cells = t.cells;
+        return RT_OK;
+    });
+}
+
+int rt_schedule_final_kinds(size_t size, double tsamp, const uint64_t* widths, size_t nw, double pmin, double pmax,
+                            size_t bmin, size_t bmax, uint64_t* launches, uint64_t* rows_launches,
+                            uint64_t* seg_launches, uint8_t* bins_kinds, size_t bins_cap)
+{
+    return guarded([&] {
+        const uint32_t wmax = checked_plan_widths(widths, nw, bmin);
+        const ExecPlan ex = host_plan(size, tsamp, nw, wmax, pmin, pmax, bmin, bmax).ex;
+        uint64_t nr = 0, ns = 0;
+        if (bins_kinds) std::fill(bins_kinds, bins_kinds + bins_cap, (uint8_t)0);
+        for (const Launch& L : ex.launches) {
+            if (L.snr == kSnrNone) continue;
+            ++(L.snr == kSnrSeg ? ns : nr);
+            if (!bins_kinds) continue;
+            for (uint32_t i = L.first; i < L.first + L.count; ++i) {
+                const uint32_t p = ex.xf[ex.items[i].xform].p;
+                if (p < bins_cap) bins_kinds[p] |= (uint8_t)(L.snr == kSnrSeg ? 2 : 1);
+            }
+        }
+        if (launches) *launches = ex.launches.size();
+        if (rows_launches) *rows_launches = nr;
+        if (seg_launches) *seg_launches = ns;
+        return RT_OK;
+    });
+}
+
+}  // extern "C"

@@ -1053,4 +1053,151 @@ void validate_exec_plan(const ExecPlan& ex, bool snr_epilogue)
         if (covered[t] != ex.xf[t].m) throw std::runtime_error("schedule: final pass does not cover the transform");
 }
 
+ExecTotals exec_totals(const ExecPlan& ex)
+{
+    ExecTotals t;
+    t.transforms = ex.xf.size();
+    t.items = ex.items.size();
+    t.launches = ex.launches.size();
+    for (const Launch& L : ex.launches) {
+        t.alg_bytes += L.alg_bytes;
+        t.moved_bytes += L.moved_bytes;
+        if (L.pass == 0) t.cells += L.cells;
+    }
+    return t;
+}
+
+// ---- downsampling ladder
+bool rung_fusable(const DsRung& d) { return d.identity || std::ceil(d.f) + 2.0 <= (double)kDsFusedMargin; }
+
+bool rung_in_fused(int mode, const DsRung& d)
+{
+    return mode == kLadderFused || (mode == kLadderHybrid && rung_fusable(d));
+}
+
+int ladder_split(size_t size, const std::vector<DsRung>& rungs, std::vector<DsRung>* f, std::vector<DsRung>* w)
+{
+    if ((uint64_t)size >= kDsFusedMaxSize) return kLadderPerRung;
+    std::vector<DsRung> a, b;
+    uint32_t blocks = 0;
+    for (const DsRung& d : rungs) {
+        if (rung_fusable(d)) {
+            a.push_back(d);
+        } else {
+            DsRung e = d;
+            e.first_block = blocks;
+            blocks += (uint32_t)((e.n + e.per_block - 1) / e.per_block);
+            b.push_back(e);
+        }
+    }
+    if (a.empty() || a.size() > kDsMaxRungs || ds_fused_margin(a.data(), a.size()) == 0) return kLadderPerRung;
+    if (f) *f = a;
+    if (w) *w = b;
+    return b.empty() ? kLadderFused : kLadderHybrid;
+}
+
+std::vector<DsRung> used_rungs(const PgramPlan& pg)
+{
+    std::vector<bool> used(pg.rungs.size(), false);
+    for (const Step& s : pg.steps)
+        if (s.rows_eval) used[s.rung] = true;
+    std::vector<DsRung> out;
+    uint32_t blocks = 0;
+    for (size_t r = 0; r < pg.rungs.size(); ++r) {
+        if (!used[r]) continue;
+        const Rung& R = pg.rungs[r];
+        DsRung d{};
+        d.f = R.f;
+        d.n = R.n;
+        d.out_off = R.leaf_off;
+        d.first_block = blocks;
+        d.identity = R.f == 1.0;
+        ds_configure(d);
+        blocks += (uint32_t)((R.n + d.per_block - 1) / d.per_block);
+        out.push_back(d);
+    }
+    return out;
+}
+
+LadderPlan plan_ladder(const PgramPlan& pg)
+{
+    LadderPlan l;
+    l.rungs = used_rungs(pg);
+    l.mode = ladder_split(pg.prm.size, l.rungs, &l.rungs_f, &l.rungs_w);
+    if (l.mode != kLadderPerRung) l.margin = ds_fused_margin(l.rungs_f.data(), l.rungs_f.size());
+    return l;
+}
+
+// ---- the whole host plan
+std::vector<FfaXform> pgram_xforms(const PgramPlan& pg)
+{
+    std::vector<FfaXform> xf;
+    for (const Step& s : pg.steps) {
+        if (!s.rows_eval) continue;   // nothing of this transform reaches the output
+        FfaXform X{};
+        X.p = s.bins;
+        X.m = s.rows;
+        X.rows_eval = s.rows_eval;
+        X.rung = s.rung;
+        X.src_off = pg.rungs[s.rung].leaf_off;
+        X.snr_row = s.out_row;
+        X.stdnoise = s.stdnoise;
+        xf.push_back(X);
+    }
+    return xf;
+}
+
+PgramParams checked_params(size_t size, double tsamp, double pmin, double pmax, size_t bmin, size_t bmax)
+{
+    PgramParams prm;
+    prm.size = size;
+    prm.tsamp = tsamp;
+    prm.pmin = pmin;
+    prm.pmax = pmax;
+    prm.bmin = bmin;
+    prm.bmax = bmax;
+    const std::string msg = check_pgram_args(prm);
+    if (!msg.empty()) throw std::invalid_argument(msg);
+    return prm;
+}
+
+void check_widths(const uint64_t* w, size_t nw, size_t bins)
+{
+    for (size_t i = 0; i < nw; ++i)
+        if (!(w[i] > 0 && w[i] < bins)) throw std::invalid_argument("trial widths must be all > 0 and < columns");
+}
+
+uint32_t checked_plan_widths(const uint64_t* w, size_t nw, size_t bmin)
+{
+    if (nw > (size_t)kMaxWidths) throw std::invalid_argument("at most 32 trial widths are supported");
+    check_widths(w, nw, bmin);
+    uint32_t wmax = 0;
+    for (size_t i = 0; i < nw; ++i) wmax = std::max(wmax, (uint32_t)w[i]);
+    return wmax;
+}
+
+uint64_t scratch_budget_floats()
+{
+    if (const char* e = std::getenv("RIPTIDE_AMD_SCRATCH_MFLOATS")) {
+        const double v = std::atof(e);
+        if (v > 0) return (uint64_t)(v * 1e6);
+    }
+    return 96ull << 20;   // 384 MiB per ping/pong buffer and trial: ~94 launches per cfg2 plan (sweep_schedule.py)
+}
+
+uint32_t cosched_banks()
+{
+    const char* e = std::getenv("RIPTIDE_AMD_COSCHED");
+    return e && e[0] == '1' ? 2u : 1u;
+}
+
+void plan_periodogram(const PgramParams& prm, uint32_t num_widths, uint32_t max_width, uint64_t scratch_budget,
+                      uint32_t banks, HostPlan& out)
+{
+    build_pgram_plan(prm, out.pg);
+    // (validates the schedule: validate_exec_plan)
+    build_exec_plan(pgram_xforms(out.pg), true, num_widths, scratch_budget, out.ex, max_width, banks);
+    out.ladder = plan_ladder(out.pg);   // over the rungs that feed at least one transform
+}
+
 }  // namespace rt

@@ -130,4 +130,81 @@ constexpr uint64_t kMaxBlockBytes = 1ull << 31;
 struct ConeNeed { int max_rows = 0; int max_floats = 0; int ranges = 0; int rows_bottom = 0; int runs_bottom = 0; int entries = 0; bool degenerate = false; };
 ConeNeed cone_need(uint32_t node_size, uint32_t s0, uint32_t s1, int levels, uint32_t p);
 
+// What rt_schedule_check and rt_plan_stats report of a schedule: the launches'
+// summed bytes, the cells of the pass-0 launches (every transform's, once).
+struct ExecTotals {
+    uint64_t transforms = 0, items = 0, launches = 0, cells = 0;
+    double alg_bytes = 0, moved_bytes = 0;
+};
+ExecTotals exec_totals(const ExecPlan& ex);
+
+// ---- downsampling ladder
+// The fused ladder (downsample_fused_kernel) indexes samples and outputs in
+// 32 bits and stages up to kDsFusedMargin floats past each span: series of 2^29
+// samples or more, rungs whose window (ceil(f) + 2) exceeds the margin, and
+// more rungs than its per-block table take the per-rung kernel (64-bit
+// indices) instead.
+constexpr uint64_t kDsFusedMaxSize = 1ull << 29;
+// kLadderPerRung / kLadderFused (every rung fits the fused ladder's margin) /
+// kLadderHybrid (the rungs that fit take the fused kernel, the wider ones the
+// per-rung kernel: LadderPlan::rungs_w, first_block within the subset)
+constexpr int kLadderPerRung = 0, kLadderFused = 1, kLadderHybrid = 2;
+
+bool rung_fusable(const DsRung& d);
+// whether the fused kernel (not the per-rung one) writes rung d of a plan in ladder mode `mode`
+bool rung_in_fused(int mode, const DsRung& d);
+
+// The ladder's kernels for a plan's rungs: every rung in the fused kernel;
+// or, when some rungs' windows exceed its margin (cfg5's long range: factors
+// up to ~1950), the others in the fused kernel and those in the per-rung
+// kernel (hybrid, `f` / `w` the two subsets, w's first_block renumbered);
+// or all per-rung (series of 2^29 samples or more: 32-bit indices; more
+// fusable rungs than the fused kernel's per-block table).
+int ladder_split(size_t size, const std::vector<DsRung>& rungs, std::vector<DsRung>* f, std::vector<DsRung>* w);
+
+// The rungs of a periodogram that feed at least one transform, in the
+// ladder kernels' form.
+std::vector<DsRung> used_rungs(const PgramPlan& pg);
+
+// A plan's whole ladder: the used rungs, the kernels they run in
+// (ladder_split) and the fused kernel's margin (0: it does not run).  What
+// rt_plan_create uploads and launches, and what rt_ladder_check and
+// rt_ladder_layout report, all come from here.
+struct LadderPlan {
+    std::vector<DsRung> rungs, rungs_f, rungs_w;
+    int mode = kLadderPerRung;
+    uint32_t margin = 0;
+};
+LadderPlan plan_ladder(const PgramPlan& pg);
+
+// ---- the whole host plan
+// The transforms of a periodogram that reach its output (rows_eval > 0), every
+// field but buf_off (build_exec_plan's) filled in.
+std::vector<FfaXform> pgram_xforms(const PgramPlan& pg);
+
+// Checked parameters (check_pgram_args): throws std::invalid_argument with the reference's text.
+PgramParams checked_params(size_t size, double tsamp, double pmin, double pmax, size_t bmin, size_t bmax);
+
+// Boxcar widths over rows of `bins` bins (snr.hpp); a plan's (at most kMaxWidths): returns the widest.
+void check_widths(const uint64_t* w, size_t nw, size_t bins);
+uint32_t checked_plan_widths(const uint64_t* w, size_t nw, size_t bmin);
+
+// Environment knobs of plan_periodogram's callers: the per-trial scratch budget
+// of one transform group (RIPTIDE_AMD_SCRATCH_MFLOATS, millions of floats per
+// ping/pong buffer) and the scratch banks (RIPTIDE_AMD_COSCHED=1: 2, the
+// groups co-scheduled on two streams, capi.cpp run_cone_launches).
+uint64_t scratch_budget_floats();
+uint32_t cosched_banks();
+
+// Everything the host decides for a periodogram: ladder and steps, the cone
+// schedule with its unit blobs (validated), the ladder's kernels.  Both
+// rt_plan_create and the host-only checks (host_api.cpp) get theirs here.
+struct HostPlan {
+    PgramPlan pg;
+    ExecPlan ex;
+    LadderPlan ladder;
+};
+void plan_periodogram(const PgramParams& prm, uint32_t num_widths, uint32_t max_width, uint64_t scratch_budget,
+                      uint32_t banks, HostPlan& out);
+
 }  // namespace rt

@@ -3,7 +3,8 @@
 // planner and the C ABI's host-only entry points -- rt_periodogram_grid,
 // rt_schedule_check, rt_ffa_schedule_check, rt_ladder_check, rt_ladder_layout -- which build
 // every unit blob, DMA segment table and row-slot table the cone kernel
-// trusts.  No device call.  Usage:
+// trusts.  No device call, and none linked: the checker is this file,
+// plan.cpp and host_api.cpp.  Usage:
 //   sched_check pgram N TSAMP PMIN PMAX BMIN BMAX NWIDTHS
 //   sched_check ffa ROWS COLS
 //   sched_check kinds N TSAMP PMIN PMAX BMIN BMAX WIDTH...

@@ -25,18 +25,8 @@ int main(int argc, char** argv)
     const int wmax = argc > 7 ? std::atoi(argv[7]) : 42;
     PgramPlan pg;
     build_pgram_plan(a, pg);
-    std::vector<FfaXform> xf;
-    for (const Step& s : pg.steps) {
-        if (!s.rows_eval) continue;
-        FfaXform X{};
-        X.p = s.bins;
-        X.m = s.rows;
-        X.rows_eval = s.rows_eval;
-        X.snr_row = s.out_row;
-        xf.push_back(X);
-    }
     ExecPlan ex;
-    build_exec_plan(xf, true, 10, 1ull << 40, ex, std::getenv("NOCAP") ? 0u : (uint32_t)wmax);
+    build_exec_plan(pgram_xforms(pg), true, 10, 1ull << 40, ex, std::getenv("NOCAP") ? 0u : (uint32_t)wmax);
     double rows = 0, rows_fit = 0, rows_whole = 0, rows_noblob = 0, units = 0;
     std::map<int, double> hist;
     for (const ConeItem& it : ex.items) {

@@ -20,18 +20,8 @@ int main(int argc, char** argv)
     a.bmax = argc > 6 ? std::atoi(argv[6]) : 260;
     PgramPlan pg;
     build_pgram_plan(a, pg);
-    std::vector<FfaXform> xf;
-    for (const Step& s : pg.steps) {
-        if (!s.rows_eval) continue;
-        FfaXform X{};
-        X.p = s.bins;
-        X.m = s.rows;
-        X.rows_eval = s.rows_eval;
-        X.snr_row = s.out_row;
-        xf.push_back(X);
-    }
     ExecPlan ex;
-    build_exec_plan(xf, true, 6, 1ull << 40, ex);
+    build_exec_plan(pgram_xforms(pg), true, 6, 1ull << 40, ex);
     double rows_tot = 0, items_tot = 0, noblob = 0, noblob_rows = 0, blob_units = 0;
     double issued = 0, useful = 0, ideal = 0, steps = 0, units = 0;
     std::map<int, double> by_rw_issued, by_rw_useful;

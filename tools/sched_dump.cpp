@@ -28,24 +28,10 @@ int main(int argc, char** argv)
     prm.bmax = std::strtoull(argv[6], nullptr, 10);
     const uint32_t nw = (uint32_t)std::atoi(argv[7]), wmax = (uint32_t)std::atoi(argv[8]);
     const uint64_t budget = (uint64_t)(std::atof(argv[9]) * 1e6);
-    PgramPlan pg;
-    build_pgram_plan(prm, pg);
-    std::vector<FfaXform> xf;
-    for (const Step& s : pg.steps) {
-        if (!s.rows_eval) continue;
-        FfaXform X{};
-        X.p = s.bins;
-        X.m = s.rows;
-        X.rows_eval = s.rows_eval;
-        X.rung = s.rung;
-        X.src_off = pg.rungs[s.rung].leaf_off;
-        X.snr_row = s.out_row;
-        X.stdnoise = s.stdnoise;
-        xf.push_back(X);
-    }
-    ExecPlan ex;
-    build_exec_plan(xf, true, nw, budget, ex, wmax, 1);
-    std::printf("transforms %zu items %zu launches %zu\n", xf.size(), ex.items.size(), ex.launches.size());
+    HostPlan hp;
+    plan_periodogram(prm, nw, wmax, budget, 1, hp);
+    const ExecPlan& ex = hp.ex;
+    std::printf("transforms %zu items %zu launches %zu\n", ex.xf.size(), ex.items.size(), ex.launches.size());
     double tot_alg = 0, tot_moved = 0;
     for (size_t i = 0; i < ex.launches.size(); ++i) {
         const Launch& L = ex.launches[i];
@@ -82,5 +68,8 @@ int main(int argc, char** argv)
         }
     }
     std::printf("total alg %.3f GB moved %.3f GB per trial\n", tot_alg / 1e9, tot_moved / 1e9);
+    const LadderPlan& l = hp.ladder;
+    std::printf("ladder mode %d (0 per-rung, 1 fused, 2 both) margin %u rungs %zu fused %zu per-rung %zu\n", l.mode,
+                l.margin, l.rungs.size(), l.rungs_f.size(), l.mode == kLadderPerRung ? l.rungs.size() : l.rungs_w.size());
     return 0;
 }

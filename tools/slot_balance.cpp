@@ -30,23 +30,9 @@ int main(int argc, char** argv)
     prm.bmax = std::strtoull(argv[6], nullptr, 10);
     const uint32_t nw = (uint32_t)std::atoi(argv[7]), wmax = (uint32_t)std::atoi(argv[8]);
     const uint64_t budget = (uint64_t)(std::atof(argv[9]) * 1e6);
-    PgramPlan pg;
-    build_pgram_plan(prm, pg);
-    std::vector<FfaXform> xf;
-    for (const Step& s : pg.steps) {
-        if (!s.rows_eval) continue;
-        FfaXform X{};
-        X.p = s.bins;
-        X.m = s.rows;
-        X.rows_eval = s.rows_eval;
-        X.rung = s.rung;
-        X.src_off = pg.rungs[s.rung].leaf_off;
-        X.snr_row = s.out_row;
-        X.stdnoise = s.stdnoise;
-        xf.push_back(X);
-    }
-    ExecPlan ex;
-    build_exec_plan(xf, true, nw, budget, ex, wmax, 1);
+    HostPlan hp;
+    plan_periodogram(prm, nw, wmax, budget, 1, hp);
+    const ExecPlan& ex = hp.ex;
     const double cost[4] = {4.0, 8.0, 5.0, 6.0};   // kSlotOne, kSlotTwo, kSlotPair, kSlotHalf
     double crit = 0, mean = 0, crit_n = 0, mean_n = 0;
     uint64_t steps = 0, kinds[4] = {};
