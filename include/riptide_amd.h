@@ -244,6 +244,43 @@ int rt_segment_order_stats_device(const float* d_snrs, size_t batch, size_t snr_
 int rt_threshold_select_device(const float* d_snrs, size_t batch, size_t snr_stride, size_t length,
                                size_t num_widths, const double* d_logf, const double* d_coeffs, size_t ncoef,
                                double smin, uint32_t* d_counts, uint32_t* d_idx, size_t cap, void* stream);
+/* Clustered peaks (find_peaks_single, peak_detection.py:130-141): the
+ * selection above, then, along every (trial b, width iw) column,
+ *   clusters  the selected rows in ascending order; a new cluster starts at a
+ *             selected row i whose previous selected row j has
+ *             fabs(d_freqs[i] - d_freqs[j]) > radius (fp64, one rounded
+ *             subtraction, strict: cluster1d's np.abs(np.diff(x)) > r);
+ *   peak      np.argmax over the cluster in cluster1d's order, ascending
+ *             frequency: of the rows attaining the cluster's maximum S/N, the
+ *             first (lowest) row on a grid whose frequencies rise with the
+ *             row, the last on one where they fall (d_freqs[L - 1] <
+ *             d_freqs[0], a periodogram's own grid).  The grid must be
+ *             monotone.
+ * d_freqs: L doubles, the trial frequencies 1 / periods; radius: clrad / tobs.
+ * A NaN S/N is never selected, +inf is selected like any value.
+ * The k-th cluster's peak, clusters in ascending row order, is left in
+ * d_rows[(b * W + iw) * cap + k] and d_snr[(b * W + iw) * cap + k], the
+ * number of clusters in d_counts[b * W + iw]; a count above cap means the
+ * first cap records are valid and the column was truncated (nothing is
+ * written past them).  chunk_rows: rows one workgroup walks (0 = default,
+ * rounded up to a multiple of 64, at most 2^20); the result does not depend
+ * on it.  d_workspace: rt_find_peaks_workspace_bytes bytes, 8-byte aligned.
+ * Stream-ordered, no host synchronisation.  RT_EINVAL (nothing is launched)
+ * for: cap == 0, ncoef == 0 or > 64, length >= 2^32, batch > 65535,
+ * batch * num_widths >= 2^31, a workspace below
+ * rt_find_peaks_workspace_bytes.  batch, length or num_widths of 0 is RT_OK
+ * (length 0: the counts are zeroed). */
+int rt_find_peaks_workspace_bytes(size_t batch, size_t length, size_t num_widths, size_t chunk_rows, size_t* bytes);
+int rt_find_peaks_device(const float* d_snrs, size_t batch, size_t snr_stride, size_t length, size_t num_widths,
+                         const double* d_logf, const double* d_freqs, const double* d_coeffs, size_t ncoef,
+                         double smin, double radius, uint32_t* d_counts, uint32_t* d_rows, float* d_snr,
+                         size_t cap, size_t chunk_rows, void* d_workspace, size_t workspace_bytes, void* stream);
+/* Host only, no device: the same walk over one trial's host arrays (snrs: L x
+ * W row-major; coeffs: W x ncoef; counts: W; rows, snr: W x cap) -- the
+ * specification the kernels are pinned to. */
+int rt_find_peaks_host(const float* snrs, size_t length, size_t num_widths, const double* logf, const double* freqs,
+                       const double* coeffs, size_t ncoef, double smin, double radius,
+                       uint32_t* counts, uint32_t* rows, float* snr, size_t cap);
 
 /* ------------------------- candidate folding ------------------------------ */
 /* riptide/folding.py:19-81 (what TimeSeries.fold returns) for a batch of

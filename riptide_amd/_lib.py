@@ -76,6 +76,12 @@ _SIGNATURES = {
     "rt_segment_order_stats_device": (_c_i, [_vp, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz, _vp, _c_sz, _vp, _vp]),
     "rt_threshold_select_device": (_c_i, [_vp, _c_sz, _c_sz, _c_sz, _c_sz, _vp, _vp, _c_sz, _c_d, _vp, _vp, _c_sz,
                                           _vp]),
+    "rt_find_peaks_workspace_bytes": (_c_i, [_c_sz, _c_sz, _c_sz, _c_sz, _psz]),
+    # snrs, batch, stride, L, W, logf, freqs, coeffs, ncoef, smin, radius, counts, rows, snr, cap, chunk_rows,
+    # workspace, workspace bytes, stream
+    "rt_find_peaks_device": (_c_i, [_vp, _c_sz, _c_sz, _c_sz, _c_sz, _vp, _vp, _vp, _c_sz, _c_d, _c_d, _vp, _vp, _vp,
+                                    _c_sz, _c_sz, _vp, _c_sz, _vp]),
+    "rt_find_peaks_host": (_c_i, [_vp, _c_sz, _c_sz, _vp, _vp, _vp, _c_sz, _c_d, _c_d, _vp, _vp, _vp, _c_sz]),
     "rt_ladder_check": (_c_i, [_c_sz, _c_d, _c_d, _c_d, _c_sz, _c_sz, ctypes.POINTER(_c_i), _pu64]),
     # the six search parameters, rungs (rt_ladder_rung[cap]), cap, count, leaf_floats, mode, margin
     "rt_ladder_layout": (_c_i, [_c_sz, _c_d, _c_d, _c_d, _c_sz, _c_sz, _vp, _c_sz, _pu64, _pu64,

@@ -8,6 +8,7 @@
 #include <stdexcept>
 
 #include "capi_common.hpp"
+#include "peaks_host.hpp"
 #include "plan.hpp"
 
 using namespace rt;
@@ -145,6 +146,29 @@ int rt_schedule_final_kinds(size_t size, double tsamp, const uint64_t* widths, s
         if (launches) *launches = ex.launches.size();
         if (rows_launches) *rows_launches = nr;
         if (seg_launches) *seg_launches = ns;
+        return RT_OK;
+    });
+}
+
+int rt_find_peaks_workspace_bytes(size_t batch, size_t length, size_t num_widths, size_t chunk_rows, size_t* bytes)
+{
+    return guarded([&] {
+        *bytes = checked_peak_workspace(batch, length, num_widths, chunk_rows);
+        return RT_OK;
+    });
+}
+
+int rt_find_peaks_host(const float* snrs, size_t length, size_t num_widths, const double* logf, const double* freqs,
+                       const double* coeffs, size_t ncoef, double smin, double radius, uint32_t* counts,
+                       uint32_t* rows, float* snr, size_t cap)
+{
+    return guarded([&] {
+        if (!cap) throw std::invalid_argument("rt_find_peaks_host: cap is 0");
+        if (!ncoef || ncoef > 64) throw std::invalid_argument("rt_find_peaks_host: 1 to 64 polynomial coefficients");
+        if (length >= (1ull << 32)) throw std::invalid_argument("rt_find_peaks_host: length must be below 2^32");
+        for (size_t iw = 0; iw < num_widths; ++iw)
+            counts[iw] = find_peaks_column(snrs + iw, num_widths, length, logf, freqs, coeffs + iw * ncoef,
+                                           (uint32_t)ncoef, smin, radius, rows + iw * cap, snr + iw * cap, cap);
         return RT_OK;
     });
 }

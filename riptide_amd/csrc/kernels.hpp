@@ -32,6 +32,12 @@ hipError_t launch_segment_order_stats(const float* snrs, uint64_t snr_stride, ui
 hipError_t launch_threshold_select(const float* snrs, uint64_t snr_stride, uint32_t batch, uint32_t L, uint32_t W,
                                    const double* logf, const double* coeffs, uint32_t ncoef, double smin,
                                    uint32_t* counts, uint32_t* idx, uint32_t cap, hipStream_t s);
+// clustered peaks of every (trial, width): chunk = peak_chunk_rows(), workspace
+// = peak_workspace_bytes() bytes (peaks_host.hpp), 8-byte aligned
+hipError_t launch_find_peaks(const float* snrs, uint64_t snr_stride, uint32_t batch, uint32_t L, uint32_t W,
+                             const double* logf, const double* freqs, const double* coeffs, uint32_t ncoef,
+                             double smin, double r, uint32_t* counts, uint32_t* rows, float* out, uint32_t cap,
+                             uint32_t chunk, void* workspace, hipStream_t s);
 
 hipError_t launch_convert_samples(const void* raw, uint64_t n, int is_signed, float* out, hipStream_t s);
 

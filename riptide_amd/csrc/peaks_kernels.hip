@@ -10,10 +10,15 @@
 //   threshold_select_kernel: the dynamic threshold poly(log f) (np.polyval's
 //     Horner loop, fp64, no contraction) and the selection mask
 //     (s > thr) & (s > smin) (peak_detection.py:131-133), compacted into
-//     index lists per (trial, width).  The host sorts each list (np.where
-//     order) and clusters it (cluster1d), which touches only selected points.
+//     index lists per (trial, width), in no order: the host sorts each list
+//     (np.where order), clusters it (cluster1d) and gathers the S/N.
+//   find_peaks_chunk_kernel / find_peaks_join_kernel: the same selection
+//     followed by the clustering and the argmax per cluster on the device
+//     (peak_detection.py:130-141, peaks_host.hpp): an ordered walk along
+//     every column, chunk by chunk, then a join of the chunks' clusters.
+//     Only the (row, S/N) of each cluster's peak is left for the host.
 //
-// Both kernels read the periodogram in the engine's [trial][L][W] layout.
+// All of them read the periodogram in the engine's [trial][L][W] layout.
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -21,6 +26,7 @@
 #include <cstdint>
 
 #include "kernels.hpp"
+#include "peaks_host.hpp"
 
 namespace rt {
 
@@ -226,9 +232,7 @@ __global__ __launch_bounds__(kPeakBlock) void threshold_select_kernel(
     if (i >= L) return;
     const double s = (double)snrs[(uint64_t)trial * snr_stride + (uint64_t)i * W + iw];
     const double* c = coeffs + ((uint64_t)trial * W + iw) * ncoef;
-    const double x = logf[i];
-    double y = 0.0;                                  // np.polyval: y = y * x + pv
-    for (uint32_t k = 0; k < ncoef; ++k) y = __dadd_rn(__dmul_rn(y, x), c[k]);
+    const double y = peak_threshold(c, ncoef, logf[i]);
     if (s > y && s > smin) {
         const uint32_t list = trial * W + iw;
         const uint32_t pos = atomicAdd(&counts[list], 1u);
@@ -281,6 +285,236 @@ hipError_t launch_threshold_select(const float* snrs, uint64_t snr_stride, uint3
     if (!batch || !W || !L) return hipSuccess;
     hipLaunchKernelGGL(threshold_select_kernel, dim3((L + kPeakBlock - 1) / kPeakBlock, W, batch), dim3(kPeakBlock), 0,
                        s, snrs, snr_stride, L, W, logf, coeffs, ncoef, smin, counts, idx, cap);
+    return hipGetLastError();
+}
+
+// ---- clustered peaks (peaks_host.hpp find_peaks_column on the device)
+//
+// Pass 1, find_peaks_chunk_kernel: one workgroup per (row chunk, group of up
+// to kPeakWidthGroup widths, trial).  The chunk is staged kFindSub rows at a
+// time: the rows' kPeakWidthGroup-float segments read coalesced into LDS (odd
+// row stride: a wave reading one width of 64 rows hits 64 banks), log f and f
+// beside them.  Wave v then walks widths v, v + 4, ... of the group, 64 rows
+// per step: the selection mask is a ballot, a selected lane's previous
+// selected row is the highest mask bit below it (or the row carried from the
+// step before), the breaks are a second ballot, and the (S/N, row) of every
+// run between breaks is a segmented inclusive scan whose operator keeps the
+// earlier lane unless the later is strictly greater (greater or equal on a
+// grid of falling frequencies: peak_better) -- associative, so the scan's
+// tree leaves the same one of several equal maxima as the serial walk does.  A width's
+// state between steps (clusters so far, the open cluster's best, the last
+// selected frequency) is wave-uniform and kept in lane q of a register for
+// the wave's q-th width.  Clusters are chunk-local: record k of the chunk is
+// its k-th cluster's peak, the head holds their number and the chunk's first
+// and last selected frequencies.
+//
+// Pass 2, find_peaks_join_kernel: one wave per (trial, width) walks the
+// chunks in order, 64 heads per load.  A chunk's first cluster joins the open
+// one when !peak_breaks(its first frequency, the open cluster's last) -- an
+// empty chunk is skipped, so it is transparent -- and a join compares the
+// two bests with the same peak_better; a chunk's inner clusters are final and copied 64 at a
+// time, its last stays open.
+constexpr int kFindBlock = 256;
+constexpr int kFindWaves = kFindBlock / 64;
+constexpr int kFindSub = 256;                         // rows staged per step
+constexpr int kFindStride = (int)kPeakWidthGroup + 1;
+constexpr int kFindSlots = (int)kPeakWidthGroup / kFindWaves;   // widths per wave
+static_assert(kFindSlots <= 64, "a width's state lives in one lane");
+
+__global__ __launch_bounds__(kFindBlock) void find_peaks_chunk_kernel(
+    const float* __restrict__ snrs, uint64_t snr_stride, uint32_t L, uint32_t W, const double* __restrict__ logf,
+    const double* __restrict__ freqs, const double* __restrict__ coeffs, uint32_t ncoef, double smin, double r,
+    uint32_t chunk, uint32_t nch, PeakChunkHead* __restrict__ heads, PeakRecord* __restrict__ recs)
+{
+    __shared__ float tile[kFindSub * kFindStride];
+    __shared__ double sx[kFindSub], sf[kFindSub];
+    const uint32_t c = blockIdx.x, w0 = blockIdx.y * kPeakWidthGroup, trial = blockIdx.z;
+    const uint32_t wn = min(kPeakWidthGroup, W - w0);
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint64_t row0 = (uint64_t)c * chunk;
+    const uint32_t row_end = (uint32_t)min((uint64_t)L, row0 + chunk);
+    const float* s = snrs + (uint64_t)trial * snr_stride + w0;
+    const uint64_t below_me = (1ull << lane) - 1;
+    const bool last_wins = peak_last_wins(freqs, L);
+    // lane q: the state of width w0 + wave + kFindWaves * q
+    uint32_t st_n = 0, st_best = 0;
+    float st_snr = 0.f;
+    double st_first = 0.0, st_prev = 0.0;
+    for (uint64_t sub64 = row0; sub64 < row_end; sub64 += kFindSub) {
+        const uint32_t sub = (uint32_t)sub64;
+        const uint32_t nrows = min((uint32_t)kFindSub, row_end - sub);
+        __syncthreads();
+        for (uint32_t e = tid; e < nrows * wn; e += kFindBlock) {
+            const uint32_t rr = e / wn, cc = e - rr * wn;
+            tile[rr * kFindStride + cc] = s[(uint64_t)(sub + rr) * W + cc];
+        }
+        if (tid < nrows) {
+            sx[tid] = logf[sub + tid];
+            sf[tid] = freqs[sub + tid];
+        }
+        __syncthreads();
+        for (uint32_t q = 0; wave + kFindWaves * q < wn; ++q) {
+            const uint32_t cc = wave + kFindWaves * q;
+            const double* cf = coeffs + ((uint64_t)trial * W + w0 + cc) * ncoef;
+            uint32_t n = __shfl(st_n, q), best = __shfl(st_best, q);
+            float best_snr = __shfl(st_snr, q);
+            double ffirst = __shfl(st_first, q), fprev = __shfl(st_prev, q);
+            PeakRecord* rec = recs + (((uint64_t)trial * W + w0 + cc) * nch + c) * chunk;
+            for (uint32_t g = 0; g < nrows; g += 64) {
+                const uint32_t rr = g + lane;
+                const bool valid = rr < nrows;
+                const float v = valid ? tile[rr * kFindStride + cc] : 0.f;
+                const double f = valid ? sf[rr] : 0.0;
+                const bool sel = valid && peak_selected(v, peak_threshold(cf, ncoef, sx[valid ? rr : 0]), smin);
+                const uint64_t mask = __ballot(sel);
+                if (!mask) continue;
+                // the previous selected row: in this step, or carried
+                const uint64_t below = mask & below_me;
+                double fp = __shfl(f, below ? 63 - __builtin_clzll(below) : (int)lane);
+                if (!below) fp = fprev;
+                const bool brk = sel && ((!below && !n) || peak_breaks(f, fp, r));
+                const uint64_t bmask = __ballot(brk);
+                // segmented scan: the first maximum of every run so far
+                float sv = sel ? v : -INFINITY;
+                uint32_t srow = sub + rr;
+                int flag = brk;
+                for (int d = 1; d < 64; d <<= 1) {
+                    const float pv = __shfl_up(sv, d);
+                    const uint32_t pr = __shfl_up(srow, d);
+                    const int pf = __shfl_up(flag, d);
+                    if ((int)lane >= d && !flag) {
+                        if (!peak_better(sv, pv, last_wins)) {
+                            sv = pv;
+                            srow = pr;
+                        }
+                        flag = pf;
+                    }
+                }
+                if (!n) ffirst = __shfl(f, __builtin_ctzll(mask));
+                // rows before the first break continue the open cluster
+                const int fb = bmask ? __builtin_ctzll(bmask) : 64;
+                if (fb > 0) {
+                    const float hv = __shfl(sv, fb - 1);
+                    const uint32_t hr = __shfl(srow, fb - 1);
+                    if (n && peak_better(hv, best_snr, last_wins)) {
+                        best = hr;
+                        best_snr = hv;
+                    }
+                }
+                if (bmask) {
+                    if (n && lane == 0) rec[n - 1] = PeakRecord{best, best_snr};
+                    // a break with a later break in this step: a whole cluster
+                    const uint64_t above = bmask & ~((2ull << lane) - 1);
+                    const int endl = above ? __builtin_ctzll(above) - 1 : 63;
+                    const float ev = __shfl(sv, endl);
+                    const uint32_t er = __shfl(srow, endl);
+                    if (brk && above) rec[n + __builtin_popcountll(bmask & below_me)] = PeakRecord{er, ev};
+                    // the last break opens the cluster carried on
+                    best_snr = __shfl(sv, 63);
+                    best = __shfl(srow, 63);
+                    n += __builtin_popcountll(bmask);
+                }
+                fprev = __shfl(f, 63 - __builtin_clzll(mask));
+            }
+            if (lane == q) {
+                st_n = n;
+                st_best = best;
+                st_snr = best_snr;
+                st_first = ffirst;
+                st_prev = fprev;
+            }
+        }
+    }
+    if (lane < (uint32_t)kFindSlots && wave + kFindWaves * lane < wn) {
+        const uint64_t at = ((uint64_t)trial * W + w0 + wave + kFindWaves * lane) * nch + c;
+        if (st_n) recs[at * chunk + st_n - 1] = PeakRecord{st_best, st_snr};
+        heads[at] = PeakChunkHead{st_n, 0u, st_first, st_prev};
+    }
+}
+
+__global__ __launch_bounds__(64) void find_peaks_join_kernel(
+    const PeakChunkHead* __restrict__ heads, const PeakRecord* __restrict__ recs, uint32_t chunk, uint32_t nch,
+    double r, const double* __restrict__ freqs, uint32_t L, uint32_t* __restrict__ counts, uint32_t* __restrict__ rows, float* __restrict__ out, uint32_t cap)
+{
+    const uint64_t col = blockIdx.x;
+    const uint32_t lane = threadIdx.x;
+    const PeakChunkHead* hd = heads + col * nch;
+    const PeakRecord* rc0 = recs + col * nch * chunk;
+    uint32_t* orow = rows + col * cap;
+    float* osnr = out + col * cap;
+    const bool last_wins = peak_last_wins(freqs, L);
+    uint32_t cnt = 0;
+    bool open = false;
+    PeakRecord best{0u, 0.f};
+    double flast = 0.0;
+    for (uint32_t c0 = 0; c0 < nch; c0 += 64) {
+        PeakChunkHead h{0u, 0u, 0.0, 0.0};
+        if (c0 + lane < nch) h = hd[c0 + lane];
+        uint64_t any = __ballot(h.n != 0);
+        while (any) {
+            const int l = __builtin_ctzll(any);
+            any &= any - 1;
+            const uint32_t n = __shfl(h.n, l);
+            const double ff = __shfl(h.f_first, l), fl = __shfl(h.f_last, l);
+            const PeakRecord* rc = rc0 + (uint64_t)(c0 + l) * chunk;
+            const bool joined = open && !peak_breaks(ff, flast, r);
+            if (joined) {
+                const PeakRecord first = rc[0];
+                if (peak_better(first.snr, best.snr, last_wins)) best = first;
+            }
+            if (open && (!joined || n > 1)) {       // the open cluster ends here
+                if (lane == 0 && cnt < cap) {
+                    orow[cnt] = best.row;
+                    osnr[cnt] = best.snr;
+                }
+                ++cnt;
+            }
+            const uint32_t start = joined ? 1u : 0u;
+            if (n > start) {
+                const uint32_t inner = n - 1 - start;
+                for (uint32_t k = lane; k < inner; k += 64) {
+                    const uint64_t at = (uint64_t)cnt + k;
+                    if (at < cap) {
+                        const PeakRecord p = rc[start + k];
+                        orow[at] = p.row;
+                        osnr[at] = p.snr;
+                    }
+                }
+                cnt += inner;
+                best = rc[n - 1];
+            }
+            open = true;
+            flast = fl;
+        }
+    }
+    if (lane == 0) {
+        if (open) {
+            if (cnt < cap) {
+                orow[cnt] = best.row;
+                osnr[cnt] = best.snr;
+            }
+            ++cnt;
+        }
+        counts[col] = cnt;
+    }
+}
+
+hipError_t launch_find_peaks(const float* snrs, uint64_t snr_stride, uint32_t batch, uint32_t L, uint32_t W,
+                             const double* logf, const double* freqs, const double* coeffs, uint32_t ncoef,
+                             double smin, double r, uint32_t* counts, uint32_t* rows, float* out, uint32_t cap,
+                             uint32_t chunk, void* workspace, hipStream_t s)
+{
+    if (!batch || !W || !L) return hipSuccess;
+    const uint32_t nch = (uint32_t)peak_chunks(L, chunk);
+    PeakChunkHead* heads = static_cast<PeakChunkHead*>(workspace);
+    PeakRecord* recs = reinterpret_cast<PeakRecord*>(heads + (uint64_t)batch * W * nch);
+    hipLaunchKernelGGL(find_peaks_chunk_kernel, dim3(nch, (W + kPeakWidthGroup - 1) / kPeakWidthGroup, batch),
+                       dim3(kFindBlock), 0, s, snrs, snr_stride, L, W, logf, freqs, coeffs, ncoef, smin, r, chunk, nch,
+                       heads, recs);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(find_peaks_join_kernel, dim3(batch * W), dim3(64), 0, s, heads, recs, chunk, nch, r, freqs,
+                       L, counts, rows, out, cap);
     return hipGetLastError();
 }
 

@@ -54,12 +54,16 @@ class EngineSearcher:
     Calling it on a list of Trial returns one peak list per trial, in the
     order given (each in range order, as WorkerPool.process_fname)."""
 
-    def __init__(self, deredden_params, range_confs, device=None, batch=8, check=True):
+    def __init__(self, deredden_params, range_confs, device=None, batch=8, check=True, device_cluster=None):
         self.deredden_params = dict(deredden_params)
         self.range_confs = list(range_confs)
         self.device = device
         self.batch = int(batch)
         self.check = bool(check)
+        # clustering and the argmax per cluster on the device (PeakFinder's
+        # device_cluster); None: the A/B switch RIPTIDE_AMD_DEVICE_PEAKS
+        self.device_cluster = (bool(os.environ.get("RIPTIDE_AMD_DEVICE_PEAKS")) if device_cluster is None
+                               else bool(device_cluster))
         self._plans = {}
         self._finders = {}
         self._ws = {}
@@ -80,7 +84,7 @@ class EngineSearcher:
         kw = conf.get("find_peaks", {}) or {}
         key = (id(plan), tobs, tuple(sorted(kw.items())))
         if key not in self._finders:
-            self._finders[key] = PeakFinder(plan, tobs, **kw)
+            self._finders[key] = PeakFinder(plan, tobs, device_cluster=self.device_cluster, **kw)
         return self._finders[key]
 
     def _workspace(self, plan, B):

@@ -14,6 +14,10 @@ branch) from the order statistics, np.polyfit / np.poly1d for the threshold
 (batched bit for bit: polyfit_columns),
 np.where order, cluster1d and the argmax per cluster -- so the peaks and
 threshold polynomials are identical to riptide's for the same S/N.
+
+With `device_cluster=True` the clustering and the argmax run on the device
+too (rt_find_peaks_device: an ordered walk along every column, the first
+maximum of each cluster) and only the peaks' (row, S/N) come back.
 """
 from math import ceil
 
@@ -118,7 +122,7 @@ class PeakFinder:
     """
 
     def __init__(self, plan, tobs, smin=6.0, segwidth=5.0, nstd=6.0, minseg=10, polydeg=2, clrad=0.1,
-                 max_selected=1 << 16):
+                 max_selected=1 << 16, device_cluster=False, max_peaks=4096):
         import torch
         self.plan = plan
         self.tobs = float(tobs)
@@ -143,6 +147,10 @@ class PeakFinder:
         self.logf = torch.from_numpy(np.log(f)).to(plan.device)
         self.ncoef = self.polydeg + 1 if self.nseg >= self.minseg else 1
         self.cap = int(min(max_selected, max(L, 1)))
+        self.device_cluster = bool(device_cluster)
+        self.max_peaks = int(min(max(int(max_peaks), 1), max(L, 1)))    # clusters kept per (trial, width)
+        if self.device_cluster:
+            self.d_freqs = torch.from_numpy(np.ascontiguousarray(f, dtype=np.float64)).to(plan.device)
 
     def _threshold_polys(self, stats):
         """Per (trial, width) threshold coefficients and the reference's polyco."""
@@ -185,6 +193,8 @@ class PeakFinder:
                                                 _lib.ptr(ranks), ranks.size, _lib.ptr(stats), sh))
         coeffs, polycos = self._threshold_polys(stats.cpu().numpy())
         d_coeffs = torch.from_numpy(coeffs).to(dev)
+        if self.device_cluster:
+            return self._finish_on_device(snr, dms, coeffs, polycos, d_coeffs, sh)
         counts = torch.empty(B * W, dtype=torch.int32, device=dev)
         idx = torch.empty(B * W * self.cap, dtype=torch.int32, device=dev)
         _check(_L.rt_threshold_select_device(_lib.ptr(snr), B, L * W, L, W, _lib.ptr(self.logf), _lib.ptr(d_coeffs),
@@ -234,6 +244,60 @@ class PeakFinder:
                     peaks.append(Peak(period=float(1.0 / freq), freq=freq, width=width,
                                       ducy=float(float(width) / self.foldbins[ip]), iw=int(iw), ip=ip,
                                       snr=float(s_sel[j]), dm=dms[b]))
+            peaks = sorted(peaks, key=lambda p: p.snr, reverse=True)
+            results.append((peaks, {iw: polycos[b][iw] for iw in range(W)}))
+        return results
+
+    def _peak(self, iw, ip, s, dm):
+        """find_peaks' Peak of row ip of width iw (peak_detection.py:205-218)."""
+        width = int(self.plan.widths[iw])
+        freq = float(self.freqs[ip])
+        return Peak(period=float(1.0 / freq), freq=freq, width=width, ducy=float(float(width) / self.foldbins[ip]),
+                    iw=int(iw), ip=int(ip), snr=float(s), dm=dm)
+
+    def _finish_on_device(self, snr, dms, coeffs, polycos, d_coeffs, sh):
+        """Selection, clustering and the argmax per cluster in one device call
+        (rt_find_peaks_device); the counts and the used part of the records
+        come back, nothing sized by the selection.  A column with more than
+        max_peaks clusters is redone on the host from its own S/N column."""
+        import ctypes
+        import torch
+        B, L, W = snr.shape
+        dev, cap = snr.device, self.max_peaks
+        need = ctypes.c_size_t()
+        _check(_L.rt_find_peaks_workspace_bytes(B, L, W, 0, ctypes.byref(need)))
+        ws = torch.empty(max(need.value, 8), dtype=torch.uint8, device=dev)    # the stream's allocator
+        counts = torch.empty(B * W, dtype=torch.int32, device=dev)
+        rows = torch.empty((B * W, cap), dtype=torch.int32, device=dev)
+        vals = torch.empty((B * W, cap), dtype=torch.float32, device=dev)
+        _check(_L.rt_find_peaks_device(_lib.ptr(snr), B, L * W, L, W, _lib.ptr(self.logf), _lib.ptr(self.d_freqs),
+                                       _lib.ptr(d_coeffs), coeffs.shape[2], self.smin, self.clrad / self.tobs,
+                                       _lib.ptr(counts), _lib.ptr(rows), _lib.ptr(vals), cap, 0, _lib.ptr(ws),
+                                       ws.numel(), sh))
+        counts_h = counts.cpu().numpy().astype(np.int64)
+        maxc = int(min(counts_h.max(initial=0), cap))
+        if maxc:
+            rows_h = rows[:, :maxc].cpu().numpy()
+            vals_h = vals[:, :maxc].cpu().numpy()
+        falling = L > 1 and self.freqs[-1] < self.freqs[0]      # a plan's grid: periods rise
+        results = []
+        for b in range(B):
+            peaks = []
+            for iw in range(W):
+                c = int(counts_h[b * W + iw])
+                if c > cap:               # truncated: the column's mask and clusters on the host
+                    col = snr[b, :, iw].double().cpu().numpy()
+                    thr = np.poly1d(polycos[b][iw])(np.log(self.freqs))
+                    sel = np.where((col > thr) & (col > self.smin))[0]
+                    s_sel = col[sel]
+                    for cl in cluster1d(self.freqs[sel], self.clrad / self.tobs):
+                        j = cl[s_sel[cl].argmax()]
+                        peaks.append(self._peak(iw, int(sel[j]), s_sel[j], dms[b]))
+                    continue
+                r, v = (rows_h[b * W + iw], vals_h[b * W + iw]) if c else ((), ())
+                # cluster1d's order: ascending frequency
+                order = range(c - 1, -1, -1) if falling else range(c)
+                peaks.extend(self._peak(iw, int(r[k]), v[k], dms[b]) for k in order)
             peaks = sorted(peaks, key=lambda p: p.snr, reverse=True)
             results.append((peaks, {iw: polycos[b][iw] for iw in range(W)}))
         return results
