@@ -385,6 +385,62 @@ int rt_flag_harmonics(const double* freq, const double* snr, const double* ducy,
  * milliseconds (HIP events).  Any pointer may be NULL. */
 int rt_flag_harmonics_stats(uint64_t* tiles, uint64_t* near_pairs, uint64_t* host_rows, double* kernel_ms);
 
+/* ------------------------ incoherent dedispersion -------------------------- */
+/* Channelised data (SIGPROC filterbank order: time-major [nsamp, nchans], the
+ * channel fastest) summed along the dispersion sweep of each trial DM:
+ *   out[d, t] = sum over unmasked channels c of x[t + delay[d, c], c]
+ * Sample type codes: */
+#define RT_DEDISP_U8  0
+#define RT_DEDISP_I8  1
+#define RT_DEDISP_F32 2
+/* 8-bit sums are exact integers in float32 while 255 * nchans < 2^24 */
+#define RT_DEDISP_MAX_CHANS_8BIT 65793
+
+/* Host only, no device: the delay table, in samples, against the highest
+ * frequency f_ref = max(freqs_mhz).  In float64, in this order:
+ *   a = 1.0 / (f * f) - 1.0 / (f_ref * f_ref)
+ *   delay[d, c] = (int64) floor(kdm * dm[d] * a / tsamp + 0.5)
+ * kdm is the dispersion constant in s MHz^2 cm^3 / pc (1 / 2.41e-4 in the
+ * PRESTO / pulsar-timing convention).  *max_delay (may be NULL) is the largest
+ * entry.  RT_EINVAL for nchans == 0 or ndm == 0, a frequency that is not
+ * positive and finite, a DM that is negative or not finite, tsamp <= 0, or a
+ * delay of 2^31 samples or more. */
+int rt_dedisperse_delays(const double* freqs_mhz, size_t nchans, const double* dms, size_t ndm, double tsamp,
+                         double kdm, int64_t* delays, int64_t* max_delay);
+/* Host only, no device: the specification the kernels are pinned to.  x is
+ * [nsamp, nchans] of the sample type, delays [ndm, nchans] with every entry in
+ * [0, max_delay], mask NULL or [nchans] with non-zero = channel skipped, out
+ * [ndm, nout].  8-bit data is summed in int32, float data in float32 in
+ * channel order.  RT_EINVAL when nout + max_delay > nsamp, a delay lies outside
+ * [0, max_delay], the type code is unknown, or 8-bit data has more than
+ * RT_DEDISP_MAX_CHANS_8BIT channels. */
+int rt_dedisperse_host(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
+                       const uint8_t* mask, size_t ndm, int64_t max_delay, size_t nout, float* out);
+/* Device workspace bytes of rt_dedisperse_device for a block of nsamp_blk
+ * samples: the block transposed to channel-major, rows padded to 16 bytes. */
+int rt_dedisperse_workspace_bytes(int dtype, size_t nsamp_blk, size_t nchans, size_t* bytes);
+/* One resident block of nsamp_blk time samples, d_block [nsamp_blk, nchans]:
+ * writes d_out[d * out_stride + out_offset + t] for t in [0, nsamp_blk -
+ * max_delay), exactly the outputs whose reads all fall inside the block.
+ * d_delays is int32 [ndm, nchans] (entries are clamped to [0, max_delay]),
+ * d_mask NULL or uint8 [nchans].  Stream-ordered, no host synchronisation; no
+ * load leaves the block or the workspace.  d_block must be aligned to its
+ * sample type, d_workspace to 16 bytes.  8-bit results are exact; float32
+ * results are summed in channel order.  RT_EINVAL (nothing is launched) for
+ * an unknown type code, nchans == 0, ndm == 0, max_delay outside [0,
+ * nsamp_blk), nsamp_blk >= 2^31, out_stride < out_offset + nsamp_blk -
+ * max_delay, 8-bit data with more than RT_DEDISP_MAX_CHANS_8BIT channels, a
+ * NULL or misaligned pointer, or a workspace below
+ * rt_dedisperse_workspace_bytes. */
+int rt_dedisperse_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans, const int32_t* d_delays,
+                         const uint8_t* d_mask, size_t ndm, int64_t max_delay, float* d_out, size_t out_stride,
+                         size_t out_offset, void* d_workspace, size_t workspace_bytes, void* stream);
+/* Host-buffer form: uploads x [nsamp, nchans], the delays (int64, as
+ * rt_dedisperse_delays writes them) and the mask, runs the kernels, copies out
+ * [ndm, nsamp - max_delay] back.  Synchronous. */
+int rt_dedisperse(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays, const uint8_t* mask,
+                  size_t ndm, int64_t max_delay, float* out);
+
 /* --------------------------- file input (device) --------------------------- */
 /* 8-bit SIGPROC samples (riptide/time_series.py:352-357) to float32 in device
  * memory: d_raw holds n bytes, int8 when is_signed else uint8; exact as

@@ -91,6 +91,17 @@ _SIGNATURES = {
     "rt_hdiag_pairs": (_c_i, [_vp, _vp, _vp, _vp, _c_sz, _vp, _vp, _c_sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rt_flag_harmonics": (_c_i, [_vp, _vp, _vp, _vp, _c_sz, _vp, _c_sz, _vp, _vp, _vp]),
     "rt_flag_harmonics_stats": (_c_i, [_pu64, _pu64, _pu64, _pd]),
+    # freqs, nchans, dms, ndm, tsamp, kdm, delays (int64), max_delay
+    "rt_dedisperse_delays": (_c_i, [_vp, _c_sz, _vp, _c_sz, _c_d, _c_d, _vp, ctypes.POINTER(ctypes.c_int64)]),
+    # x, dtype, nsamp, nchans, delays (int64), mask, ndm, max_delay, nout, out
+    "rt_dedisperse_host": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _c_sz, ctypes.c_int64, _c_sz, _vp]),
+    "rt_dedisperse_workspace_bytes": (_c_i, [_c_i, _c_sz, _c_sz, _psz]),
+    # block, dtype, nsamp_blk, nchans, delays (int32), mask, ndm, max_delay, out, out_stride, out_offset,
+    # workspace, workspace bytes, stream
+    "rt_dedisperse_device": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _c_sz, ctypes.c_int64, _vp, _c_sz, _c_sz,
+                                    _vp, _c_sz, _vp]),
+    # x, dtype, nsamp, nchans, delays (int64), mask, ndm, max_delay, out
+    "rt_dedisperse": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _c_sz, ctypes.c_int64, _vp]),
 }
 
 EXPORTED = tuple(_SIGNATURES)

@@ -1,0 +1,177 @@
+// Host-only checker of the dedispersion delay table and specification
+// (rt_dedisperse_delays, rt_dedisperse_host: dedisp_host.cpp), built with
+// AddressSanitizer + UBSan by `make -C riptide_amd/csrc asan`.  Every array is
+// a heap block of exactly the size the entry point may touch, so a read past
+// the last sample, a delay row or the mask is a sanitizer report.  No device
+// call, and none linked.  Usage:
+//   dedisp_check
+// Runs the edge shapes (1, 3, 37, 64, 65 channels, both band orders, DM 0,
+// nout = nsamp - max_delay and nout = 1, with and without a mask, the three
+// sample types) against a recount, then every error return.  Exit status 0
+// iff all agree.
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "riptide_amd.h"
+
+namespace {
+
+uint64_t g_state = 12345;
+uint32_t draw()
+{
+    g_state = g_state * 6364136223846793005ull + 1442695040888963407ull;
+    return (uint32_t)(g_state >> 33);
+}
+
+int fails = 0;
+void expect(bool ok, const char* what)
+{
+    if (!ok) {
+        std::printf("FAILED: %s (%s)\n", what, rt_last_error());
+        ++fails;
+    }
+}
+
+template <class T>
+double sample(const std::vector<unsigned char>& x, size_t i)
+{
+    T v;
+    std::memcpy(&v, x.data() + i * sizeof(T), sizeof(T));
+    return (double)v;
+}
+
+void run_shape(size_t nchans, bool ascending, int dtype, bool masked, bool single_out)
+{
+    const double tsamp = 1e-3, kdm = 1.0 / 2.41e-4;
+    const double dms_[] = {0.0, 50.0, 12.5, 50.0, 3.0};
+    const size_t ndm = 5;
+    std::vector<double> freqs(nchans), dms(dms_, dms_ + ndm);
+    for (size_t c = 0; c < nchans; ++c) {
+        const double step = 32.0 / (double)nchans;
+        freqs[c] = ascending ? 368.0 + step * (double)c : 400.0 - step * (double)c;
+    }
+    std::vector<int64_t> delays(ndm * nchans);
+    int64_t max_delay = -1;
+    expect(rt_dedisperse_delays(freqs.data(), nchans, dms.data(), ndm, tsamp, kdm, delays.data(), &max_delay) == RT_OK,
+           "delays");
+    for (size_t c = 0; c < nchans; ++c) expect(delays[c] == 0, "DM 0 has zero delays");
+    int64_t recount = 0;
+    for (int64_t v : delays) recount = v > recount ? v : recount;
+    expect(recount == max_delay, "max_delay");
+    const size_t nsamp = (size_t)max_delay + 300;
+    const size_t nout = single_out ? 1 : nsamp - (size_t)max_delay;
+    const size_t esize = dtype == RT_DEDISP_F32 ? 4 : 1;
+    std::vector<unsigned char> x(nsamp * nchans * esize);
+    for (size_t i = 0; i < nsamp * nchans; ++i) {
+        if (dtype == RT_DEDISP_F32) {
+            const float v = (float)((double)draw() / 4294967296.0 - 0.5);
+            std::memcpy(x.data() + 4 * i, &v, 4);
+        } else {
+            x[i] = (unsigned char)draw();
+        }
+    }
+    std::vector<uint8_t> mask;
+    if (masked) {
+        mask.assign(nchans, 0);
+        mask[0] = 1;
+        mask[nchans - 1] = 1;
+        if (nchans > 4) mask[nchans / 2] = 1;
+    }
+    std::vector<float> out(ndm * nout);
+    expect(rt_dedisperse_host(x.data(), dtype, nsamp, nchans, delays.data(), masked ? mask.data() : nullptr, ndm,
+                              max_delay, nout, out.data()) == RT_OK,
+           "dedisperse_host");
+    for (size_t d = 0; d < ndm; ++d)
+        for (size_t t = 0; t < nout; ++t) {
+            double ref = 0.0, mag = 0.0;
+            for (size_t c = 0; c < nchans; ++c) {
+                if (masked && mask[c]) continue;
+                const size_t i = (t + (size_t)delays[d * nchans + c]) * nchans + c;
+                const double v = dtype == RT_DEDISP_U8 ? sample<uint8_t>(x, i)
+                                 : dtype == RT_DEDISP_I8 ? sample<int8_t>(x, i) : sample<float>(x, i);
+                ref += v;
+                mag += std::fabs(v);
+            }
+            const double tol = dtype == RT_DEDISP_F32 ? (double)nchans * std::ldexp(1.0, -24) * mag : 0.0;
+            if (std::fabs((double)out[d * nout + t] - ref) > tol) {
+                std::printf("FAILED: nchans %zu dtype %d dm %zu t %zu: %g vs %g\n", nchans, dtype, d, t,
+                            (double)out[d * nout + t], ref);
+                ++fails;
+                return;
+            }
+        }
+}
+
+void run_errors()
+{
+    std::vector<double> f{400.0, 390.0}, dm{1.0};
+    std::vector<int64_t> del(2);
+    int64_t md = 0;
+    auto delays = [&](size_t nchans, size_t ndm, double tsamp) {
+        return rt_dedisperse_delays(f.data(), nchans, dm.data(), ndm, tsamp, 1.0 / 2.41e-4, del.data(), &md);
+    };
+    expect(delays(0, 1, 1e-3) == RT_EINVAL, "nchans == 0");
+    expect(delays(2, 0, 1e-3) == RT_EINVAL, "ndm == 0");
+    expect(delays(2, 1, 0.0) == RT_EINVAL, "tsamp == 0");
+    expect(delays(2, 1, -1.0) == RT_EINVAL, "tsamp < 0");
+    f[1] = 0.0;
+    expect(delays(2, 1, 1e-3) == RT_EINVAL, "zero frequency");
+    f[1] = -5.0;
+    expect(delays(2, 1, 1e-3) == RT_EINVAL, "negative frequency");
+    f[1] = INFINITY;
+    expect(delays(2, 1, 1e-3) == RT_EINVAL, "infinite frequency");
+    f[1] = NAN;
+    expect(delays(2, 1, 1e-3) == RT_EINVAL, "NaN frequency");
+    f[1] = 390.0;
+    dm[0] = -1.0;
+    expect(delays(2, 1, 1e-3) == RT_EINVAL, "negative DM");
+    dm[0] = NAN;
+    expect(delays(2, 1, 1e-3) == RT_EINVAL, "NaN DM");
+    dm[0] = INFINITY;
+    expect(delays(2, 1, 1e-3) == RT_EINVAL, "infinite DM");
+    dm[0] = 1.0;
+    expect(delays(2, 1, 1e-16) == RT_EINVAL, "delay of 2^31 or more");
+    expect(delays(2, 1, 1e-3) == RT_OK, "valid call after the errors");
+
+    std::vector<uint8_t> x(10 * 2, 1);
+    std::vector<float> out(10);
+    std::vector<int64_t> d2{0, 3};
+    expect(rt_dedisperse_host(x.data(), RT_DEDISP_U8, 10, 2, d2.data(), nullptr, 1, 3, 8, out.data()) == RT_EINVAL,
+           "nout + max_delay > nsamp");
+    expect(rt_dedisperse_host(x.data(), RT_DEDISP_U8, 10, 2, d2.data(), nullptr, 1, 3, 7, out.data()) == RT_OK,
+           "nout + max_delay == nsamp");
+    expect(out[6] == 2.0f, "last output reads the last sample");
+    expect(rt_dedisperse_host(x.data(), 7, 10, 2, d2.data(), nullptr, 1, 3, 7, out.data()) == RT_EINVAL,
+           "unknown type code");
+    expect(rt_dedisperse_host(x.data(), RT_DEDISP_U8, 10, 2, d2.data(), nullptr, 1, 2, 7, out.data()) == RT_EINVAL,
+           "delay above max_delay");
+    d2[1] = -1;
+    expect(rt_dedisperse_host(x.data(), RT_DEDISP_U8, 10, 2, d2.data(), nullptr, 1, 3, 7, out.data()) == RT_EINVAL,
+           "negative delay");
+    expect(rt_dedisperse_host(x.data(), RT_DEDISP_U8, 10, 0, d2.data(), nullptr, 1, 3, 7, out.data()) == RT_EINVAL,
+           "nchans == 0 (host)");
+}
+
+}  // namespace
+
+int main()
+{
+    const size_t chans[] = {1, 3, 37, 64, 65};
+    for (size_t nchans : chans)
+        for (int asc = 0; asc < 2; ++asc)
+            for (int dtype = 0; dtype < 3; ++dtype)
+                for (int masked = 0; masked < 2; ++masked)
+                    for (int single = 0; single < 2; ++single) {
+                        if (masked && nchans < 3) continue;
+                        run_shape(nchans, asc != 0, dtype, masked != 0, single != 0);
+                    }
+    run_errors();
+    if (fails)
+        std::printf("dedisp_check: %d failures\n", fails);
+    else
+        std::printf("dedisp_check OK\n");
+    return fails ? 1 : 0;
+}

@@ -1,0 +1,99 @@
+// Incoherent dedispersion, host side: the delay table every caller shares and
+// the specification the kernels of dedisp_kernels.hip are pinned to
+// (rt_dedisperse_host, in the role rt_find_peaks_host and rt_hdiag_host play
+// for theirs).  No HIP header (`make asan` builds this file as is).
+#include "riptide_amd.h"
+
+#include <cmath>
+#include <stdexcept>
+#include <string>
+
+#include "capi_common.hpp"
+
+using namespace rt;
+
+namespace {
+
+template <class T, class Acc>
+void dedisperse_rows(const T* x, size_t nchans, const int64_t* delays, const uint8_t* mask, size_t ndm, size_t nout,
+                     float* out)
+{
+    for (size_t d = 0; d < ndm; ++d) {
+        const int64_t* del = delays + d * nchans;
+        float* o = out + d * nout;
+        for (size_t t = 0; t < nout; ++t) {
+            Acc acc = 0;
+            for (size_t c = 0; c < nchans; ++c)
+                if (!mask || !mask[c]) acc += (Acc)x[(t + (size_t)del[c]) * nchans + c];
+            o[t] = (float)acc;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_dedisperse_delays(const double* freqs_mhz, size_t nchans, const double* dms, size_t ndm, double tsamp,
+                         double kdm, int64_t* delays, int64_t* max_delay)
+{
+    return guarded([&] {
+        if (!nchans || !ndm) throw std::invalid_argument("dedisperse: nchans and ndm must be at least 1");
+        if (!(tsamp > 0.0) || !std::isfinite(tsamp)) throw std::invalid_argument("dedisperse: tsamp must be > 0");
+        if (!std::isfinite(kdm)) throw std::invalid_argument("dedisperse: kdm must be finite");
+        double f_ref = 0.0;
+        for (size_t c = 0; c < nchans; ++c) {
+            const double f = freqs_mhz[c];
+            if (!(f > 0.0) || !std::isfinite(f))
+                throw std::invalid_argument("dedisperse: channel frequencies must be positive and finite");
+            if (f > f_ref) f_ref = f;
+        }
+        for (size_t d = 0; d < ndm; ++d)
+            if (!(dms[d] >= 0.0) || !std::isfinite(dms[d]))
+                throw std::invalid_argument("dedisperse: DMs must be non-negative and finite");
+        int64_t dmax = 0;
+        for (size_t d = 0; d < ndm; ++d)
+            for (size_t c = 0; c < nchans; ++c) {
+                const double f = freqs_mhz[c];
+                const double a = 1.0 / (f * f) - 1.0 / (f_ref * f_ref);
+                const double v = std::floor(kdm * dms[d] * a / tsamp + 0.5);
+                if (!(v < 2147483648.0) || !(v >= 0.0))
+                    throw std::invalid_argument("dedisperse: a delay is outside [0, 2^31) samples");
+                const int64_t k = (int64_t)v;
+                delays[d * nchans + c] = k;
+                if (k > dmax) dmax = k;
+            }
+        if (max_delay) *max_delay = dmax;
+        return RT_OK;
+    });
+}
+
+int rt_dedisperse_host(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
+                       const uint8_t* mask, size_t ndm, int64_t max_delay, size_t nout, float* out)
+{
+    return guarded([&] {
+        if (!nchans || !ndm) throw std::invalid_argument("dedisperse: nchans and ndm must be at least 1");
+        if (dtype != RT_DEDISP_U8 && dtype != RT_DEDISP_I8 && dtype != RT_DEDISP_F32)
+            throw std::invalid_argument("dedisperse: unknown sample type code");
+        if (max_delay < 0 || max_delay >= 2147483648ll)
+            throw std::invalid_argument("dedisperse: max_delay is outside [0, 2^31)");
+        if (nout > nsamp || (uint64_t)max_delay > nsamp - nout)
+            throw std::invalid_argument("dedisperse: nout + max_delay exceeds the " + std::to_string(nsamp) +
+                                        " samples of the input");
+        if (dtype != RT_DEDISP_F32 && nchans > RT_DEDISP_MAX_CHANS_8BIT)
+            throw std::invalid_argument("dedisperse: too many channels for an exact 8-bit sum");
+        for (size_t i = 0; i < ndm * nchans; ++i)
+            if (delays[i] < 0 || delays[i] > max_delay)
+                throw std::invalid_argument("dedisperse: a delay is outside [0, max_delay]");
+        if (!nout) return RT_OK;
+        if (dtype == RT_DEDISP_U8)
+            dedisperse_rows<uint8_t, int32_t>((const uint8_t*)x, nchans, delays, mask, ndm, nout, out);
+        else if (dtype == RT_DEDISP_I8)
+            dedisperse_rows<int8_t, int32_t>((const int8_t*)x, nchans, delays, mask, ndm, nout, out);
+        else
+            dedisperse_rows<float, float>((const float*)x, nchans, delays, mask, ndm, nout, out);
+        return RT_OK;
+    });
+}
+
+}  // extern "C"

@@ -1,0 +1,263 @@
+// Incoherent dedispersion for MI355X (gfx950): a resident block of
+// channelised samples, time-major [nsamp, nchans] as a SIGPROC filterbank
+// stores them, summed along the sweep of every trial DM
+//   out[d, t] = sum over unmasked c of x[t + delay[d, c], c]
+// (the specification: rt_dedisperse_host, dedisp_host.cpp).
+//
+//   dedisp_transpose*_kernel  the block to channel-major rows in the
+//                             workspace, through an LDS tile; 8-bit data stays
+//                             8-bit (signed samples are stored biased by 128),
+//                             the row pitch is padded to 16 bytes and the
+//                             padding is written as zero
+//   dedisp_sum_kernel         one workgroup = 16 DMs x 256 outputs; per step
+//                             of 16 channels the span of each channel that the
+//                             tile's DMs read is staged in LDS with aligned
+//                             dword loads, then every wave adds its four DMs
+//                             (one DM at a time, its delay wave-uniform)
+//
+// No load leaves its buffer: the transpose reads x only at t < nsamp, the
+// staging loads are clamped to the row's padded pitch inside the workspace,
+// and delays are clamped to [0, max_delay] as they are read.
+// Exactness: 8-bit sums are integers (16-bit packed partial sums of at most
+// 16 channels, then int32), converted once; float sums are float32 additions
+// in channel order.
+#include <hip/hip_runtime.h>
+
+#include "common.hpp"
+#include "kernels.hpp"
+
+namespace rt {
+
+namespace {
+
+constexpr uint32_t kDdThreads = 256;
+constexpr uint32_t kDdWaves = 4;
+constexpr uint32_t kDdTile = 256;       // outputs of a time tile: 4 per lane
+constexpr uint32_t kDdPerWave = 4;      // DMs a wave sums
+constexpr uint32_t kDdDms = kDdWaves * kDdPerWave;
+constexpr uint32_t kDdChans = 16;       // channels staged per step
+constexpr uint32_t kDdSkip = 0xFFFFFFFFu;     // channel masked or past nchans
+constexpr uint32_t kDdDirect = 0xFFFFFFFEu;   // span too long to stage: read from the workspace row
+
+// dwords of one channel's staged span: the time tile plus the spread of the
+// tile's delays (up to 794 samples of 8-bit data, 264 of float data; a wider
+// spread takes the direct path)
+template <class T>
+struct DdSpan {
+    static constexpr uint32_t dwords = sizeof(T) == 1 ? 264 : 520;
+};
+
+// 8-bit: tile of 64 channels x 256 samples, read a byte per lane along the
+// channels, written a dword per lane along time.
+__global__ __launch_bounds__(kDdThreads) void dedisp_transpose8_kernel(
+    const uint8_t* __restrict__ x, uint32_t nsamp, uint32_t nchans, uint8_t* __restrict__ ws, uint64_t pitch,
+    uint32_t flip)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t tile[64][260];
+    const uint32_t tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const uint64_t t0 = (uint64_t)blockIdx.x * 256;
+    const uint32_t c0 = blockIdx.y * 64;
+    const uint32_t c = c0 + tx;
+    for (uint32_t i = ty; i < 256; i += 4) {
+        const uint64_t t = t0 + i;
+        uint32_t v = 0;
+        if (c < nchans && t < nsamp) v = x[t * nchans + c] ^ flip;
+        tile[tx][i] = (uint8_t)v;
+    }
+    __syncthreads();
+    const uint64_t tb = t0 + tx * 4;
+    for (uint32_t i = ty; i < 64; i += 4) {
+        const uint32_t co = c0 + i;
+        if (co < nchans && tb < pitch)   // the pitch is a multiple of 16: the dword is inside the row
+            *reinterpret_cast<uint32_t*>(ws + (uint64_t)co * pitch + tb) =
+                *reinterpret_cast<const uint32_t*>(&tile[i][tx * 4]);
+    }
+}
+
+// float: tile of 64 channels x 64 samples.
+__global__ __launch_bounds__(kDdThreads) void dedisp_transpose32_kernel(
+    const float* __restrict__ x, uint32_t nsamp, uint32_t nchans, float* __restrict__ ws, uint64_t pitch)
+{
+    __shared__ float tile[64][65];
+    const uint32_t tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const uint64_t t0 = (uint64_t)blockIdx.x * 64;
+    const uint32_t c0 = blockIdx.y * 64;
+    const uint32_t c = c0 + tx;
+    for (uint32_t i = ty; i < 64; i += 4) {
+        const uint64_t t = t0 + i;
+        tile[tx][i] = (c < nchans && t < nsamp) ? x[t * nchans + c] : 0.0f;
+    }
+    __syncthreads();
+    const uint64_t t = t0 + tx;
+    for (uint32_t i = ty; i < 64; i += 4) {
+        const uint32_t co = c0 + i;
+        if (co < nchans && t < pitch) ws[(uint64_t)co * pitch + t] = tile[i][tx];
+    }
+}
+
+// T = uint8_t (signed samples biased by 128: bias = 128) or float.  pitch is
+// in elements.  Lane l of a wave owns the outputs t0 + 4 l + j (8-bit) or
+// t0 + l + 64 j (float), j = 0..3, of each of the wave's four DMs.
+template <class T>
+__global__ __launch_bounds__(kDdThreads) void dedisp_sum_kernel(
+    const T* __restrict__ ws, uint64_t pitch, uint32_t nchans, const int32_t* __restrict__ delays,
+    const uint8_t* __restrict__ mask, uint32_t ndm, uint32_t max_delay, uint32_t nout, float* __restrict__ out,
+    uint64_t out_stride, int32_t bias)
+{
+    constexpr bool kBytes = sizeof(T) == 1;
+    constexpr uint32_t kE = 4 / sizeof(T);   // elements per dword
+    constexpr uint32_t kSpan = DdSpan<T>::dwords;
+    using Acc = typename std::conditional<kBytes, int32_t, float>::type;
+    __shared__ uint32_t span[kDdChans][kSpan + 1];   // + 1: the high dword of an aligned last read
+    __shared__ int32_t sdel[kDdDms][kDdChans];
+    __shared__ uint32_t sbase[kDdChans];
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t t0 = blockIdx.x * kDdTile;
+    const uint32_t d0 = blockIdx.y * kDdDms;
+    const uint32_t row_dw = (uint32_t)(pitch / kE);
+    Acc acc[kDdPerWave][4];
+#pragma unroll
+    for (uint32_t r = 0; r < kDdPerWave; ++r)
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) acc[r][j] = 0;
+    int32_t nsum = 0;
+
+    for (uint32_t c0 = 0; c0 < nchans; c0 += kDdChans) {
+        __syncthreads();   // the previous step's spans and delays are consumed
+        {
+            // the tile's delays: rows past ndm repeat the last DM (never stored)
+            const uint32_t dd = tid >> 4, cc = tid & 15;
+            const uint32_t d = min(d0 + dd, ndm - 1), c = c0 + cc;
+            int32_t v = 0;
+            if (c < nchans) v = min(max(delays[(uint64_t)d * nchans + c], 0), (int32_t)max_delay);
+            sdel[dd][cc] = v;
+        }
+        __syncthreads();
+        for (uint32_t cc = wave; cc < kDdChans; cc += kDdWaves) {
+            const uint32_t c = c0 + cc;
+            if (c >= nchans || (mask && mask[c])) {
+                if (lane == 0) sbase[cc] = kDdSkip;
+                continue;
+            }
+            // smallest and largest delay of the tile's 16 DMs: 16 broadcast
+            // LDS reads, the same in every lane (a cross-lane butterfly over
+            // one read per lane measured 4 % slower for the whole call)
+            int32_t lo = sdel[0][cc], hi = lo;
+#pragma unroll
+            for (uint32_t dd = 1; dd < kDdDms; ++dd) {
+                lo = min(lo, sdel[dd][cc]);
+                hi = max(hi, sdel[dd][cc]);
+            }
+            const uint32_t e0 = (t0 + (uint32_t)lo) & ~(kE - 1);   // first element staged
+            const uint32_t e1 = t0 + kDdTile + (uint32_t)hi;        // one past the last element read
+            const uint32_t ndw = (e1 - e0 + kE - 1) / kE;
+            if (ndw > kSpan) {
+                if (lane == 0) sbase[cc] = kDdDirect;
+                continue;
+            }
+            const uint32_t* row = reinterpret_cast<const uint32_t*>(ws + (uint64_t)c * pitch);
+            const uint32_t w0 = e0 / kE;
+            for (uint32_t i = lane; i < ndw; i += 64) {
+                const uint32_t w = w0 + i;
+                span[cc][i] = w < row_dw ? row[w] : 0u;
+            }
+            if (lane == 0) sbase[cc] = e0;
+        }
+        __syncthreads();
+
+        uint32_t pe[kDdPerWave], po[kDdPerWave];   // 8-bit: 16-bit partial sums of outputs (0, 2) and (1, 3)
+#pragma unroll
+        for (uint32_t r = 0; r < kDdPerWave; ++r) pe[r] = po[r] = 0;
+        for (uint32_t cc = 0; cc < kDdChans; ++cc) {
+            const uint32_t base = __builtin_amdgcn_readfirstlane(sbase[cc]);
+            if (base == kDdSkip) continue;
+            ++nsum;
+            if (base == kDdDirect) {
+                const T* row = ws + (uint64_t)(c0 + cc) * pitch;
+#pragma unroll
+                for (uint32_t r = 0; r < kDdPerWave; ++r) {
+                    const uint32_t del = (uint32_t)__builtin_amdgcn_readfirstlane(sdel[wave * kDdPerWave + r][cc]);
+#pragma unroll
+                    for (uint32_t j = 0; j < 4; ++j) {
+                        const uint64_t e = (uint64_t)t0 + del + (kBytes ? lane * 4 + j : lane + 64 * j);
+                        acc[r][j] += e < pitch ? (Acc)row[e] : (Acc)0;
+                    }
+                }
+                continue;
+            }
+#pragma unroll
+            for (uint32_t r = 0; r < kDdPerWave; ++r) {
+                const uint32_t del = (uint32_t)__builtin_amdgcn_readfirstlane(sdel[wave * kDdPerWave + r][cc]);
+                const uint32_t p = t0 + del - base;   // element of output t0 in the span
+                if constexpr (kBytes) {
+                    const uint32_t w = (p >> 2) + lane;
+                    const uint32_t v = __builtin_amdgcn_alignbyte(span[cc][w + 1], span[cc][w], p & 3);
+                    pe[r] += v & 0x00FF00FFu;
+                    po[r] += (v >> 8) & 0x00FF00FFu;
+                } else {
+#pragma unroll
+                    for (uint32_t j = 0; j < 4; ++j) acc[r][j] += __uint_as_float(span[cc][p + lane + 64 * j]);
+                }
+            }
+        }
+        if constexpr (kBytes) {   // at most 16 x 255 per 16-bit field
+#pragma unroll
+            for (uint32_t r = 0; r < kDdPerWave; ++r) {
+                acc[r][0] += (int32_t)(pe[r] & 0xFFFFu);
+                acc[r][1] += (int32_t)(po[r] & 0xFFFFu);
+                acc[r][2] += (int32_t)(pe[r] >> 16);
+                acc[r][3] += (int32_t)(po[r] >> 16);
+            }
+        }
+    }
+
+#pragma unroll
+    for (uint32_t r = 0; r < kDdPerWave; ++r) {
+        const uint32_t d = d0 + wave * kDdPerWave + r;
+        if (d >= ndm) continue;
+        float* o = out + (uint64_t)d * out_stride;
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t t = t0 + (kBytes ? lane * 4 + j : lane + 64 * j);
+            if (t >= nout) continue;
+            if constexpr (kBytes) o[t] = (float)(acc[r][j] - bias * nsum);
+            else o[t] = acc[r][j];
+        }
+    }
+}
+
+}  // namespace
+
+uint64_t dedisp_pitch_bytes(int dtype, uint64_t nsamp_blk)
+{
+    const uint64_t esize = dtype == 2 ? 4 : 1;
+    return (nsamp_blk * esize + 15) / 16 * 16;
+}
+
+hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
+                             const int32_t* d_delays, const uint8_t* d_mask, uint32_t ndm, uint32_t max_delay,
+                             float* out, uint64_t out_stride, void* ws, hipStream_t s)
+{
+    const uint32_t nout = nsamp_blk - max_delay;
+    const uint64_t pitch_bytes = dedisp_pitch_bytes(dtype, nsamp_blk);
+    const dim3 sum_grid((nout + kDdTile - 1) / kDdTile, (ndm + kDdDms - 1) / kDdDms);
+    if (dtype == 2) {
+        const uint64_t pitch = pitch_bytes / 4;
+        const dim3 grid((uint32_t)((pitch + 63) / 64), (nchans + 63) / 64);
+        hipLaunchKernelGGL(dedisp_transpose32_kernel, grid, dim3(kDdThreads), 0, s, (const float*)block, nsamp_blk,
+                           nchans, (float*)ws, pitch);
+        hipLaunchKernelGGL(dedisp_sum_kernel<float>, sum_grid, dim3(kDdThreads), 0, s, (const float*)ws, pitch,
+                           nchans, d_delays, d_mask, ndm, max_delay, nout, out, out_stride, 0);
+    } else {
+        const dim3 grid((uint32_t)((pitch_bytes + 255) / 256), (nchans + 63) / 64);
+        hipLaunchKernelGGL(dedisp_transpose8_kernel, grid, dim3(kDdThreads), 0, s, (const uint8_t*)block, nsamp_blk,
+                           nchans, (uint8_t*)ws, pitch_bytes, dtype == 1 ? 0x80u : 0u);
+        hipLaunchKernelGGL(dedisp_sum_kernel<uint8_t>, sum_grid, dim3(kDdThreads), 0, s, (const uint8_t*)ws,
+                           pitch_bytes, nchans, d_delays, d_mask, ndm, max_delay, nout, out, out_stride,
+                           dtype == 1 ? 128 : 0);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace rt

@@ -102,6 +102,17 @@ hipError_t launch_fold_rows(const float* data, uint64_t n_in, const FoldCand* d_
 hipError_t launch_fold_subints(const FoldCand* d_cands, uint32_t num_cands, uint32_t total_blocks, float* out,
                                const float* rows_ws, hipStream_t s);
 
+// dedisp_kernels.hip
+// bytes of one channel-major row of the transposed block (dtype: the
+// RT_DEDISP_* code of riptide_amd.h), a multiple of 16
+uint64_t dedisp_pitch_bytes(int dtype, uint64_t nsamp_blk);
+// out[d * out_stride + t] for t < nsamp_blk - max_delay; ws: nchans rows of
+// dedisp_pitch_bytes, 16-byte aligned.  The caller has checked the shape
+// (rt_dedisperse_device).
+hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
+                             const int32_t* d_delays, const uint8_t* d_mask, uint32_t ndm, uint32_t max_delay,
+                             float* out, uint64_t out_stride, void* ws, hipStream_t s);
+
 // harmonic_kernels.hip
 // One tile of the harmonic pair matrix: rows [i0, i0 + rows) of the n ranked
 // clusters, wpr = ceil(n / 64) 64-bit words per row, bit j of row i =

@@ -1,0 +1,203 @@
+"""Incoherent dedispersion of channelised data on the GPU: the stage in front
+of the periodicity search, so a filterbank file is read once and every DM
+trial is produced in device memory (rt_dedisperse_* in include/riptide_amd.h,
+kernels in csrc/dedisp_kernels.hip).
+
+  out[d, t] = sum over unmasked channels c of x[t + delay[d, c], c]
+
+with the delay of channel c against the highest frequency of the band
+
+  delay[d, c] = floor(kdm * dm[d] * (f_c ** -2 - f_ref ** -2) / tsamp + 0.5)
+
+8-bit data gives exact integer sums; float32 data is summed in float32.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+
+_L = _lib.load()
+_check = _lib.check
+
+# Dispersion constant in s MHz^2 cm^3 / pc: the rounded value 1 / 2.41e-4 that
+# PRESTO, SIGPROC and pulsar timing software share (not the more precise
+# 4.148808e3, which would put DMs on a slightly different scale than theirs).
+KDM = 1.0 / 2.41e-4
+
+# dedisperse_filterbank refuses a call whose output plus gulp buffers exceeds this
+DEFAULT_BUDGET_BYTES = 32 << 30
+# default bytes of one gulp of input
+DEFAULT_GULP_BYTES = 256 << 20
+
+_DTYPE_CODES = {np.dtype(np.uint8): 0, np.dtype(np.int8): 1, np.dtype(np.float32): 2}
+MAX_CHANS_8BIT = 65793    # RT_DEDISP_MAX_CHANS_8BIT: 255 * nchans < 2^24
+
+
+def dispersion_delays(freqs, dms, tsamp, kdm=KDM):
+    """(delays int64 [ndm, nchans], max_delay) in samples of `tsamp` seconds
+    for channel frequencies `freqs` (MHz) and trial DMs `dms` (pc cm^-3),
+    against the highest frequency (rt_dedisperse_delays; host only).
+    ValueError for an empty input, a frequency that is not positive and finite,
+    a DM that is negative or not finite, tsamp <= 0, or a delay of 2^31
+    samples or more."""
+    freqs = np.ascontiguousarray(np.atleast_1d(freqs), dtype=np.float64)
+    dms = np.ascontiguousarray(np.atleast_1d(dms), dtype=np.float64)
+    if freqs.ndim != 1 or dms.ndim != 1:
+        raise ValueError("freqs and dms must be one-dimensional")
+    delays = np.zeros((dms.size, freqs.size), dtype=np.int64)
+    md = ctypes.c_int64(0)
+    _check(_L.rt_dedisperse_delays(_lib.ptr(freqs), freqs.size, _lib.ptr(dms), dms.size, float(tsamp), float(kdm),
+                                   _lib.ptr(delays), ctypes.byref(md)))
+    return delays, int(md.value)
+
+
+def _checked_mask(mask, nchans):
+    if mask is None:
+        return None
+    mask = np.ascontiguousarray(np.asarray(mask).astype(bool), dtype=np.uint8)
+    if mask.shape != (nchans,):
+        raise ValueError(f"mask must have one entry per channel ({nchans})")
+    return mask
+
+
+def _checked_data(data):
+    data = np.asarray(data)
+    if data.ndim != 2 or data.dtype not in _DTYPE_CODES:
+        raise ValueError("data must be a uint8, int8 or float32 array [nsamp, nchans]")
+    if data.dtype != np.float32 and data.shape[1] > MAX_CHANS_8BIT:
+        raise ValueError(f"8-bit data with {data.shape[1]} channels: sums are exact only up to {MAX_CHANS_8BIT} "
+                         "channels (255 * nchans must be below 2^24)")
+    return data
+
+
+def dedisperse_host(data, delays, max_delay, mask=None, nout=None):
+    """The specification on the host (rt_dedisperse_host, no device): float32
+    [ndm, nout] from data [nsamp, nchans] and a delay table; nout defaults to
+    nsamp - max_delay."""
+    data = np.ascontiguousarray(_checked_data(data))
+    nsamp, nchans = data.shape
+    delays = np.ascontiguousarray(delays, dtype=np.int64)
+    if delays.ndim != 2 or delays.shape[1] != nchans:
+        raise ValueError("delays must be [ndm, nchans]")
+    mask = _checked_mask(mask, nchans)
+    nout = nsamp - int(max_delay) if nout is None else int(nout)
+    if nout < 0:
+        raise ValueError(f"max_delay {max_delay} exceeds the {nsamp} samples of the input")
+    out = np.zeros((delays.shape[0], nout), dtype=np.float32)
+    _check(_L.rt_dedisperse_host(_lib.ptr(data), _DTYPE_CODES[data.dtype], nsamp, nchans, _lib.ptr(delays),
+                                 None if mask is None else _lib.ptr(mask), delays.shape[0], int(max_delay), nout,
+                                 _lib.ptr(out)))
+    return out
+
+
+def dedisperse(data, freqs, tsamp, dms, mask=None, kdm=KDM):
+    """Dedisperse host data [nsamp, nchans] (uint8, int8 or float32) at the
+    trial DMs on the GPU: float32 [ndm, nsamp - max_delay] (rt_dedisperse:
+    upload, kernels, download).  mask: per channel, True = skipped; a masked
+    channel still counts towards the reference frequency and max_delay."""
+    data = np.ascontiguousarray(_checked_data(data))
+    nsamp, nchans = data.shape
+    delays, max_delay = dispersion_delays(freqs, dms, tsamp, kdm)
+    if delays.shape[1] != nchans:
+        raise ValueError("freqs must have one entry per channel of data")
+    mask = _checked_mask(mask, nchans)
+    if max_delay >= nsamp:
+        raise ValueError(f"the largest delay ({max_delay} samples) is not below the {nsamp} samples of the data")
+    out = np.empty((delays.shape[0], nsamp - max_delay), dtype=np.float32)
+    _check(_L.rt_dedisperse(_lib.ptr(data), _DTYPE_CODES[data.dtype], nsamp, nchans, _lib.ptr(delays),
+                            None if mask is None else _lib.ptr(mask), delays.shape[0], max_delay, _lib.ptr(out)))
+    return out
+
+
+def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, nout=None,
+                          budget_bytes=DEFAULT_BUDGET_BYTES):
+    """Dedisperse a reading.Filterbank at the trial DMs into one device tensor
+    float32 [ndm, nout], nout = nsamp - max_delay (or a smaller `nout`: the
+    first nout samples, e.g. the length a larger DM list would leave).
+
+    The memory map is streamed in gulps of `gulp` time samples (default: about
+    256 MiB of input, at least 2 * max_delay + 1) that overlap by max_delay,
+    through two page-locked staging buffers: the upload of gulp k + 1 runs on a
+    copy stream behind the kernels of gulp k.  The result does not depend on
+    gulp.  Queued on the current stream of `device`; the call returns once the
+    last gulp is queued.
+
+    ValueError -- nothing is launched -- when max_delay >= nsamp, for 8-bit
+    data of more than 65793 channels, and when the output (ndm * nout * 4
+    bytes) plus the gulp buffers exceed budget_bytes: pass fewer DMs per call."""
+    import torch
+    from . import engine
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else
+                       (device.index if isinstance(device, torch.device) else int(device)))
+    nsamp, nchans = fb.nsamp, fb.nchans
+    dtype = np.dtype(fb.dtype)
+    if dtype not in _DTYPE_CODES:
+        raise ValueError("the filterbank's samples must be uint8, int8 or float32")
+    if dtype != np.float32 and nchans > MAX_CHANS_8BIT:
+        raise ValueError(f"8-bit data with {nchans} channels: sums are exact only up to {MAX_CHANS_8BIT} channels "
+                         "(255 * nchans must be below 2^24)")
+    delays, max_delay = dispersion_delays(fb.freqs, dms, fb.tsamp, kdm)
+    mask = _checked_mask(mask, nchans)
+    if max_delay >= nsamp:
+        raise ValueError(f"the largest delay ({max_delay} samples) is not below the {nsamp} samples of the file")
+    full = nsamp - max_delay
+    nout = full if nout is None else int(nout)
+    if not 0 < nout <= full:
+        raise ValueError(f"nout must be in [1, {full}]")
+    ndm = delays.shape[0]
+    row_bytes = nchans * dtype.itemsize
+    if gulp is None:
+        gulp = max(DEFAULT_GULP_BYTES // row_bytes, 2 * max_delay + 1)
+    gulp = int(gulp)
+    if gulp <= max_delay:
+        raise ValueError(f"gulp must exceed the largest delay ({max_delay} samples)")
+    need_in = nout + max_delay          # input rows the outputs read
+    gulp = min(gulp, need_in)
+    ws_bytes = engine.dedisperse_workspace_bytes(dtype.name, gulp, nchans)
+    total = ndm * nout * 4 + 2 * gulp * row_bytes + ws_bytes
+    if total > int(budget_bytes):
+        raise ValueError(f"dedispersing {ndm} DMs needs {total} bytes of device memory ({ndm * nout * 4} of output "
+                         f"plus the gulp buffers), over the budget of {int(budget_bytes)}: pass fewer DMs per call")
+    tdtype = {"uint8": torch.uint8, "int8": torch.int8, "float32": torch.float32}[dtype.name]
+    with torch.cuda.device(dev):
+        main = torch.cuda.current_stream(dev)
+        copy = torch.cuda.Stream(device=dev)
+        out = torch.empty((ndm, nout), dtype=torch.float32, device=dev)
+        d_delays = torch.from_numpy(delays.astype(np.int32)).to(dev)
+        d_mask = None if mask is None else torch.from_numpy(mask).to(dev)
+        workspace = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        pinned = [torch.empty((gulp, nchans), dtype=tdtype).pin_memory() for _ in range(2)]
+        blocks = [torch.empty((gulp, nchans), dtype=tdtype, device=dev) for _ in range(2)]
+        uploaded = [torch.cuda.Event() for _ in range(2)]   # slot's upload is done: its staging buffer is free
+        consumed = [torch.cuda.Event() for _ in range(2)]   # slot's kernels are done: its device block is free
+        # The device blocks come from the main stream's pool: the allocator may
+        # hand out memory that work already queued on main (an earlier call's
+        # last kernels, say) still reads.  The copy stream starts behind it.
+        copy.wait_stream(main)
+        start, k = 0, 0
+        while start < nout:
+            g = min(gulp, need_in - start)
+            slot = k & 1
+            if k >= 2:
+                uploaded[slot].synchronize()
+            np.copyto(pinned[slot][:g].numpy(), fb.data[start:start + g])
+            with torch.cuda.stream(copy):
+                if k >= 2:
+                    copy.wait_event(consumed[slot])
+                blocks[slot][:g].copy_(pinned[slot][:g], non_blocking=True)
+                uploaded[slot].record(copy)
+            main.wait_event(uploaded[slot])
+            engine.dedisperse_device(blocks[slot][:g], d_delays, max_delay, mask=d_mask, out=out, out_offset=start,
+                                     workspace=workspace, stream=main)
+            consumed[slot].record(main)
+            start += g - max_delay
+            k += 1
+        # Every upload is done before the staging buffers and the device blocks
+        # are released with this frame, so the copy stream no longer uses
+        # them; the kernels still queued read the blocks on main, the stream
+        # the blocks were allocated on, whose pool reuses them in stream order.
+        uploaded[(k - 1) & 1].synchronize()
+        if k > 1:
+            uploaded[k & 1].synchronize()
+    return out

@@ -214,6 +214,38 @@ class EngineSearcher:
         (8-bit data converted on the device), results in input order."""
         return self.submit_samples(samples, tsamps, metadatas)()
 
+    def search_filterbank(self, fb, dms, mask=None, nout=None, kdm=None):
+        """Dedisperse a reading.Filterbank at the trial DMs on the device
+        (dedispersion.dedisperse_filterbank) and search every series: one peak
+        list per DM, in the order given (the __call__ contract).  The series
+        never leave the device: they go to _enqueue / _detect in slices of
+        `batch` DMs, slice k + 1 queued before slice k's detection as in
+        submit_samples.  Each trial's metadata is the file's with `dm` set.
+        `nout` cuts every series to its first nout samples (the length a
+        longer DM list would leave: search_filterbank of this module); `kdm`
+        is the dispersion constant of the delay table (default:
+        dedispersion.KDM)."""
+        import torch
+        from .dedispersion import KDM, dedisperse_filterbank
+        kdm = KDM if kdm is None else float(kdm)
+        dms = [float(d) for d in dms]
+        if not dms:
+            return []
+        dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else
+                           (self.device.index if isinstance(self.device, torch.device) else int(self.device)))
+        with torch.cuda.device(dev):
+            series = dedisperse_filterbank(fb, dms, mask=mask, device=dev, nout=nout, kdm=kdm)
+            metas = [fb.metadata(dm) for dm in dms]
+            slices = [(b0, min(b0 + self.batch, len(dms))) for b0 in range(0, len(dms), self.batch)]
+            per, pending = [], None
+            for b0, b1 in slices:
+                pend = self._enqueue(series[b0:b1], fb.tsamp, metas[b0:b1])
+                if pending is not None:
+                    per.extend(self._detect(pending))
+                pending = pend
+            per.extend(self._detect(pending))
+        return per
+
     def __call__(self, trials):
         return self.search_samples([t.data for t in trials], [t.tsamp for t in trials],
                                    [t.metadata for t in trials])
@@ -278,4 +310,36 @@ def search_files(fnames, pool, group=None, chunksize=None):
     tagged = []
     for first, per_file in pool.search_chunks([fnames[i] for i in mine], chunksize=chunksize):
         tagged += [(mine[first + j], [tuple(p) for p in plist]) for j, plist in enumerate(per_file)]
+    return _gather_tagged(tagged, group, world)
+
+
+def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=None):
+    """Search a channelised SIGPROC file at the trial DMs without leaving the
+    device: each rank dedisperses its round-robin share of `dms`
+    (searcher.search_filterbank, an EngineSearcher) from the one file and
+    searches the series in device memory; one gather of the tagged peak
+    lists.  Returns the full peak list on every rank, in the order of `dms`
+    (then range order within a DM): the search_trials contract.  Every rank
+    cuts its series to the length the whole DM list leaves, nsamp minus the
+    list's largest delay, so the result does not depend on the sharding.
+    `kdm` is the dispersion constant of the delay table, on every rank
+    (default: dedispersion.KDM)."""
+    from .dedispersion import KDM, dispersion_delays
+    kdm = KDM if kdm is None else float(kdm)
+    from .reading import Filterbank
+    fb = fb_or_fname if isinstance(fb_or_fname, Filterbank) else Filterbank(fb_or_fname)
+    dms = [float(d) for d in dms]
+    rank, world = _rank_world(group)
+    tagged = []
+    if dms:
+        _, max_delay = dispersion_delays(fb.freqs, dms, fb.tsamp, kdm)
+        if max_delay >= fb.nsamp:
+            raise ValueError(f"the largest delay ({max_delay} samples) is not below the {fb.nsamp} samples of the "
+                             "file")
+        mine = shard(len(dms), rank, world)
+        local = searcher.search_filterbank(fb, [dms[i] for i in mine], mask=mask, nout=fb.nsamp - max_delay,
+                                          kdm=kdm)
+        if len(local) != len(mine):
+            raise RuntimeError("searcher must return one peak list per DM")
+        tagged = [(i, [tuple(p) for p in plist]) for i, plist in zip(mine, local)]
     return _gather_tagged(tagged, group, world)

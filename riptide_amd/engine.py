@@ -268,6 +268,71 @@ def fold_device(data, tsamp, specs, stream=None):
     return results
 
 
+# RT_DEDISP_* sample type codes (include/riptide_amd.h)
+DEDISP_DTYPES = {"uint8": 0, "int8": 1, "float32": 2}
+
+
+def dedisperse_workspace_bytes(dtype, nsamp_blk, nchans):
+    """Device workspace bytes of dedisperse_device for a block of this shape;
+    dtype is 'uint8', 'int8' or 'float32'."""
+    b = ctypes.c_size_t()
+    _check(_L.rt_dedisperse_workspace_bytes(DEDISP_DTYPES[str(dtype)], int(nsamp_blk), int(nchans),
+                                            ctypes.byref(b)))
+    return b.value
+
+
+def dedisperse_device(block, delays, max_delay, mask=None, out=None, out_offset=0, workspace=None, stream=None):
+    """Incoherent dedispersion of one resident block (rt_dedisperse_device):
+    block uint8 / int8 / float32 [nsamp_blk, nchans] (time-major, contiguous),
+    delays int32 [ndm, nchans] and mask (uint8 [nchans], non-zero = skipped, or
+    None) on the block's device.  Writes out[d, out_offset + t] = the sum over
+    unmasked channels of block[t + delays[d, c], c] for t in [0, nsamp_blk -
+    max_delay) and returns out (float32 [ndm, >= out_offset + nsamp_blk -
+    max_delay], rows with unit stride; allocated [ndm, nsamp_blk - max_delay]
+    when None).  Stream-ordered, no host synchronisation.  8-bit results are
+    exact; float32 results are summed in channel order."""
+    import torch
+    if block.dim() != 2 or block.device.type != "cuda" or not block.is_contiguous():
+        raise ValueError("block must be a contiguous [nsamp_blk, nchans] device tensor")
+    name = str(block.dtype).replace("torch.", "")
+    if name not in DEDISP_DTYPES:
+        raise ValueError("block must be uint8, int8 or float32")
+    nsamp_blk, nchans = block.shape
+    if (delays.dim() != 2 or delays.dtype != torch.int32 or delays.device != block.device
+            or not delays.is_contiguous() or delays.shape[1] != nchans):
+        raise ValueError("delays must be a contiguous int32 [ndm, nchans] tensor on the block's device")
+    ndm = delays.shape[0]
+    if mask is not None and (mask.dtype != torch.uint8 or mask.device != block.device or not mask.is_contiguous()
+                             or tuple(mask.shape) != (nchans,)):
+        raise ValueError("mask must be a contiguous uint8 [nchans] tensor on the block's device")
+    max_delay = int(max_delay)
+    nout = nsamp_blk - max_delay
+    s = stream if stream is not None else torch.cuda.current_stream(block.device)
+    with torch.cuda.device(block.device), torch.cuda.stream(s):
+        # validates the shape before anything is allocated
+        need = dedisperse_workspace_bytes(name, nsamp_blk, nchans)
+        if not 0 <= max_delay < nsamp_blk:
+            raise ValueError(f"max_delay {max_delay} must be in [0, {nsamp_blk}): the block is no longer than the "
+                             "largest delay")
+        if out is None:
+            out = torch.empty((ndm, nout), dtype=torch.float32, device=block.device)
+        elif (out.dim() != 2 or out.dtype != torch.float32 or out.device != block.device or out.shape[0] != ndm
+              or out.stride(1) != 1 or out.shape[1] < int(out_offset) + nout
+              or (ndm > 1 and out.stride(0) < out.shape[1])):
+            raise ValueError(f"out must be float32 [{ndm}, >= {int(out_offset) + nout}] rows with unit stride on "
+                             "the block's device")
+        if workspace is None:
+            workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=block.device)
+        elif (workspace.dtype != torch.uint8 or workspace.device != block.device or not workspace.is_contiguous()
+              or workspace.numel() < need):
+            raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on the block's device")
+        _check(_L.rt_dedisperse_device(_lib.ptr(block), DEDISP_DTYPES[name], nsamp_blk, nchans, _lib.ptr(delays),
+                                       None if mask is None else _lib.ptr(mask), ndm, max_delay, _lib.ptr(out),
+                                       out.stride(0) if ndm > 1 else out.shape[1], int(out_offset),
+                                       _lib.ptr(workspace), workspace.numel(), _stream_handle(s)))
+    return out
+
+
 def profile_enable(on=True):
     _check(_L.rt_profile_enable(int(bool(on))))
 

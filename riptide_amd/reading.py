@@ -161,9 +161,78 @@ def read_sigproc(fname, extra_keys=None):
     return data, meta, sh["tsamp"]
 
 
+class Filterbank:
+    """A channelised SIGPROC file (nchans >= 1, one IF), opened for
+    dedispersion: the samples are a read-only memory map, nothing is read
+    until a slice of it is taken.
+
+      header   the SigprocHeader
+      nsamp, nchans, tsamp
+      freqs    channel centre frequencies in MHz, fch1 + c * foff (foff of
+               either sign), float64 [nchans]
+      dtype    sample type: 8-bit data is unsigned unless the header key
+               `signed` says otherwise; 32-bit data is float
+      data     np.memmap [nsamp, nchans], time-major as stored
+
+    1-, 2-, 4- and 16-bit data is not supported."""
+
+    def __init__(self, fname, extra_keys=None):
+        sh = SigprocHeader(fname, extra_keys=extra_keys)
+        if sh.get("nifs", 1) != 1:
+            raise ValueError(f"File {sh.fname!r} has nifs = {sh['nifs']}; only single-IF filterbanks are supported")
+        nbits = sh["nbits"]
+        if nbits not in {8, 32}:
+            raise ValueError(f"Only 8-bit and 32-bit SIGPROC data are supported. File {sh.fname!r} contains "
+                             f"{nbits}-bit data")
+        self.header = sh
+        self.fname = sh.fname
+        self.nchans = int(sh["nchans"])
+        if self.nchans < 1:
+            raise ValueError(f"File {sh.fname!r} has nchans = {self.nchans}")
+        self.tsamp = float(sh["tsamp"])
+        self.nsamp = int(sh.nsamp)
+        if self.nsamp < 1:
+            raise ValueError(f"File {sh.fname!r} holds no samples")
+        if nbits == 32:
+            self.dtype = np.dtype(np.float32)
+        else:
+            self.dtype = np.dtype(np.int8 if sh.get("signed", False) else np.uint8)
+        self.freqs = float(sh["fch1"]) + np.arange(self.nchans, dtype=np.float64) * float(sh["foff"])
+        self.data = np.memmap(sh.fname, dtype=self.dtype, mode="r", offset=sh.bytesize,
+                              shape=(self.nsamp, self.nchans))
+
+    @property
+    def tobs(self):
+        return self.nsamp * self.tsamp
+
+    def metadata(self, dm=None):
+        """The file's header as the Metadata of a series dedispersed at `dm`
+        (the keys sigproc_metadata derives, without its single-channel check)."""
+        sh = self.header
+        attrs = dict(sh)
+        attrs["dm"] = dm
+        attrs["skycoord"] = sh.skycoord if "src_raj" in sh and "src_dej" in sh else None
+        attrs["source_name"] = attrs.get("source_name", None)
+        attrs["mjd"] = attrs.get("tstart", None)
+        attrs["fname"] = os.path.realpath(sh.fname)
+        attrs["tobs"] = self.tobs
+        return Metadata(attrs)
+
+
 def write_sigproc(fname, data, header):
-    """Write a SIGPROC time series file (used by tests and tools; the header
-    keys must be in SIGPROC_KEYS)."""
+    """Write a SIGPROC file (used by tests and tools; the header keys must be
+    in SIGPROC_KEYS): a time series from 1-D data, or a filterbank from data
+    [nsamp, nchans], written time-major as given (the header's nchans must
+    then equal the second dimension, and the array's item size its nbits)."""
+    data = np.asarray(data)
+    if data.ndim == 2:
+        if int(header.get("nchans", -1)) != data.shape[1]:
+            raise ValueError("write_sigproc: header nchans must equal the channels of 2-D data")
+        if int(header.get("nbits", -1)) != 8 * data.dtype.itemsize:
+            raise ValueError("write_sigproc: header nbits must equal the bits of a 2-D array's samples")
+    elif data.ndim > 2:
+        raise ValueError("write_sigproc: data must be 1-D or [nsamp, nchans]")
+
     def wstr(f, s):
         b = s.encode()
         f.write(struct.pack("i", len(b)))
