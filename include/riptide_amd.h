@@ -441,6 +441,63 @@ int rt_dedisperse_device(const void* d_block, int dtype, size_t nsamp_blk, size_
 int rt_dedisperse(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays, const uint8_t* mask,
                   size_t ndm, int64_t max_delay, float* out);
 
+/* ---- RFI mitigation in front of the sum: zero-DM filter, channel statistics */
+/* Flag of the _opt forms below: the zero-DM filter (Eatough, Keane & Lyne
+ * 2009), every time sample minus its mean over the unmasked channels U, Nu =
+ * |U|, before the sum.  One definition for host and device:
+ *   S[t]      = sum over c in U of x[t, c]     8-bit: an exact integer;
+ *               float32: accumulated in float64 (the host in ascending channel
+ *               order, the device in its own fixed order)
+ *   m[t]      = (float32)(S[t] / Nu)           divided in float64, rounded once
+ *   y[t, c]   = (float32)x[t, c] - m[t]        one float32 subtraction; int8
+ *                                              samples enter as signed values
+ *   out[d, t] = sum over c in U of y[t + delay[d, c], c]
+ *               float32 additions in channel order
+ * Nu == 0 gives m = 0 and out = 0.  For 8-bit data m and y are reproducible
+ * bit for bit; only the last sum carries a rounding bound. */
+#define RT_DEDISP_ZERO_DM 1u
+/* The four entry points above with a flags argument (0 or RT_DEDISP_ZERO_DM;
+ * any other bit is RT_EINVAL).  flags == 0 is the plain call, bit for bit.
+ * With RT_DEDISP_ZERO_DM every sample type takes the float32 path: the
+ * workspace is nchans float32 rows of the padded pitch plus nsamp_blk floats
+ * for m (16-byte aligned), and 8-bit data is still refused above
+ * RT_DEDISP_MAX_CHANS_8BIT channels. */
+int rt_dedisperse_host_opt(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
+                           const uint8_t* mask, size_t ndm, int64_t max_delay, size_t nout, float* out,
+                           uint32_t flags);
+int rt_dedisperse_workspace_bytes_opt(int dtype, size_t nsamp_blk, size_t nchans, uint32_t flags, size_t* bytes);
+int rt_dedisperse_device_opt(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans,
+                             const int32_t* d_delays, const uint8_t* d_mask, size_t ndm, int64_t max_delay,
+                             float* d_out, size_t out_stride, size_t out_offset, void* d_workspace,
+                             size_t workspace_bytes, void* stream, uint32_t flags);
+int rt_dedisperse_opt(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
+                      const uint8_t* mask, size_t ndm, int64_t max_delay, float* out, uint32_t flags);
+/* Host only, no device: the zero-DM mean series m [nsamp] of x [nsamp, nchans]
+ * as defined above (mask NULL or [nchans], non-zero = channel skipped).
+ * RT_EINVAL for an unknown type code, nchans == 0, or 8-bit data of more than
+ * RT_DEDISP_MAX_CHANS_8BIT channels. */
+int rt_zero_dm_mean_host(const void* x, int dtype, size_t nsamp, size_t nchans, const uint8_t* mask, float* m);
+/* The same series of one resident block, d_m float32 [nsamp_blk]: the
+ * row-mean kernel alone.  Stream-ordered; no load leaves the block. */
+int rt_zero_dm_mean_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans, const uint8_t* d_mask,
+                           float* d_m, void* stream);
+/* Host only, no device: ADDS the per-channel sums of x [nsamp, nchans] into
+ * acc, float64 [2, nchans]: acc[0][c] += sum over t of x[t, c], acc[1][c] +=
+ * sum over t of x[t, c]^2 (int8 samples as signed values), in time order.
+ * A file is streamed block by block into zeroed accumulators; 8-bit sums are
+ * integers, exact below 2^53. */
+int rt_channel_stats_host(const void* x, int dtype, size_t nsamp, size_t nchans, double* acc);
+/* Device workspace bytes of rt_channel_stats_device: the per-chunk partial
+ * sums. */
+int rt_channel_stats_workspace_bytes(size_t nsamp_blk, size_t nchans, size_t* bytes);
+/* The same addition for one resident block into d_acc, float64 [2, nchans] in
+ * device memory: per-chunk partial sums to the workspace, folded into d_acc
+ * in chunk order by a second kernel.  No floating-point atomics: the same
+ * input gives the same bits.  Stream-ordered.  d_acc and d_workspace must be
+ * 8-byte aligned. */
+int rt_channel_stats_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans, double* d_acc,
+                            void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* --------------------------- file input (device) --------------------------- */
 /* 8-bit SIGPROC samples (riptide/time_series.py:352-357) to float32 in device
  * memory: d_raw holds n bytes, int8 when is_signed else uint8; exact as

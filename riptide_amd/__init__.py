@@ -23,10 +23,12 @@ from .candidate import Candidate, build_candidates
 from .harmonic_testing import apply_candidate_filters, flag_harmonics, hdiag, htest
 from .reading import Filterbank
 from .dispatch import search_filterbank
+from . import dedispersion, rfi
 
 __all__ = [
     "Candidate", "PeakCluster", "build_candidates", "flag_harmonics", "apply_candidate_filters", "htest", "hdiag",
     "TimeSeries", "Periodogram", "Metadata", "ffa_search", "ffa1", "ffa2", "ffafreq", "ffaprd",
     "generate_signal", "downsample", "boxcar_snr", "find_peaks", "running_median",
     "fast_running_median", "generate_width_trials", "cluster1d", "Peak", "Filterbank", "search_filterbank",
+    "dedispersion", "rfi",
 ]

@@ -102,6 +102,22 @@ _SIGNATURES = {
                                     _vp, _c_sz, _vp]),
     # x, dtype, nsamp, nchans, delays (int64), mask, ndm, max_delay, out
     "rt_dedisperse": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _c_sz, ctypes.c_int64, _vp]),
+    # the four above with a trailing flags argument (before `bytes` in the workspace query)
+    "rt_dedisperse_host_opt": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _c_sz, ctypes.c_int64, _c_sz, _vp,
+                                      ctypes.c_uint32]),
+    "rt_dedisperse_workspace_bytes_opt": (_c_i, [_c_i, _c_sz, _c_sz, ctypes.c_uint32, _psz]),
+    "rt_dedisperse_device_opt": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _c_sz, ctypes.c_int64, _vp, _c_sz, _c_sz,
+                                        _vp, _c_sz, _vp, ctypes.c_uint32]),
+    "rt_dedisperse_opt": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _c_sz, ctypes.c_int64, _vp, ctypes.c_uint32]),
+    # x, dtype, nsamp, nchans, mask, m
+    "rt_zero_dm_mean_host": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp]),
+    # block, dtype, nsamp_blk, nchans, mask, m, stream
+    "rt_zero_dm_mean_device": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _vp]),
+    # x, dtype, nsamp, nchans, acc (float64 [2, nchans])
+    "rt_channel_stats_host": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp]),
+    "rt_channel_stats_workspace_bytes": (_c_i, [_c_sz, _c_sz, _psz]),
+    # block, dtype, nsamp_blk, nchans, acc, workspace, workspace bytes, stream
+    "rt_channel_stats_device": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _c_sz, _vp]),
 }
 
 EXPORTED = tuple(_SIGNATURES)

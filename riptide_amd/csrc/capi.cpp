@@ -1414,12 +1414,23 @@ int rt_fold(const float* x, size_t size, size_t nseries, const rt_fold_spec* spe
     });
 }
 
+static void dedisp_check_flags(uint32_t flags)
+{
+    if (flags & ~RT_DEDISP_ZERO_DM) throw std::invalid_argument("dedisperse: unknown flag bit");
+}
+
 int rt_dedisperse_workspace_bytes(int dtype, size_t nsamp_blk, size_t nchans, size_t* bytes)
+{
+    return rt_dedisperse_workspace_bytes_opt(dtype, nsamp_blk, nchans, 0u, bytes);
+}
+
+int rt_dedisperse_workspace_bytes_opt(int dtype, size_t nsamp_blk, size_t nchans, uint32_t flags, size_t* bytes)
 {
     return guarded([&] {
         if (!bytes) throw std::invalid_argument("dedisperse: bytes is NULL");
+        dedisp_check_flags(flags);
         dedisp_check_shape(dtype, nsamp_blk, nchans, 1, 0);
-        *bytes = (size_t)dedisp_pitch_bytes(dtype, nsamp_blk) * nchans;
+        *bytes = (size_t)dedisp_workspace_bytes(dtype, nsamp_blk, nchans, flags);
         return RT_OK;
     });
 }
@@ -1428,7 +1439,17 @@ int rt_dedisperse_device(const void* d_block, int dtype, size_t nsamp_blk, size_
                          const uint8_t* d_mask, size_t ndm, int64_t max_delay, float* d_out, size_t out_stride,
                          size_t out_offset, void* d_ws, size_t ws_bytes, void* stream)
 {
+    return rt_dedisperse_device_opt(d_block, dtype, nsamp_blk, nchans, d_delays, d_mask, ndm, max_delay, d_out,
+                                    out_stride, out_offset, d_ws, ws_bytes, stream, 0u);
+}
+
+int rt_dedisperse_device_opt(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans,
+                             const int32_t* d_delays, const uint8_t* d_mask, size_t ndm, int64_t max_delay,
+                             float* d_out, size_t out_stride, size_t out_offset, void* d_ws, size_t ws_bytes,
+                             void* stream, uint32_t flags)
+{
     return guarded([&] {
+        dedisp_check_flags(flags);
         dedisp_check_shape(dtype, nsamp_blk, nchans, ndm, max_delay);
         const size_t nout = nsamp_blk - (size_t)max_delay;
         if (out_offset > out_stride || nout > out_stride - out_offset)
@@ -1436,10 +1457,10 @@ int rt_dedisperse_device(const void* d_block, int dtype, size_t nsamp_blk, size_
         if (!d_block || !d_delays || !d_out || !d_ws) throw std::invalid_argument("dedisperse: null device pointer");
         if ((uintptr_t)d_ws % 16 || (dtype == RT_DEDISP_F32 && (uintptr_t)d_block % 4))
             throw std::invalid_argument("dedisperse: misaligned device pointer");
-        if (ws_bytes < dedisp_pitch_bytes(dtype, nsamp_blk) * nchans)
+        if (ws_bytes < dedisp_workspace_bytes(dtype, nsamp_blk, nchans, flags))
             throw std::invalid_argument("workspace too small");
         ck(launch_dedisperse(d_block, dtype, (uint32_t)nsamp_blk, (uint32_t)nchans, d_delays, d_mask, (uint32_t)ndm,
-                             (uint32_t)max_delay, d_out + out_offset, out_stride, d_ws, (hipStream_t)stream),
+                             (uint32_t)max_delay, d_out + out_offset, out_stride, d_ws, flags, (hipStream_t)stream),
            "dedisperse");
         return RT_OK;
     });
@@ -1448,7 +1469,14 @@ int rt_dedisperse_device(const void* d_block, int dtype, size_t nsamp_blk, size_
 int rt_dedisperse(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays, const uint8_t* mask,
                   size_t ndm, int64_t max_delay, float* out)
 {
+    return rt_dedisperse_opt(x, dtype, nsamp, nchans, delays, mask, ndm, max_delay, out, 0u);
+}
+
+int rt_dedisperse_opt(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
+                      const uint8_t* mask, size_t ndm, int64_t max_delay, float* out, uint32_t flags)
+{
     return guarded([&] {
+        dedisp_check_flags(flags);
         dedisp_check_shape(dtype, nsamp, nchans, ndm, max_delay);
         if (!x || !delays || !out) throw std::invalid_argument("dedisperse: null buffer");
         std::vector<int32_t> del(ndm * nchans);
@@ -1459,7 +1487,7 @@ int rt_dedisperse(const void* x, int dtype, size_t nsamp, size_t nchans, const i
         }
         const size_t nout = nsamp - (size_t)max_delay;
         const size_t in_bytes = nsamp * nchans * (dtype == RT_DEDISP_F32 ? 4 : 1);
-        const size_t ws_bytes = (size_t)dedisp_pitch_bytes(dtype, nsamp) * nchans;
+        const size_t ws_bytes = (size_t)dedisp_workspace_bytes(dtype, nsamp, nchans, flags);
         std::lock_guard<std::mutex> lk(g_mu);
         Context& c = context();
         void* dx = c.buf[0].get(in_bytes);
@@ -1471,10 +1499,60 @@ int rt_dedisperse(const void* x, int dtype, size_t nsamp, size_t nchans, const i
         h2d(dd, del.data(), del.size() * 4, c.stream);
         if (mask) h2d(dm, mask, nchans, c.stream);
         ck(launch_dedisperse(dx, dtype, (uint32_t)nsamp, (uint32_t)nchans, dd, dm, (uint32_t)ndm,
-                             (uint32_t)max_delay, dz, nout, dw, c.stream),
+                             (uint32_t)max_delay, dz, nout, dw, flags, c.stream),
            "dedisperse");
         d2h(out, dz, ndm * nout * 4, c.stream);
         sync(c.stream);
+        return RT_OK;
+    });
+}
+
+int rt_zero_dm_mean_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans, const uint8_t* d_mask,
+                           float* d_m, void* stream)
+{
+    return guarded([&] {
+        dedisp_check_shape(dtype, nsamp_blk, nchans, 1, 0);
+        if (!d_block || !d_m) throw std::invalid_argument("zero_dm_mean: null device pointer");
+        if ((uintptr_t)d_m % 4 || (dtype == RT_DEDISP_F32 && (uintptr_t)d_block % 4))
+            throw std::invalid_argument("zero_dm_mean: misaligned device pointer");
+        ck(launch_zero_dm_mean(d_block, dtype, (uint32_t)nsamp_blk, (uint32_t)nchans, d_mask, d_m,
+                               (hipStream_t)stream),
+           "zero_dm_mean");
+        return RT_OK;
+    });
+}
+
+// the statistics have no exactness limit on the channel count of 8-bit data
+static void chanstats_check_shape(int dtype, size_t nsamp_blk, size_t nchans)
+{
+    dedisp_check_shape(RT_DEDISP_F32, nsamp_blk, nchans, 1, 0);
+    if (dtype != RT_DEDISP_U8 && dtype != RT_DEDISP_I8 && dtype != RT_DEDISP_F32)
+        throw std::invalid_argument("channel_stats: unknown sample type code");
+}
+
+int rt_channel_stats_workspace_bytes(size_t nsamp_blk, size_t nchans, size_t* bytes)
+{
+    return guarded([&] {
+        if (!bytes) throw std::invalid_argument("channel_stats: bytes is NULL");
+        chanstats_check_shape(RT_DEDISP_F32, nsamp_blk, nchans);
+        *bytes = (size_t)chanstats_workspace_bytes(nsamp_blk, nchans);
+        return RT_OK;
+    });
+}
+
+int rt_channel_stats_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans, double* d_acc,
+                            void* d_ws, size_t ws_bytes, void* stream)
+{
+    return guarded([&] {
+        chanstats_check_shape(dtype, nsamp_blk, nchans);
+        if (!d_block || !d_acc || !d_ws) throw std::invalid_argument("channel_stats: null device pointer");
+        if ((uintptr_t)d_acc % 8 || (uintptr_t)d_ws % 8 || (dtype == RT_DEDISP_F32 && (uintptr_t)d_block % 4))
+            throw std::invalid_argument("channel_stats: misaligned device pointer");
+        if (ws_bytes < chanstats_workspace_bytes(nsamp_blk, nchans))
+            throw std::invalid_argument("workspace too small");
+        ck(launch_channel_stats(d_block, dtype, (uint32_t)nsamp_blk, (uint32_t)nchans, d_acc, d_ws,
+                                (hipStream_t)stream),
+           "channel_stats");
         return RT_OK;
     });
 }

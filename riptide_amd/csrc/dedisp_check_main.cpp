@@ -1,5 +1,7 @@
 // Host-only checker of the dedispersion delay table and specification
-// (rt_dedisperse_delays, rt_dedisperse_host: dedisp_host.cpp), built with
+// (rt_dedisperse_delays, rt_dedisperse_host, and the zero-DM and channel
+// statistics forms rt_dedisperse_host_opt, rt_zero_dm_mean_host,
+// rt_channel_stats_host: dedisp_host.cpp), built with
 // AddressSanitizer + UBSan by `make -C riptide_amd/csrc asan`.  Every array is
 // a heap block of exactly the size the entry point may touch, so a read past
 // the last sample, a delay row or the mask is a sanitizer report.  No device
@@ -7,8 +9,9 @@
 //   dedisp_check
 // Runs the edge shapes (1, 3, 37, 64, 65 channels, both band orders, DM 0,
 // nout = nsamp - max_delay and nout = 1, with and without a mask, the three
-// sample types) against a recount, then every error return.  Exit status 0
-// iff all agree.
+// sample types) against a recount, the same shapes with RT_DEDISP_ZERO_DM
+// and through the statistics, then every error return.  Exit status 0 iff all
+// agree.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -105,6 +108,147 @@ void run_shape(size_t nchans, bool ascending, int dtype, bool masked, bool singl
         }
 }
 
+// The same shape through rt_zero_dm_mean_host, rt_dedisperse_host_opt with
+// RT_DEDISP_ZERO_DM and rt_channel_stats_host (in two halves), every array of
+// exact size.
+void run_rfi_shape(size_t nchans, int dtype, bool masked, bool single_out)
+{
+    const double tsamp = 1e-3, kdm = 1.0 / 2.41e-4;
+    const size_t ndm = 5;
+    std::vector<double> freqs(nchans), dms{0.0, 50.0, 12.5, 50.0, 3.0};
+    for (size_t c = 0; c < nchans; ++c) freqs[c] = 400.0 - 32.0 / (double)nchans * (double)c;
+    std::vector<int64_t> delays(ndm * nchans);
+    int64_t max_delay = -1;
+    expect(rt_dedisperse_delays(freqs.data(), nchans, dms.data(), ndm, tsamp, kdm, delays.data(), &max_delay) == RT_OK,
+           "delays");
+    const size_t nsamp = (size_t)max_delay + 300;
+    const size_t nout = single_out ? 1 : nsamp - (size_t)max_delay;
+    const size_t esize = dtype == RT_DEDISP_F32 ? 4 : 1;
+    std::vector<unsigned char> x(nsamp * nchans * esize);
+    for (size_t i = 0; i < nsamp * nchans; ++i) {
+        if (dtype == RT_DEDISP_F32) {
+            const float v = (float)((double)draw() / 4294967296.0 - 0.5);
+            std::memcpy(x.data() + 4 * i, &v, 4);
+        } else {
+            x[i] = (unsigned char)draw();
+        }
+    }
+    auto value = [&](size_t i) {
+        return dtype == RT_DEDISP_U8 ? sample<uint8_t>(x, i) : dtype == RT_DEDISP_I8 ? sample<int8_t>(x, i)
+                                                                                      : sample<float>(x, i);
+    };
+    std::vector<uint8_t> mask;
+    if (masked) {
+        mask.assign(nchans, 0);
+        mask[0] = 1;
+        mask[nchans - 1] = 1;
+    }
+    const uint8_t* mk = masked ? mask.data() : nullptr;
+    size_t nu = 0;
+    for (size_t c = 0; c < nchans; ++c) nu += !masked || !mask[c];
+
+    std::vector<float> m(nsamp);
+    expect(rt_zero_dm_mean_host(x.data(), dtype, nsamp, nchans, mk, m.data()) == RT_OK, "zero_dm_mean_host");
+    for (size_t t = 0; t < nsamp; ++t) {
+        double s = 0.0;
+        for (size_t c = 0; c < nchans; ++c)
+            if (!masked || !mask[c]) s += value(t * nchans + c);
+        const float want = nu ? (float)(s / (double)nu) : 0.0f;
+        // 8-bit: s is an exact integer, so the mean is the same bits
+        const double tol = dtype == RT_DEDISP_F32 ? std::ldexp(std::fabs((double)want), -23) : 0.0;
+        if (std::fabs((double)m[t] - (double)want) > tol) {
+            std::printf("FAILED: zero-DM mean nchans %zu dtype %d t %zu: %g vs %g\n", nchans, dtype, t, (double)m[t],
+                        (double)want);
+            ++fails;
+            return;
+        }
+    }
+
+    std::vector<float> out(ndm * nout);
+    expect(rt_dedisperse_host_opt(x.data(), dtype, nsamp, nchans, delays.data(), mk, ndm, max_delay, nout, out.data(),
+                                  RT_DEDISP_ZERO_DM) == RT_OK,
+           "dedisperse_host_opt");
+    for (size_t d = 0; d < ndm; ++d)
+        for (size_t t = 0; t < nout; ++t) {
+            double ref = 0.0, mag = 0.0;
+            for (size_t c = 0; c < nchans; ++c) {
+                if (masked && mask[c]) continue;
+                const size_t tt = t + (size_t)delays[d * nchans + c];
+                const double y = value(tt * nchans + c) - (double)m[tt];
+                ref += y;
+                mag += std::fabs(y);
+            }
+            const double tol = (double)(nchans + 2) * std::ldexp(1.0, -24) * mag;
+            if (std::fabs((double)out[d * nout + t] - ref) > tol) {
+                std::printf("FAILED: zero-DM nchans %zu dtype %d dm %zu t %zu: %g vs %g\n", nchans, dtype, d, t,
+                            (double)out[d * nout + t], ref);
+                ++fails;
+                return;
+            }
+        }
+
+    // the plain call through the flag-taking form
+    std::vector<float> plain(ndm * nout), plain_opt(ndm * nout);
+    expect(rt_dedisperse_host(x.data(), dtype, nsamp, nchans, delays.data(), mk, ndm, max_delay, nout,
+                              plain.data()) == RT_OK, "dedisperse_host");
+    expect(rt_dedisperse_host_opt(x.data(), dtype, nsamp, nchans, delays.data(), mk, ndm, max_delay, nout,
+                                  plain_opt.data(), 0u) == RT_OK, "dedisperse_host_opt, flags 0");
+    expect(std::memcmp(plain.data(), plain_opt.data(), plain.size() * sizeof(float)) == 0,
+           "flags 0 equals the plain call");
+
+    // the statistics: two halves, each an exact-size copy, into one accumulator
+    std::vector<double> acc(2 * nchans, 0.0);
+    const size_t half = nsamp / 3;
+    std::vector<unsigned char> a(x.begin(), x.begin() + (std::ptrdiff_t)(half * nchans * esize));
+    std::vector<unsigned char> b(x.begin() + (std::ptrdiff_t)(half * nchans * esize), x.end());
+    expect(rt_channel_stats_host(a.data(), dtype, half, nchans, acc.data()) == RT_OK, "channel_stats_host (a)");
+    expect(rt_channel_stats_host(b.data(), dtype, nsamp - half, nchans, acc.data()) == RT_OK,
+           "channel_stats_host (b)");
+    for (size_t c = 0; c < nchans; ++c) {
+        double s = 0.0, q = 0.0, sa = 0.0;
+        for (size_t t = 0; t < nsamp; ++t) {
+            const double v = value(t * nchans + c);
+            s += v;
+            q += v * v;
+            sa += std::fabs(v);
+        }
+        const double u = dtype == RT_DEDISP_F32 ? 2.0 * (double)nsamp * std::ldexp(1.0, -53) : 0.0;
+        if (std::fabs(acc[c] - s) > u * sa || std::fabs(acc[nchans + c] - q) > u * q) {
+            std::printf("FAILED: channel stats nchans %zu dtype %d channel %zu\n", nchans, dtype, c);
+            ++fails;
+            return;
+        }
+    }
+}
+
+void run_rfi_errors()
+{
+    std::vector<uint8_t> x(10 * 2, 1);
+    std::vector<float> out(7), m(10);
+    std::vector<int64_t> d2{0, 3};
+    std::vector<double> acc(4, 0.0);
+    expect(rt_dedisperse_host_opt(x.data(), RT_DEDISP_U8, 10, 2, d2.data(), nullptr, 1, 3, 7, out.data(), 2u) ==
+               RT_EINVAL, "unknown flag bit");
+    expect(rt_dedisperse_host_opt(x.data(), RT_DEDISP_U8, 10, 2, d2.data(), nullptr, 1, 3, 8, out.data(),
+                                  RT_DEDISP_ZERO_DM) == RT_EINVAL, "nout + max_delay > nsamp (zero-DM)");
+    expect(rt_dedisperse_host_opt(x.data(), RT_DEDISP_U8, 10, 2, d2.data(), nullptr, 1, 3, 7, out.data(),
+                                  RT_DEDISP_ZERO_DM) == RT_OK, "zero-DM of a constant block");
+    for (float v : out) expect(v == 0.0f, "a constant block is all mean");
+    std::vector<uint8_t> every{1, 1};
+    expect(rt_dedisperse_host_opt(x.data(), RT_DEDISP_U8, 10, 2, d2.data(), every.data(), 1, 3, 7, out.data(),
+                                  RT_DEDISP_ZERO_DM) == RT_OK, "every channel masked");
+    for (float v : out) expect(v == 0.0f, "no unmasked channel: zero");
+    expect(rt_zero_dm_mean_host(x.data(), RT_DEDISP_U8, 10, 2, every.data(), m.data()) == RT_OK, "mean, all masked");
+    for (float v : m) expect(v == 0.0f, "no unmasked channel: m = 0");
+    expect(rt_zero_dm_mean_host(x.data(), 7, 10, 2, nullptr, m.data()) == RT_EINVAL, "mean: unknown type code");
+    expect(rt_zero_dm_mean_host(x.data(), RT_DEDISP_U8, 10, 0, nullptr, m.data()) == RT_EINVAL, "mean: nchans == 0");
+    expect(rt_channel_stats_host(x.data(), 7, 10, 2, acc.data()) == RT_EINVAL, "stats: unknown type code");
+    expect(rt_channel_stats_host(x.data(), RT_DEDISP_U8, 10, 0, acc.data()) == RT_EINVAL, "stats: nchans == 0");
+    expect(rt_channel_stats_host(x.data(), RT_DEDISP_U8, 10, 2, nullptr) == RT_EINVAL, "stats: acc is NULL");
+    expect(rt_channel_stats_host(x.data(), RT_DEDISP_U8, 10, 2, acc.data()) == RT_OK, "stats");
+    expect(acc[0] == 10.0 && acc[1] == 10.0 && acc[2] == 10.0 && acc[3] == 10.0, "stats of a block of ones");
+}
+
 void run_errors()
 {
     std::vector<double> f{400.0, 390.0}, dm{1.0};
@@ -168,7 +312,15 @@ int main()
                         if (masked && nchans < 3) continue;
                         run_shape(nchans, asc != 0, dtype, masked != 0, single != 0);
                     }
+    for (size_t nchans : chans)
+        for (int dtype = 0; dtype < 3; ++dtype)
+            for (int masked = 0; masked < 2; ++masked)
+                for (int single = 0; single < 2; ++single) {
+                    if (masked && nchans < 3) continue;
+                    run_rfi_shape(nchans, dtype, masked != 0, single != 0);
+                }
     run_errors();
+    run_rfi_errors();
     if (fails)
         std::printf("dedisp_check: %d failures\n", fails);
     else

@@ -7,6 +7,8 @@
 #include <cmath>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
+#include <vector>
 
 #include "capi_common.hpp"
 
@@ -28,6 +30,64 @@ void dedisperse_rows(const T* x, size_t nchans, const int64_t* delays, const uin
             o[t] = (float)acc;
         }
     }
+}
+
+// The zero-DM mean series (riptide_amd.h, RT_DEDISP_ZERO_DM): Acc = int64_t
+// for 8-bit samples (an exact sum), double for float samples.
+template <class T, class Acc>
+void zero_dm_mean(const T* x, size_t nsamp, size_t nchans, const uint8_t* mask, float* m)
+{
+    size_t nu = 0;
+    for (size_t c = 0; c < nchans; ++c) nu += !mask || !mask[c];
+    for (size_t t = 0; t < nsamp; ++t) {
+        Acc s = 0;
+        const T* row = x + t * nchans;
+        for (size_t c = 0; c < nchans; ++c)
+            if (!mask || !mask[c]) s += (Acc)row[c];
+        m[t] = nu ? (float)((double)s / (double)nu) : 0.0f;
+    }
+}
+
+template <class T>
+void dedisperse_rows_zero_dm(const T* x, size_t nsamp, size_t nchans, const int64_t* delays, const uint8_t* mask,
+                             size_t ndm, size_t nout, float* out)
+{
+    std::vector<float> m(nsamp);
+    zero_dm_mean<T, typename std::conditional<sizeof(T) == 1, int64_t, double>::type>(x, nsamp, nchans, mask,
+                                                                                      m.data());
+    for (size_t d = 0; d < ndm; ++d) {
+        const int64_t* del = delays + d * nchans;
+        float* o = out + d * nout;
+        for (size_t t = 0; t < nout; ++t) {
+            float acc = 0.0f;
+            for (size_t c = 0; c < nchans; ++c) {
+                if (mask && mask[c]) continue;
+                const size_t tt = t + (size_t)del[c];
+                acc += (float)x[tt * nchans + c] - m[tt];
+            }
+            o[t] = acc;
+        }
+    }
+}
+
+template <class T>
+void channel_stats(const T* x, size_t nsamp, size_t nchans, double* acc)
+{
+    for (size_t t = 0; t < nsamp; ++t)
+        for (size_t c = 0; c < nchans; ++c) {
+            const double v = (double)x[t * nchans + c];
+            acc[c] += v;
+            acc[nchans + c] += v * v;
+        }
+}
+
+void check_dtype(int dtype, size_t nchans)
+{
+    if (dtype != RT_DEDISP_U8 && dtype != RT_DEDISP_I8 && dtype != RT_DEDISP_F32)
+        throw std::invalid_argument("dedisperse: unknown sample type code");
+    if (!nchans) throw std::invalid_argument("dedisperse: nchans and ndm must be at least 1");
+    if (dtype != RT_DEDISP_F32 && nchans > RT_DEDISP_MAX_CHANS_8BIT)
+        throw std::invalid_argument("dedisperse: too many channels for an exact 8-bit sum");
 }
 
 }  // namespace
@@ -71,7 +131,15 @@ int rt_dedisperse_delays(const double* freqs_mhz, size_t nchans, const double* d
 int rt_dedisperse_host(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
                        const uint8_t* mask, size_t ndm, int64_t max_delay, size_t nout, float* out)
 {
+    return rt_dedisperse_host_opt(x, dtype, nsamp, nchans, delays, mask, ndm, max_delay, nout, out, 0u);
+}
+
+int rt_dedisperse_host_opt(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
+                           const uint8_t* mask, size_t ndm, int64_t max_delay, size_t nout, float* out,
+                           uint32_t flags)
+{
     return guarded([&] {
+        if (flags & ~RT_DEDISP_ZERO_DM) throw std::invalid_argument("dedisperse: unknown flag bit");
         if (!nchans || !ndm) throw std::invalid_argument("dedisperse: nchans and ndm must be at least 1");
         if (dtype != RT_DEDISP_U8 && dtype != RT_DEDISP_I8 && dtype != RT_DEDISP_F32)
             throw std::invalid_argument("dedisperse: unknown sample type code");
@@ -86,12 +154,56 @@ int rt_dedisperse_host(const void* x, int dtype, size_t nsamp, size_t nchans, co
             if (delays[i] < 0 || delays[i] > max_delay)
                 throw std::invalid_argument("dedisperse: a delay is outside [0, max_delay]");
         if (!nout) return RT_OK;
+        if (flags & RT_DEDISP_ZERO_DM) {
+            if (dtype == RT_DEDISP_U8)
+                dedisperse_rows_zero_dm((const uint8_t*)x, nsamp, nchans, delays, mask, ndm, nout, out);
+            else if (dtype == RT_DEDISP_I8)
+                dedisperse_rows_zero_dm((const int8_t*)x, nsamp, nchans, delays, mask, ndm, nout, out);
+            else
+                dedisperse_rows_zero_dm((const float*)x, nsamp, nchans, delays, mask, ndm, nout, out);
+            return RT_OK;
+        }
         if (dtype == RT_DEDISP_U8)
             dedisperse_rows<uint8_t, int32_t>((const uint8_t*)x, nchans, delays, mask, ndm, nout, out);
         else if (dtype == RT_DEDISP_I8)
             dedisperse_rows<int8_t, int32_t>((const int8_t*)x, nchans, delays, mask, ndm, nout, out);
         else
             dedisperse_rows<float, float>((const float*)x, nchans, delays, mask, ndm, nout, out);
+        return RT_OK;
+    });
+}
+
+int rt_zero_dm_mean_host(const void* x, int dtype, size_t nsamp, size_t nchans, const uint8_t* mask, float* m)
+{
+    return guarded([&] {
+        check_dtype(dtype, nchans);
+        if (!nsamp) return RT_OK;
+        if (!x || !m) throw std::invalid_argument("zero_dm_mean: null buffer");
+        if (dtype == RT_DEDISP_U8)
+            zero_dm_mean<uint8_t, int64_t>((const uint8_t*)x, nsamp, nchans, mask, m);
+        else if (dtype == RT_DEDISP_I8)
+            zero_dm_mean<int8_t, int64_t>((const int8_t*)x, nsamp, nchans, mask, m);
+        else
+            zero_dm_mean<float, double>((const float*)x, nsamp, nchans, mask, m);
+        return RT_OK;
+    });
+}
+
+int rt_channel_stats_host(const void* x, int dtype, size_t nsamp, size_t nchans, double* acc)
+{
+    return guarded([&] {
+        if (dtype != RT_DEDISP_U8 && dtype != RT_DEDISP_I8 && dtype != RT_DEDISP_F32)
+            throw std::invalid_argument("channel_stats: unknown sample type code");
+        if (!nchans) throw std::invalid_argument("channel_stats: nchans must be at least 1");
+        if (!acc) throw std::invalid_argument("channel_stats: null buffer");
+        if (!nsamp) return RT_OK;
+        if (!x) throw std::invalid_argument("channel_stats: null buffer");
+        if (dtype == RT_DEDISP_U8)
+            channel_stats((const uint8_t*)x, nsamp, nchans, acc);
+        else if (dtype == RT_DEDISP_I8)
+            channel_stats((const int8_t*)x, nsamp, nchans, acc);
+        else
+            channel_stats((const float*)x, nsamp, nchans, acc);
         return RT_OK;
     });
 }

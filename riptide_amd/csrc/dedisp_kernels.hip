@@ -14,6 +14,15 @@
 //                             tile's DMs read is staged in LDS with aligned
 //                             dword loads, then every wave adds its four DMs
 //                             (one DM at a time, its delay wave-uniform)
+//   dedisp_rowmean_kernel     zero-DM filter (RT_DEDISP_ZERO_DM): m[t], the mean
+//                             of time sample t over the unmasked channels, one
+//                             wave per sample
+//   dedisp_transpose_zdm_kernel  the zero-DM form of both transposes: float32
+//                             x - m rows for every sample type, then summed by
+//                             dedisp_sum_kernel<float>
+//   dedisp_chanstats*_kernel  per-channel sum and sum of squares: partial sums
+//                             per chunk of time, folded in chunk order (no
+//                             atomics: the same bits every time)
 //
 // No load leaves its buffer: the transpose reads x only at t < nsamp, the
 // staging loads are clamped to the row's padded pitch inside the workspace,
@@ -93,6 +102,128 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_transpose32_kernel(
         const uint32_t co = c0 + i;
         if (co < nchans && t < pitch) ws[(uint64_t)co * pitch + t] = tile[i][tx];
     }
+}
+
+// ---- zero-DM filter (RT_DEDISP_ZERO_DM, riptide_amd.h) and channel statistics
+constexpr uint32_t kRmRows = 4;                          // time samples a wave takes, one after the other
+constexpr uint32_t kRmRowsPerWg = kDdWaves * kRmRows;    // time samples of a workgroup
+constexpr uint32_t kCsChunk = 2048;                      // time samples of one partial sum of the statistics
+
+// the sample as the value it stands for: int8 signed, no bias
+template <class T>
+__device__ inline float dd_value(T v)
+{
+    return (float)v;
+}
+
+// m[t] = (float32)(S[t] / Nu), S the sum of row t over the unmasked channels,
+// Nu their number.  One wave per time sample, the lanes striding the channels
+// (the fastest index: coalesced); int32 partial sums for 8-bit samples (at
+// most 65793 * 255), float64 for float samples; a 64-lane butterfly, so every
+// lane holds the same total, summed in an order that depends on nchans alone.
+template <class T>
+__global__ __launch_bounds__(kDdThreads) void dedisp_rowmean_kernel(
+    const T* __restrict__ x, uint32_t nsamp, uint32_t nchans, const uint8_t* __restrict__ mask,
+    float* __restrict__ m)
+{
+    using Acc = typename std::conditional<sizeof(T) == 1, int32_t, double>::type;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t t0 = (uint64_t)blockIdx.x * kRmRowsPerWg + wave * kRmRows;
+    for (uint32_t r = 0; r < kRmRows; ++r) {
+        const uint64_t t = t0 + r;
+        if (t >= nsamp) return;   // wave-uniform
+        const T* row = x + t * nchans;
+        Acc s = 0;
+        int32_t nu = 0;
+        for (uint32_t c = lane; c < nchans; c += 64) {
+            if (mask && mask[c]) continue;
+            s += (Acc)row[c];
+            ++nu;
+        }
+#pragma unroll
+        for (uint32_t off = 32; off > 0; off >>= 1) {
+            s += __shfl_xor(s, off, 64);
+            nu += __shfl_xor(nu, off, 64);
+        }
+        if (lane == 0) m[t] = nu ? (float)((double)s / (double)nu) : 0.0f;
+    }
+}
+
+// Zero-DM variant of both transposes: T = uint8_t, int8_t or float in, float32
+// x - m out, channel-major; tile of 64 channels x 64 samples, the pitch in
+// floats, its padding (and every t >= nsamp) written as zero.
+template <class T>
+__global__ __launch_bounds__(kDdThreads) void dedisp_transpose_zdm_kernel(
+    const T* __restrict__ x, uint32_t nsamp, uint32_t nchans, const float* __restrict__ m, float* __restrict__ ws,
+    uint64_t pitch)
+{
+    __shared__ float tile[64][65];
+    const uint32_t tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const uint64_t t0 = (uint64_t)blockIdx.x * 64;
+    const uint32_t c0 = blockIdx.y * 64;
+    const uint32_t c = c0 + tx;
+    for (uint32_t i = ty; i < 64; i += 4) {
+        const uint64_t t = t0 + i;
+        float v = 0.0f;
+        if (t < nsamp) {   // wave-uniform: m[t] is one broadcast load
+            const float mt = m[t];
+            if (c < nchans) v = dd_value(x[t * nchans + c]) - mt;
+        }
+        tile[tx][i] = v;
+    }
+    __syncthreads();
+    const uint64_t t = t0 + tx;
+    for (uint32_t i = ty; i < 64; i += 4) {
+        const uint32_t co = c0 + i;
+        if (co < nchans && t < pitch) ws[(uint64_t)co * pitch + t] = tile[i][tx];
+    }
+}
+
+// Per-channel sum and sum of squares of one chunk of kCsChunk time samples:
+// the lanes across 64 channels, the four waves interleaved over the chunk's
+// rows, their partial sums added in wave order through LDS.  8-bit samples
+// are summed as integers (at most 512 rows x 128^2 or 255^2 per wave: below
+// 2^31 / 2^32), float samples in float64.  part is [nchunks, 2, nchans].
+template <class T>
+__global__ __launch_bounds__(kDdThreads) void dedisp_chanstats_kernel(
+    const T* __restrict__ x, uint32_t nsamp, uint32_t nchans, double* __restrict__ part)
+{
+    constexpr bool kBytes = sizeof(T) == 1;
+    using Sum = typename std::conditional<kBytes, int32_t, double>::type;
+    using Sq = typename std::conditional<kBytes, uint32_t, double>::type;
+    __shared__ double red[2][kDdWaves][64];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t c = blockIdx.y * 64 + lane;
+    const uint64_t t0 = (uint64_t)blockIdx.x * kCsChunk;
+    const uint64_t t1 = min(t0 + kCsChunk, (uint64_t)nsamp);
+    Sum s = 0;
+    Sq q = 0;
+    if (c < nchans)
+        for (uint64_t t = t0 + wave; t < t1; t += kDdWaves) {
+            const Sum v = (Sum)x[t * nchans + c];
+            s += v;
+            q += (Sq)(v * v);
+        }
+    red[0][wave][lane] = (double)s;
+    red[1][wave][lane] = (double)q;
+    __syncthreads();
+    if (wave < 2 && c < nchans) {   // wave 0 the sums, wave 1 the squares
+        double a = red[wave][0][lane];
+#pragma unroll
+        for (uint32_t w = 1; w < kDdWaves; ++w) a += red[wave][w][lane];
+        part[((uint64_t)blockIdx.x * 2 + wave) * nchans + c] = a;
+    }
+}
+
+// acc[k, c] += the chunks' partial sums, in chunk order: one thread per (k, c)
+__global__ __launch_bounds__(kDdThreads) void dedisp_chanstats_fold_kernel(
+    const double* __restrict__ part, uint32_t nchunks, uint32_t nchans, double* __restrict__ acc)
+{
+    const uint32_t i = blockIdx.x * kDdThreads + threadIdx.x;   // k * nchans + c
+    if (i >= 2 * nchans) return;
+    double a = acc[i];
+    for (uint32_t k = 0; k < nchunks; ++k) a += part[(uint64_t)k * 2 * nchans + i];
+    acc[i] = a;
 }
 
 // T = uint8_t (signed samples biased by 128: bias = 128) or float.  pitch is
@@ -235,14 +366,79 @@ uint64_t dedisp_pitch_bytes(int dtype, uint64_t nsamp_blk)
     return (nsamp_blk * esize + 15) / 16 * 16;
 }
 
+uint64_t dedisp_workspace_bytes(int dtype, uint64_t nsamp_blk, uint64_t nchans, uint32_t flags)
+{
+    if (flags & kDdZeroDm) return dedisp_pitch_bytes(2, nsamp_blk) * (nchans + 1);   // float rows, then m
+    return dedisp_pitch_bytes(dtype, nsamp_blk) * nchans;
+}
+
+hipError_t launch_zero_dm_mean(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
+                               const uint8_t* d_mask, float* m, hipStream_t s)
+{
+    const dim3 grid((nsamp_blk + kRmRowsPerWg - 1) / kRmRowsPerWg);
+    if (dtype == 0)
+        hipLaunchKernelGGL(dedisp_rowmean_kernel<uint8_t>, grid, dim3(kDdThreads), 0, s, (const uint8_t*)block,
+                           nsamp_blk, nchans, d_mask, m);
+    else if (dtype == 1)
+        hipLaunchKernelGGL(dedisp_rowmean_kernel<int8_t>, grid, dim3(kDdThreads), 0, s, (const int8_t*)block,
+                           nsamp_blk, nchans, d_mask, m);
+    else
+        hipLaunchKernelGGL(dedisp_rowmean_kernel<float>, grid, dim3(kDdThreads), 0, s, (const float*)block,
+                           nsamp_blk, nchans, d_mask, m);
+    return hipGetLastError();
+}
+
+uint64_t chanstats_workspace_bytes(uint64_t nsamp_blk, uint64_t nchans)
+{
+    return (nsamp_blk + kCsChunk - 1) / kCsChunk * 2 * nchans * sizeof(double);
+}
+
+hipError_t launch_channel_stats(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans, double* acc,
+                                void* ws, hipStream_t s)
+{
+    const uint32_t nchunks = (nsamp_blk + kCsChunk - 1) / kCsChunk;
+    const dim3 grid(nchunks, (nchans + 63) / 64);
+    double* part = (double*)ws;
+    if (dtype == 0)
+        hipLaunchKernelGGL(dedisp_chanstats_kernel<uint8_t>, grid, dim3(kDdThreads), 0, s, (const uint8_t*)block,
+                           nsamp_blk, nchans, part);
+    else if (dtype == 1)
+        hipLaunchKernelGGL(dedisp_chanstats_kernel<int8_t>, grid, dim3(kDdThreads), 0, s, (const int8_t*)block,
+                           nsamp_blk, nchans, part);
+    else
+        hipLaunchKernelGGL(dedisp_chanstats_kernel<float>, grid, dim3(kDdThreads), 0, s, (const float*)block,
+                           nsamp_blk, nchans, part);
+    hipLaunchKernelGGL(dedisp_chanstats_fold_kernel, dim3((2 * nchans + kDdThreads - 1) / kDdThreads),
+                       dim3(kDdThreads), 0, s, (const double*)part, nchunks, nchans, acc);
+    return hipGetLastError();
+}
+
 hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
                              const int32_t* d_delays, const uint8_t* d_mask, uint32_t ndm, uint32_t max_delay,
-                             float* out, uint64_t out_stride, void* ws, hipStream_t s)
+                             float* out, uint64_t out_stride, void* ws, uint32_t flags, hipStream_t s)
 {
     const uint32_t nout = nsamp_blk - max_delay;
-    const uint64_t pitch_bytes = dedisp_pitch_bytes(dtype, nsamp_blk);
+    const uint64_t pitch_bytes = dedisp_pitch_bytes(flags & kDdZeroDm ? 2 : dtype, nsamp_blk);
     const dim3 sum_grid((nout + kDdTile - 1) / kDdTile, (ndm + kDdDms - 1) / kDdDms);
-    if (dtype == 2) {
+    if (flags & kDdZeroDm) {
+        // m behind the float rows; every sample type then takes the float sum
+        const uint64_t pitch = pitch_bytes / 4;
+        float* m = (float*)ws + pitch * nchans;
+        const hipError_t e = launch_zero_dm_mean(block, dtype, nsamp_blk, nchans, d_mask, m, s);
+        if (e != hipSuccess) return e;
+        const dim3 grid((uint32_t)((pitch + 63) / 64), (nchans + 63) / 64);
+        if (dtype == 0)
+            hipLaunchKernelGGL(dedisp_transpose_zdm_kernel<uint8_t>, grid, dim3(kDdThreads), 0, s,
+                               (const uint8_t*)block, nsamp_blk, nchans, (const float*)m, (float*)ws, pitch);
+        else if (dtype == 1)
+            hipLaunchKernelGGL(dedisp_transpose_zdm_kernel<int8_t>, grid, dim3(kDdThreads), 0, s,
+                               (const int8_t*)block, nsamp_blk, nchans, (const float*)m, (float*)ws, pitch);
+        else
+            hipLaunchKernelGGL(dedisp_transpose_zdm_kernel<float>, grid, dim3(kDdThreads), 0, s,
+                               (const float*)block, nsamp_blk, nchans, (const float*)m, (float*)ws, pitch);
+        hipLaunchKernelGGL(dedisp_sum_kernel<float>, sum_grid, dim3(kDdThreads), 0, s, (const float*)ws, pitch,
+                           nchans, d_delays, d_mask, ndm, max_delay, nout, out, out_stride, 0);
+    } else if (dtype == 2) {
         const uint64_t pitch = pitch_bytes / 4;
         const dim3 grid((uint32_t)((pitch + 63) / 64), (nchans + 63) / 64);
         hipLaunchKernelGGL(dedisp_transpose32_kernel, grid, dim3(kDdThreads), 0, s, (const float*)block, nsamp_blk,

@@ -109,9 +109,23 @@ uint64_t dedisp_pitch_bytes(int dtype, uint64_t nsamp_blk);
 // out[d * out_stride + t] for t < nsamp_blk - max_delay; ws: nchans rows of
 // dedisp_pitch_bytes, 16-byte aligned.  The caller has checked the shape
 // (rt_dedisperse_device).
+// flags: 0 or kDdZeroDm (the zero-DM filter: m = the rows' means over the
+// unmasked channels, float rows of x - m, the float sum for every dtype).
+constexpr uint32_t kDdZeroDm = 1u;   // RT_DEDISP_ZERO_DM
+// bytes of ws for these flags: the rows, with kDdZeroDm float rows plus one
+// more pitch for m [nsamp_blk]
+uint64_t dedisp_workspace_bytes(int dtype, uint64_t nsamp_blk, uint64_t nchans, uint32_t flags);
 hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
                              const int32_t* d_delays, const uint8_t* d_mask, uint32_t ndm, uint32_t max_delay,
-                             float* out, uint64_t out_stride, void* ws, hipStream_t s);
+                             float* out, uint64_t out_stride, void* ws, uint32_t flags, hipStream_t s);
+// m[t] = (float32)(sum over unmasked c of block[t, c] / their number), t < nsamp_blk
+hipError_t launch_zero_dm_mean(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
+                               const uint8_t* d_mask, float* m, hipStream_t s);
+// acc [2, nchans] float64 += the block's per-channel sums and sums of squares;
+// ws: chanstats_workspace_bytes of per-chunk partial sums
+uint64_t chanstats_workspace_bytes(uint64_t nsamp_blk, uint64_t nchans);
+hipError_t launch_channel_stats(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans, double* acc,
+                                void* ws, hipStream_t s);
 
 // harmonic_kernels.hip
 // One tile of the harmonic pair matrix: rows [i0, i0 + rows) of the n ranked

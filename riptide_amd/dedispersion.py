@@ -10,6 +10,14 @@ with the delay of channel c against the highest frequency of the band
   delay[d, c] = floor(kdm * dm[d] * (f_c ** -2 - f_ref ** -2) / tsamp + 0.5)
 
 8-bit data gives exact integer sums; float32 data is summed in float32.
+
+zero_dm=True puts the zero-DM filter (Eatough, Keane & Lyne 2009) in front of
+the sum: every time sample first loses its mean over the unmasked channels,
+
+  m[t] = float32(sum over unmasked c of x[t, c] / their number),  y = x - m,
+
+and y is summed in float32 for every sample type (RT_DEDISP_ZERO_DM in
+include/riptide_amd.h; rfi.py for the mean series and channel statistics).
 """
 import ctypes
 
@@ -71,10 +79,26 @@ def _checked_data(data):
     return data
 
 
-def dedisperse_host(data, delays, max_delay, mask=None, nout=None):
-    """The specification on the host (rt_dedisperse_host, no device): float32
-    [ndm, nout] from data [nsamp, nchans] and a delay table; nout defaults to
-    nsamp - max_delay."""
+def _flags(zero_dm):
+    return 1 if zero_dm else 0     # RT_DEDISP_ZERO_DM
+
+
+def zero_dm_mean_host(data, mask=None):
+    """The zero-DM mean series on the host (rt_zero_dm_mean_host, no device):
+    float32 [nsamp], every time sample's mean over the unmasked channels."""
+    data = np.ascontiguousarray(_checked_data(data))
+    nsamp, nchans = data.shape
+    mask = _checked_mask(mask, nchans)
+    m = np.zeros(nsamp, dtype=np.float32)
+    _check(_L.rt_zero_dm_mean_host(_lib.ptr(data), _DTYPE_CODES[data.dtype], nsamp, nchans,
+                                   None if mask is None else _lib.ptr(mask), _lib.ptr(m)))
+    return m
+
+
+def dedisperse_host(data, delays, max_delay, mask=None, nout=None, zero_dm=False):
+    """The specification on the host (rt_dedisperse_host_opt, no device):
+    float32 [ndm, nout] from data [nsamp, nchans] and a delay table; nout
+    defaults to nsamp - max_delay."""
     data = np.ascontiguousarray(_checked_data(data))
     nsamp, nchans = data.shape
     delays = np.ascontiguousarray(delays, dtype=np.int64)
@@ -85,13 +109,13 @@ def dedisperse_host(data, delays, max_delay, mask=None, nout=None):
     if nout < 0:
         raise ValueError(f"max_delay {max_delay} exceeds the {nsamp} samples of the input")
     out = np.zeros((delays.shape[0], nout), dtype=np.float32)
-    _check(_L.rt_dedisperse_host(_lib.ptr(data), _DTYPE_CODES[data.dtype], nsamp, nchans, _lib.ptr(delays),
-                                 None if mask is None else _lib.ptr(mask), delays.shape[0], int(max_delay), nout,
-                                 _lib.ptr(out)))
+    _check(_L.rt_dedisperse_host_opt(_lib.ptr(data), _DTYPE_CODES[data.dtype], nsamp, nchans, _lib.ptr(delays),
+                                     None if mask is None else _lib.ptr(mask), delays.shape[0], int(max_delay),
+                                     nout, _lib.ptr(out), _flags(zero_dm)))
     return out
 
 
-def dedisperse(data, freqs, tsamp, dms, mask=None, kdm=KDM):
+def dedisperse(data, freqs, tsamp, dms, mask=None, kdm=KDM, zero_dm=False):
     """Dedisperse host data [nsamp, nchans] (uint8, int8 or float32) at the
     trial DMs on the GPU: float32 [ndm, nsamp - max_delay] (rt_dedisperse:
     upload, kernels, download).  mask: per channel, True = skipped; a masked
@@ -105,13 +129,63 @@ def dedisperse(data, freqs, tsamp, dms, mask=None, kdm=KDM):
     if max_delay >= nsamp:
         raise ValueError(f"the largest delay ({max_delay} samples) is not below the {nsamp} samples of the data")
     out = np.empty((delays.shape[0], nsamp - max_delay), dtype=np.float32)
-    _check(_L.rt_dedisperse(_lib.ptr(data), _DTYPE_CODES[data.dtype], nsamp, nchans, _lib.ptr(delays),
-                            None if mask is None else _lib.ptr(mask), delays.shape[0], max_delay, _lib.ptr(out)))
+    _check(_L.rt_dedisperse_opt(_lib.ptr(data), _DTYPE_CODES[data.dtype], nsamp, nchans, _lib.ptr(delays),
+                                None if mask is None else _lib.ptr(mask), delays.shape[0], max_delay, _lib.ptr(out),
+                                _flags(zero_dm)))
     return out
 
 
+def stream_gulps(fb, dev, gulp, nrows, overlap, process):
+    """Stream rows [0, nrows) of a reading.Filterbank's memory map to `dev` in
+    gulps of `gulp` time samples that overlap by `overlap`, through two
+    page-locked staging buffers and two device blocks: the upload of gulp
+    k + 1 runs on a copy stream behind the kernels of gulp k.  For every gulp
+    process(block, start) queues its kernels on the current stream; block is
+    the device tensor [g, nchans] of rows [start, start + g).  Called inside
+    torch.cuda.device(dev); returns once the last gulp is queued and every
+    upload is done.  (dedisperse_filterbank, rfi.channel_stats and
+    rfi.zero_dm_series share it.)"""
+    import torch
+    nchans = fb.nchans
+    tdtype = {"uint8": torch.uint8, "int8": torch.int8, "float32": torch.float32}[np.dtype(fb.dtype).name]
+    main = torch.cuda.current_stream(dev)
+    copy = torch.cuda.Stream(device=dev)
+    pinned = [torch.empty((gulp, nchans), dtype=tdtype).pin_memory() for _ in range(2)]
+    blocks = [torch.empty((gulp, nchans), dtype=tdtype, device=dev) for _ in range(2)]
+    uploaded = [torch.cuda.Event() for _ in range(2)]   # slot's upload is done: its staging buffer is free
+    consumed = [torch.cuda.Event() for _ in range(2)]   # slot's kernels are done: its device block is free
+    # The device blocks come from the main stream's pool: the allocator may
+    # hand out memory that work already queued on main (an earlier call's
+    # last kernels, say) still reads.  The copy stream starts behind it.
+    copy.wait_stream(main)
+    start, k = 0, 0
+    while start < nrows - overlap:
+        g = min(gulp, nrows - start)
+        slot = k & 1
+        if k >= 2:
+            uploaded[slot].synchronize()
+        np.copyto(pinned[slot][:g].numpy(), fb.data[start:start + g])
+        with torch.cuda.stream(copy):
+            if k >= 2:
+                copy.wait_event(consumed[slot])
+            blocks[slot][:g].copy_(pinned[slot][:g], non_blocking=True)
+            uploaded[slot].record(copy)
+        main.wait_event(uploaded[slot])
+        process(blocks[slot][:g], start)
+        consumed[slot].record(main)
+        start += g - overlap
+        k += 1
+    # Every upload is done before the staging buffers and the device blocks
+    # are released with this frame, so the copy stream no longer uses
+    # them; the kernels still queued read the blocks on main, the stream
+    # the blocks were allocated on, whose pool reuses them in stream order.
+    uploaded[(k - 1) & 1].synchronize()
+    if k > 1:
+        uploaded[k & 1].synchronize()
+
+
 def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, nout=None,
-                          budget_bytes=DEFAULT_BUDGET_BYTES):
+                          budget_bytes=DEFAULT_BUDGET_BYTES, zero_dm=False):
     """Dedisperse a reading.Filterbank at the trial DMs into one device tensor
     float32 [ndm, nout], nout = nsamp - max_delay (or a smaller `nout`: the
     first nout samples, e.g. the length a larger DM list would leave).
@@ -122,6 +196,10 @@ def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, n
     copy stream behind the kernels of gulp k.  The result does not depend on
     gulp.  Queued on the current stream of `device`; the call returns once the
     last gulp is queued.
+
+    zero_dm: the zero-DM filter in front of the sum (module docstring).  The
+    mean of a time sample needs that sample's row alone, so the result still
+    does not depend on gulp; the workspace of a gulp is the larger float32 one.
 
     ValueError -- nothing is launched -- when max_delay >= nsamp, for 8-bit
     data of more than 65793 channels, and when the output (ndm * nout * 4
@@ -154,50 +232,20 @@ def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, n
         raise ValueError(f"gulp must exceed the largest delay ({max_delay} samples)")
     need_in = nout + max_delay          # input rows the outputs read
     gulp = min(gulp, need_in)
-    ws_bytes = engine.dedisperse_workspace_bytes(dtype.name, gulp, nchans)
+    ws_bytes = engine.dedisperse_workspace_bytes(dtype.name, gulp, nchans, zero_dm)
     total = ndm * nout * 4 + 2 * gulp * row_bytes + ws_bytes
     if total > int(budget_bytes):
         raise ValueError(f"dedispersing {ndm} DMs needs {total} bytes of device memory ({ndm * nout * 4} of output "
                          f"plus the gulp buffers), over the budget of {int(budget_bytes)}: pass fewer DMs per call")
-    tdtype = {"uint8": torch.uint8, "int8": torch.int8, "float32": torch.float32}[dtype.name]
     with torch.cuda.device(dev):
-        main = torch.cuda.current_stream(dev)
-        copy = torch.cuda.Stream(device=dev)
         out = torch.empty((ndm, nout), dtype=torch.float32, device=dev)
         d_delays = torch.from_numpy(delays.astype(np.int32)).to(dev)
         d_mask = None if mask is None else torch.from_numpy(mask).to(dev)
         workspace = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        pinned = [torch.empty((gulp, nchans), dtype=tdtype).pin_memory() for _ in range(2)]
-        blocks = [torch.empty((gulp, nchans), dtype=tdtype, device=dev) for _ in range(2)]
-        uploaded = [torch.cuda.Event() for _ in range(2)]   # slot's upload is done: its staging buffer is free
-        consumed = [torch.cuda.Event() for _ in range(2)]   # slot's kernels are done: its device block is free
-        # The device blocks come from the main stream's pool: the allocator may
-        # hand out memory that work already queued on main (an earlier call's
-        # last kernels, say) still reads.  The copy stream starts behind it.
-        copy.wait_stream(main)
-        start, k = 0, 0
-        while start < nout:
-            g = min(gulp, need_in - start)
-            slot = k & 1
-            if k >= 2:
-                uploaded[slot].synchronize()
-            np.copyto(pinned[slot][:g].numpy(), fb.data[start:start + g])
-            with torch.cuda.stream(copy):
-                if k >= 2:
-                    copy.wait_event(consumed[slot])
-                blocks[slot][:g].copy_(pinned[slot][:g], non_blocking=True)
-                uploaded[slot].record(copy)
-            main.wait_event(uploaded[slot])
-            engine.dedisperse_device(blocks[slot][:g], d_delays, max_delay, mask=d_mask, out=out, out_offset=start,
-                                     workspace=workspace, stream=main)
-            consumed[slot].record(main)
-            start += g - max_delay
-            k += 1
-        # Every upload is done before the staging buffers and the device blocks
-        # are released with this frame, so the copy stream no longer uses
-        # them; the kernels still queued read the blocks on main, the stream
-        # the blocks were allocated on, whose pool reuses them in stream order.
-        uploaded[(k - 1) & 1].synchronize()
-        if k > 1:
-            uploaded[k & 1].synchronize()
+
+        def process(block, start):
+            engine.dedisperse_device(block, d_delays, max_delay, mask=d_mask, out=out, out_offset=start,
+                                     workspace=workspace, zero_dm=zero_dm)
+
+        stream_gulps(fb, dev, gulp, need_in, max_delay, process)
     return out

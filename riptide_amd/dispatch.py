@@ -214,7 +214,7 @@ class EngineSearcher:
         (8-bit data converted on the device), results in input order."""
         return self.submit_samples(samples, tsamps, metadatas)()
 
-    def search_filterbank(self, fb, dms, mask=None, nout=None, kdm=None):
+    def search_filterbank(self, fb, dms, mask=None, nout=None, kdm=None, zero_dm=False):
         """Dedisperse a reading.Filterbank at the trial DMs on the device
         (dedispersion.dedisperse_filterbank) and search every series: one peak
         list per DM, in the order given (the __call__ contract).  The series
@@ -224,7 +224,9 @@ class EngineSearcher:
         `nout` cuts every series to its first nout samples (the length a
         longer DM list would leave: search_filterbank of this module); `kdm`
         is the dispersion constant of the delay table (default:
-        dedispersion.KDM)."""
+        dedispersion.KDM); `zero_dm` puts the zero-DM filter in front of the
+        sum (dedispersion.dedisperse_filterbank; rfi.channel_mask builds a
+        `mask` from the file's channel statistics)."""
         import torch
         from .dedispersion import KDM, dedisperse_filterbank
         kdm = KDM if kdm is None else float(kdm)
@@ -234,7 +236,7 @@ class EngineSearcher:
         dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else
                            (self.device.index if isinstance(self.device, torch.device) else int(self.device)))
         with torch.cuda.device(dev):
-            series = dedisperse_filterbank(fb, dms, mask=mask, device=dev, nout=nout, kdm=kdm)
+            series = dedisperse_filterbank(fb, dms, mask=mask, device=dev, nout=nout, kdm=kdm, zero_dm=zero_dm)
             metas = [fb.metadata(dm) for dm in dms]
             slices = [(b0, min(b0 + self.batch, len(dms))) for b0 in range(0, len(dms), self.batch)]
             per, pending = [], None
@@ -313,7 +315,7 @@ def search_files(fnames, pool, group=None, chunksize=None):
     return _gather_tagged(tagged, group, world)
 
 
-def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=None):
+def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=None, zero_dm=False):
     """Search a channelised SIGPROC file at the trial DMs without leaving the
     device: each rank dedisperses its round-robin share of `dms`
     (searcher.search_filterbank, an EngineSearcher) from the one file and
@@ -323,7 +325,8 @@ def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=Non
     cuts its series to the length the whole DM list leaves, nsamp minus the
     list's largest delay, so the result does not depend on the sharding.
     `kdm` is the dispersion constant of the delay table, on every rank
-    (default: dedispersion.KDM)."""
+    (default: dedispersion.KDM); `zero_dm` subtracts every time sample's mean
+    over the unmasked channels before the sum (the zero-DM filter)."""
     from .dedispersion import KDM, dispersion_delays
     kdm = KDM if kdm is None else float(kdm)
     from .reading import Filterbank
@@ -337,8 +340,10 @@ def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=Non
             raise ValueError(f"the largest delay ({max_delay} samples) is not below the {fb.nsamp} samples of the "
                              "file")
         mine = shard(len(dms), rank, world)
+        # zero_dm is passed only when set: a searcher without the argument keeps working
+        extra = {"zero_dm": True} if zero_dm else {}
         local = searcher.search_filterbank(fb, [dms[i] for i in mine], mask=mask, nout=fb.nsamp - max_delay,
-                                          kdm=kdm)
+                                          kdm=kdm, **extra)
         if len(local) != len(mine):
             raise RuntimeError("searcher must return one peak list per DM")
         tagged = [(i, [tuple(p) for p in plist]) for i, plist in zip(mine, local)]

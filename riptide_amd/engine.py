@@ -272,16 +272,91 @@ def fold_device(data, tsamp, specs, stream=None):
 DEDISP_DTYPES = {"uint8": 0, "int8": 1, "float32": 2}
 
 
-def dedisperse_workspace_bytes(dtype, nsamp_blk, nchans):
+DEDISP_ZERO_DM = 1    # RT_DEDISP_ZERO_DM
+
+
+def dedisperse_workspace_bytes(dtype, nsamp_blk, nchans, zero_dm=False):
     """Device workspace bytes of dedisperse_device for a block of this shape;
-    dtype is 'uint8', 'int8' or 'float32'."""
+    dtype is 'uint8', 'int8' or 'float32'.  With zero_dm every dtype takes
+    float32 rows, plus nsamp_blk floats for the mean series."""
     b = ctypes.c_size_t()
-    _check(_L.rt_dedisperse_workspace_bytes(DEDISP_DTYPES[str(dtype)], int(nsamp_blk), int(nchans),
-                                            ctypes.byref(b)))
+    _check(_L.rt_dedisperse_workspace_bytes_opt(DEDISP_DTYPES[str(dtype)], int(nsamp_blk), int(nchans),
+                                                DEDISP_ZERO_DM if zero_dm else 0, ctypes.byref(b)))
     return b.value
 
 
-def dedisperse_device(block, delays, max_delay, mask=None, out=None, out_offset=0, workspace=None, stream=None):
+def _dedisp_block(block):
+    """(dtype name, nsamp_blk, nchans) of a block argument, validated."""
+    if block.dim() != 2 or block.device.type != "cuda" or not block.is_contiguous():
+        raise ValueError("block must be a contiguous [nsamp_blk, nchans] device tensor")
+    name = str(block.dtype).replace("torch.", "")
+    if name not in DEDISP_DTYPES:
+        raise ValueError("block must be uint8, int8 or float32")
+    return name, block.shape[0], block.shape[1]
+
+
+def zero_dm_mean_device(block, mask=None, out=None, stream=None):
+    """The zero-DM time series of one resident block (rt_zero_dm_mean_device,
+    the row-mean kernel alone): float32 [nsamp_blk], every time sample's mean
+    over the unmasked channels -- the sum exact for 8-bit data, in float64 for
+    float32 data, divided in float64 and rounded to float32 once; all zero
+    when every channel is masked.  block and mask as for dedisperse_device.
+    Stream-ordered, no host synchronisation."""
+    import torch
+    name, nsamp_blk, nchans = _dedisp_block(block)
+    if mask is not None and (mask.dtype != torch.uint8 or mask.device != block.device or not mask.is_contiguous()
+                             or tuple(mask.shape) != (nchans,)):
+        raise ValueError("mask must be a contiguous uint8 [nchans] tensor on the block's device")
+    s = stream if stream is not None else torch.cuda.current_stream(block.device)
+    with torch.cuda.device(block.device), torch.cuda.stream(s):
+        if out is None:
+            out = torch.empty(nsamp_blk, dtype=torch.float32, device=block.device)
+        elif (out.dtype != torch.float32 or out.device != block.device or not out.is_contiguous()
+              or tuple(out.shape) != (nsamp_blk,)):
+            raise ValueError(f"out must be a contiguous float32 [{nsamp_blk}] tensor on the block's device")
+        if nsamp_blk:
+            _check(_L.rt_zero_dm_mean_device(_lib.ptr(block), DEDISP_DTYPES[name], nsamp_blk, nchans,
+                                             None if mask is None else _lib.ptr(mask), _lib.ptr(out),
+                                             _stream_handle(s)))
+    return out
+
+
+def channel_stats_workspace_bytes(nsamp_blk, nchans):
+    """Device workspace bytes of channel_stats_device for a block of this shape."""
+    b = ctypes.c_size_t()
+    _check(_L.rt_channel_stats_workspace_bytes(int(nsamp_blk), int(nchans), ctypes.byref(b)))
+    return b.value
+
+
+def channel_stats_device(block, acc, workspace=None, stream=None):
+    """Add the per-channel sums of one resident block into acc, float64
+    [2, nchans] on the block's device (rt_channel_stats_device): acc[0] += the
+    sum over time of block[:, c], acc[1] += the sum of its squares (int8
+    samples as signed values).  Partial sums per chunk of time, folded in
+    chunk order: no atomics, the same bits every time; 8-bit sums are exact.
+    Stream-ordered, no host synchronisation.  Returns acc."""
+    import torch
+    name, nsamp_blk, nchans = _dedisp_block(block)
+    if (acc.dtype != torch.float64 or acc.device != block.device or not acc.is_contiguous()
+            or tuple(acc.shape) != (2, nchans)):
+        raise ValueError(f"acc must be a contiguous float64 [2, {nchans}] tensor on the block's device")
+    s = stream if stream is not None else torch.cuda.current_stream(block.device)
+    with torch.cuda.device(block.device), torch.cuda.stream(s):
+        if not nsamp_blk:
+            return acc
+        need = channel_stats_workspace_bytes(nsamp_blk, nchans)
+        if workspace is None:
+            workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=block.device)
+        elif (workspace.dtype != torch.uint8 or workspace.device != block.device or not workspace.is_contiguous()
+              or workspace.numel() < need):
+            raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on the block's device")
+        _check(_L.rt_channel_stats_device(_lib.ptr(block), DEDISP_DTYPES[name], nsamp_blk, nchans, _lib.ptr(acc),
+                                          _lib.ptr(workspace), workspace.numel(), _stream_handle(s)))
+    return acc
+
+
+def dedisperse_device(block, delays, max_delay, mask=None, out=None, out_offset=0, workspace=None, stream=None,
+                      zero_dm=False):
     """Incoherent dedispersion of one resident block (rt_dedisperse_device):
     block uint8 / int8 / float32 [nsamp_blk, nchans] (time-major, contiguous),
     delays int32 [ndm, nchans] and mask (uint8 [nchans], non-zero = skipped, or
@@ -290,14 +365,15 @@ def dedisperse_device(block, delays, max_delay, mask=None, out=None, out_offset=
     max_delay) and returns out (float32 [ndm, >= out_offset + nsamp_blk -
     max_delay], rows with unit stride; allocated [ndm, nsamp_blk - max_delay]
     when None).  Stream-ordered, no host synchronisation.  8-bit results are
-    exact; float32 results are summed in channel order."""
+    exact; float32 results are summed in channel order.
+
+    zero_dm: the zero-DM filter (RT_DEDISP_ZERO_DM in include/riptide_amd.h).
+    Every time sample first loses its mean over the unmasked channels
+    (zero_dm_mean_device), and every dtype is then summed in float32 in channel
+    order; the workspace is the larger one of dedisperse_workspace_bytes(...,
+    zero_dm=True)."""
     import torch
-    if block.dim() != 2 or block.device.type != "cuda" or not block.is_contiguous():
-        raise ValueError("block must be a contiguous [nsamp_blk, nchans] device tensor")
-    name = str(block.dtype).replace("torch.", "")
-    if name not in DEDISP_DTYPES:
-        raise ValueError("block must be uint8, int8 or float32")
-    nsamp_blk, nchans = block.shape
+    name, nsamp_blk, nchans = _dedisp_block(block)
     if (delays.dim() != 2 or delays.dtype != torch.int32 or delays.device != block.device
             or not delays.is_contiguous() or delays.shape[1] != nchans):
         raise ValueError("delays must be a contiguous int32 [ndm, nchans] tensor on the block's device")
@@ -310,7 +386,7 @@ def dedisperse_device(block, delays, max_delay, mask=None, out=None, out_offset=
     s = stream if stream is not None else torch.cuda.current_stream(block.device)
     with torch.cuda.device(block.device), torch.cuda.stream(s):
         # validates the shape before anything is allocated
-        need = dedisperse_workspace_bytes(name, nsamp_blk, nchans)
+        need = dedisperse_workspace_bytes(name, nsamp_blk, nchans, zero_dm)
         if not 0 <= max_delay < nsamp_blk:
             raise ValueError(f"max_delay {max_delay} must be in [0, {nsamp_blk}): the block is no longer than the "
                              "largest delay")
@@ -326,10 +402,14 @@ def dedisperse_device(block, delays, max_delay, mask=None, out=None, out_offset=
         elif (workspace.dtype != torch.uint8 or workspace.device != block.device or not workspace.is_contiguous()
               or workspace.numel() < need):
             raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on the block's device")
-        _check(_L.rt_dedisperse_device(_lib.ptr(block), DEDISP_DTYPES[name], nsamp_blk, nchans, _lib.ptr(delays),
-                                       None if mask is None else _lib.ptr(mask), ndm, max_delay, _lib.ptr(out),
-                                       out.stride(0) if ndm > 1 else out.shape[1], int(out_offset),
-                                       _lib.ptr(workspace), workspace.numel(), _stream_handle(s)))
+        args = (_lib.ptr(block), DEDISP_DTYPES[name], nsamp_blk, nchans, _lib.ptr(delays),
+                None if mask is None else _lib.ptr(mask), ndm, max_delay, _lib.ptr(out),
+                out.stride(0) if ndm > 1 else out.shape[1], int(out_offset), _lib.ptr(workspace), workspace.numel(),
+                _stream_handle(s))
+        if zero_dm:
+            _check(_L.rt_dedisperse_device_opt(*args, DEDISP_ZERO_DM))
+        else:
+            _check(_L.rt_dedisperse_device(*args))
     return out
 
 

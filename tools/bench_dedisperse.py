@@ -7,6 +7,11 @@ workspace preallocated); one warm-up, then the median of --repeats calls.
 Reports ms per DM trial, channel-samples/s, algorithmic bytes/s (block read
 once, output written once) and the ratio of the per-trial time to the
 per-trial search time of BENCH_r06.json (cfg2: ms_per_step over 16 trials).
+--zero-dm adds the same call with the zero-DM filter (row mean + float
+transpose + float sum) and the row-mean kernel alone; --stats adds
+engine.channel_stats_device alone.  Both report their time next to the plain
+call's, the row-mean and statistics kernels also as GB/s against the block's
+bytes (each reads the block once).
 A record, not a gate: prints one JSON line and writes it to --out.
 
     python tools/bench_dedisperse.py --out profiles/<tag>_dedisperse.json
@@ -30,6 +35,8 @@ def main():
     ap.add_argument("--log2-nsamp", type=int, default=22)
     ap.add_argument("--ndm", type=int, default=256)
     ap.add_argument("--dm-max", type=float, default=255.0)
+    ap.add_argument("--zero-dm", action="store_true", help="also time the call with the zero-DM filter")
+    ap.add_argument("--stats", action="store_true", help="also time the channel statistics")
     args = ap.parse_args()
     if args.repeats < 10:
         ap.error("--repeats must be at least 10")
@@ -64,14 +71,67 @@ def main():
     got = out[rows, t_chk:t_chk + 64].to(torch.int64)
     assert torch.equal(got, ref), "dedisperse_device differs from its definition"
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ms = []
-    for _ in range(args.repeats):
-        a.record()
-        run()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
+
+    def timed(fn):
+        ms = []
+        for _ in range(args.repeats):
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ms.append(a.elapsed_time(b))
+        return ms
+
+    ms = timed(run)
     med = float(np.median(ms))
+    block_bytes = nsamp * nchans
+    extra = {}
+    if args.zero_dm:
+        zws = torch.empty(engine.dedisperse_workspace_bytes("uint8", nsamp, nchans, zero_dm=True), dtype=torch.uint8,
+                          device="cuda")
+        mean = torch.empty(nsamp, dtype=torch.float32, device="cuda")
+
+        def run_zero_dm():
+            engine.dedisperse_device(block, d_delays, max_delay, out=out, workspace=zws, zero_dm=True)
+
+        def run_mean():
+            engine.zero_dm_mean_device(block, out=mean)
+
+        run_zero_dm()
+        run_mean()
+        torch.cuda.synchronize()
+        # spot check against the definition: the mean series bit for bit, the
+        # sums within nchans * 2^-24 * sum |y| of the float64 sums of x - m
+        s_chk = block[t_chk:t_chk + 4096].to(torch.int64).sum(dim=1)
+        m_ref = (s_chk.to(torch.float64) / nchans).to(torch.float32)
+        assert torch.equal(mean[t_chk:t_chk + 4096], m_ref), "zero_dm_mean_device differs from its definition"
+        chan = torch.arange(nchans, device="cuda")[None, None, :]
+        y = block[idx, chan].to(torch.float64) - mean[idx].to(torch.float64)
+        err = (out[rows, t_chk:t_chk + 64].to(torch.float64) - y.sum(dim=2)).abs()
+        assert bool((err <= nchans * 2.0 ** -24 * y.abs().sum(dim=2)).all()), "zero-DM sums differ from the definition"
+        zms, mms = timed(run_zero_dm), timed(run_mean)
+        zmed, mmed = float(np.median(zms)), float(np.median(mms))
+        extra.update({"zero_dm_call_ms_median": zmed, "zero_dm_call_ms_min": float(np.min(zms)),
+                      "zero_dm_call_ms_max": float(np.max(zms)), "zero_dm_ms_per_dm_trial": zmed / ndm,
+                      "zero_dm_to_plain_ratio": zmed / med,
+                      "zero_dm_workspace_bytes": zws.numel(),
+                      "row_mean_ms_median": mmed, "row_mean_block_gb_per_s": block_bytes / (mmed * 1e-3) / 1e9})
+    if args.stats:
+        acc = torch.zeros((2, nchans), dtype=torch.float64, device="cuda")
+        sws = torch.empty(engine.channel_stats_workspace_bytes(nsamp, nchans), dtype=torch.uint8, device="cuda")
+
+        def run_stats():
+            engine.channel_stats_device(block, acc, workspace=sws)
+
+        run_stats()
+        torch.cuda.synchronize()
+        part = block[:, :8].to(torch.int64)
+        assert torch.equal(acc[0, :8].to(torch.int64), part.sum(dim=0)), "channel sums differ"
+        assert torch.equal(acc[1, :8].to(torch.int64), (part * part).sum(dim=0)), "channel sums of squares differ"
+        sms = timed(run_stats)
+        smed = float(np.median(sms))
+        extra.update({"stats_ms_median": smed, "stats_ms_min": float(np.min(sms)), "stats_ms_max": float(np.max(sms)),
+                      "stats_block_gb_per_s": block_bytes / (smed * 1e-3) / 1e9})
     with open(os.path.join(REPO, "BENCH_r06.json")) as f:
         search_ms = json.load(f)["parsed"]["ms_per_step"] / 16.0
     result = {"nchans": nchans, "nsamp": nsamp, "ndm": ndm, "tsamp": tsamp, "dm_max": float(dms[-1]),
@@ -83,6 +143,9 @@ def main():
               "search_ms_per_trial_bench_r06_cfg2": search_ms,
               "dedisperse_to_search_ratio": (med / ndm) / search_ms,
               "source_digest": bench.source_digest(), "device": torch.cuda.get_device_name(0)}
+    if "zero_dm_ms_per_dm_trial" in extra:
+        extra["zero_dm_to_search_ratio"] = extra["zero_dm_ms_per_dm_trial"] / search_ms
+    result.update(extra)
     line = json.dumps(result)
     print(line)
     if args.out:
