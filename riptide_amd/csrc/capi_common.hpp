@@ -1,6 +1,7 @@
-// Shared by the C ABI's translation units (capi.cpp, host_api.cpp): the
+// Shared by the C ABI's translation units (capi_*.cpp, host_api.cpp): the
 // thread's error text and the entry points' exception barrier.  No HIP header.
 #pragma once
+#include <cstddef>
 #include <stdexcept>
 #include <string>
 
@@ -20,7 +21,7 @@ inline int fail(int code, const std::string& msg)
     return code;
 }
 
-struct HipError : std::runtime_error {   // a failed HIP runtime call (capi.cpp ck): RT_EHIP
+struct HipError : std::runtime_error {   // a failed HIP runtime call (capi_device.hpp ck): RT_EHIP
     using std::runtime_error::runtime_error;
 };
 
@@ -40,5 +41,7 @@ int guarded(F&& f)
         return fail(RT_EINTERNAL, "unknown error");
     }
 }
+
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 }  // namespace rt

@@ -1,0 +1,180 @@
+// C ABI, filterbank side: incoherent dedispersion, the zero-DM filter and the
+// channel statistics, with the shape limits of their kernels' 32-bit indices
+// and grids.
+#include "riptide_amd.h"
+
+#include <mutex>
+#include <stdexcept>
+#include <vector>
+
+#include "capi_device.hpp"
+#include "kernels.hpp"
+
+using namespace rt;
+
+namespace {
+
+void dedisp_check_shape(int dtype, size_t nsamp_blk, size_t nchans, size_t ndm, int64_t max_delay)
+{
+    if (dtype != RT_DEDISP_U8 && dtype != RT_DEDISP_I8 && dtype != RT_DEDISP_F32)
+        throw std::invalid_argument("dedisperse: unknown sample type code");
+    if (!nchans || !ndm) throw std::invalid_argument("dedisperse: nchans and ndm must be at least 1");
+    if (dtype != RT_DEDISP_F32 && nchans > RT_DEDISP_MAX_CHANS_8BIT)
+        throw std::invalid_argument("dedisperse: too many channels for an exact 8-bit sum (255 * nchans must be "
+                                    "below 2^24)");
+    if (nchans > 65535ull * 64) throw std::invalid_argument("dedisperse: too many channels");
+    if (ndm > 65535ull * 16) throw std::invalid_argument("dedisperse: too many DMs for one call");
+    if (nsamp_blk >= (1ull << 31)) throw std::invalid_argument("dedisperse: a block must be below 2^31 samples");
+    if (max_delay < 0 || (uint64_t)max_delay >= nsamp_blk)
+        throw std::invalid_argument("dedisperse: max_delay must be in [0, nsamp): the block is no longer than the "
+                                    "largest delay");
+}
+
+void dedisp_check_flags(uint32_t flags)
+{
+    if (flags & ~RT_DEDISP_ZERO_DM) throw std::invalid_argument("dedisperse: unknown flag bit");
+}
+
+// the statistics have no exactness limit on the channel count of 8-bit data
+void chanstats_check_shape(int dtype, size_t nsamp_blk, size_t nchans)
+{
+    dedisp_check_shape(RT_DEDISP_F32, nsamp_blk, nchans, 1, 0);
+    if (dtype != RT_DEDISP_U8 && dtype != RT_DEDISP_I8 && dtype != RT_DEDISP_F32)
+        throw std::invalid_argument("channel_stats: unknown sample type code");
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_dedisperse_workspace_bytes(int dtype, size_t nsamp_blk, size_t nchans, size_t* bytes)
+{
+    return rt_dedisperse_workspace_bytes_opt(dtype, nsamp_blk, nchans, 0u, bytes);
+}
+
+int rt_dedisperse_workspace_bytes_opt(int dtype, size_t nsamp_blk, size_t nchans, uint32_t flags, size_t* bytes)
+{
+    return guarded([&] {
+        if (!bytes) throw std::invalid_argument("dedisperse: bytes is NULL");
+        dedisp_check_flags(flags);
+        dedisp_check_shape(dtype, nsamp_blk, nchans, 1, 0);
+        *bytes = (size_t)dedisp_workspace_bytes(dtype, nsamp_blk, nchans, flags);
+        return RT_OK;
+    });
+}
+
+int rt_dedisperse_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans, const int32_t* d_delays,
+                         const uint8_t* d_mask, size_t ndm, int64_t max_delay, float* d_out, size_t out_stride,
+                         size_t out_offset, void* d_ws, size_t ws_bytes, void* stream)
+{
+    return rt_dedisperse_device_opt(d_block, dtype, nsamp_blk, nchans, d_delays, d_mask, ndm, max_delay, d_out,
+                                    out_stride, out_offset, d_ws, ws_bytes, stream, 0u);
+}
+
+int rt_dedisperse_device_opt(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans,
+                             const int32_t* d_delays, const uint8_t* d_mask, size_t ndm, int64_t max_delay,
+                             float* d_out, size_t out_stride, size_t out_offset, void* d_ws, size_t ws_bytes,
+                             void* stream, uint32_t flags)
+{
+    return guarded([&] {
+        dedisp_check_flags(flags);
+        dedisp_check_shape(dtype, nsamp_blk, nchans, ndm, max_delay);
+        const size_t nout = nsamp_blk - (size_t)max_delay;
+        if (out_offset > out_stride || nout > out_stride - out_offset)
+            throw std::invalid_argument("dedisperse: out_stride is shorter than out_offset plus the block's outputs");
+        if (!d_block || !d_delays || !d_out || !d_ws) throw std::invalid_argument("dedisperse: null device pointer");
+        if ((uintptr_t)d_ws % 16 || (dtype == RT_DEDISP_F32 && (uintptr_t)d_block % 4))
+            throw std::invalid_argument("dedisperse: misaligned device pointer");
+        if (ws_bytes < dedisp_workspace_bytes(dtype, nsamp_blk, nchans, flags))
+            throw std::invalid_argument("workspace too small");
+        ck(launch_dedisperse(d_block, dtype, (uint32_t)nsamp_blk, (uint32_t)nchans, d_delays, d_mask, (uint32_t)ndm,
+                             (uint32_t)max_delay, d_out + out_offset, out_stride, d_ws, flags, (hipStream_t)stream),
+           "dedisperse");
+        return RT_OK;
+    });
+}
+
+int rt_dedisperse(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays, const uint8_t* mask,
+                  size_t ndm, int64_t max_delay, float* out)
+{
+    return rt_dedisperse_opt(x, dtype, nsamp, nchans, delays, mask, ndm, max_delay, out, 0u);
+}
+
+int rt_dedisperse_opt(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
+                      const uint8_t* mask, size_t ndm, int64_t max_delay, float* out, uint32_t flags)
+{
+    return guarded([&] {
+        dedisp_check_flags(flags);
+        dedisp_check_shape(dtype, nsamp, nchans, ndm, max_delay);
+        if (!x || !delays || !out) throw std::invalid_argument("dedisperse: null buffer");
+        std::vector<int32_t> del(ndm * nchans);
+        for (size_t i = 0; i < del.size(); ++i) {
+            if (delays[i] < 0 || delays[i] > max_delay)
+                throw std::invalid_argument("dedisperse: a delay is outside [0, max_delay]");
+            del[i] = (int32_t)delays[i];
+        }
+        const size_t nout = nsamp - (size_t)max_delay;
+        const size_t in_bytes = nsamp * nchans * (dtype == RT_DEDISP_F32 ? 4 : 1);
+        const size_t ws_bytes = (size_t)dedisp_workspace_bytes(dtype, nsamp, nchans, flags);
+        std::lock_guard<std::mutex> lk(g_mu);
+        Context& c = context();
+        void* dx = c.buf[0].get(in_bytes);
+        float* dz = dev<float>(c, 1, ndm * nout);
+        void* dw = c.buf[2].get(ws_bytes);
+        int32_t* dd = dev<int32_t>(c, 3, del.size());
+        uint8_t* dm = mask ? dev<uint8_t>(c, 4, nchans) : nullptr;
+        h2d(dx, x, in_bytes, c.stream);
+        h2d(dd, del.data(), del.size() * 4, c.stream);
+        if (mask) h2d(dm, mask, nchans, c.stream);
+        ck(launch_dedisperse(dx, dtype, (uint32_t)nsamp, (uint32_t)nchans, dd, dm, (uint32_t)ndm,
+                             (uint32_t)max_delay, dz, nout, dw, flags, c.stream),
+           "dedisperse");
+        d2h(out, dz, ndm * nout * 4, c.stream);
+        sync(c.stream);
+        return RT_OK;
+    });
+}
+
+int rt_zero_dm_mean_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans, const uint8_t* d_mask,
+                           float* d_m, void* stream)
+{
+    return guarded([&] {
+        dedisp_check_shape(dtype, nsamp_blk, nchans, 1, 0);
+        if (!d_block || !d_m) throw std::invalid_argument("zero_dm_mean: null device pointer");
+        if ((uintptr_t)d_m % 4 || (dtype == RT_DEDISP_F32 && (uintptr_t)d_block % 4))
+            throw std::invalid_argument("zero_dm_mean: misaligned device pointer");
+        ck(launch_zero_dm_mean(d_block, dtype, (uint32_t)nsamp_blk, (uint32_t)nchans, d_mask, d_m,
+                               (hipStream_t)stream),
+           "zero_dm_mean");
+        return RT_OK;
+    });
+}
+
+int rt_channel_stats_workspace_bytes(size_t nsamp_blk, size_t nchans, size_t* bytes)
+{
+    return guarded([&] {
+        if (!bytes) throw std::invalid_argument("channel_stats: bytes is NULL");
+        chanstats_check_shape(RT_DEDISP_F32, nsamp_blk, nchans);
+        *bytes = (size_t)chanstats_workspace_bytes(nsamp_blk, nchans);
+        return RT_OK;
+    });
+}
+
+int rt_channel_stats_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans, double* d_acc,
+                            void* d_ws, size_t ws_bytes, void* stream)
+{
+    return guarded([&] {
+        chanstats_check_shape(dtype, nsamp_blk, nchans);
+        if (!d_block || !d_acc || !d_ws) throw std::invalid_argument("channel_stats: null device pointer");
+        if ((uintptr_t)d_acc % 8 || (uintptr_t)d_ws % 8 || (dtype == RT_DEDISP_F32 && (uintptr_t)d_block % 4))
+            throw std::invalid_argument("channel_stats: misaligned device pointer");
+        if (ws_bytes < chanstats_workspace_bytes(nsamp_blk, nchans))
+            throw std::invalid_argument("workspace too small");
+        ck(launch_channel_stats(d_block, dtype, (uint32_t)nsamp_blk, (uint32_t)nchans, d_acc, d_ws,
+                                (hipStream_t)stream),
+           "channel_stats");
+        return RT_OK;
+    });
+}
+
+}  // extern "C"

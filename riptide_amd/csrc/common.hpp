@@ -384,7 +384,7 @@ struct ConeArgs {
     // only unit issues the next trial's fill before storing the current one
     uint32_t trials_per_wg;
 };
-constexpr uint32_t kConeTrialsPerWg = 16;  // default trials per workgroup (capi.cpp cone_trials_per_wg)
+constexpr uint32_t kConeTrialsPerWg = 16;  // default trials per workgroup (capi_pgram.cpp cone_trials_per_wg)
 // workgroups per item of a cone launch
 RT_HD inline uint32_t cone_trial_groups(uint32_t batch, uint32_t tpw)
 {

@@ -44,7 +44,7 @@ struct HCand {
     double freq, snr, ducy, dm;
 };
 
-// rt_htest_params, by another name (capi.cpp asserts the layout)
+// rt_htest_params, by another name (capi_harmonic.cpp asserts the layout)
 struct HParams {
     double tobs, band, phase_distance_max, dm_distance_max, snr_distance_max;
     uint32_t denom_max;

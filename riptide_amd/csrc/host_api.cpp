@@ -1,13 +1,17 @@
 // The C ABI's host-only entry points: what the planner decides for a set of
 // search parameters, read back without a device.  Each is checked_params ->
-// planner (plan.hpp) -> copy out; rt_plan_create (capi.cpp) uploads the same
-// plan_periodogram result.  No HIP header (`make asan` builds this file as is).
+// planner (plan.hpp) -> copy out; rt_plan_create (capi_pgram.cpp) uploads the
+// same plan_periodogram result.  Likewise the fold's shape and workspace
+// (fold_host.hpp) and the dereddening workspace (dered_host.hpp).  No HIP
+// header (`make asan` builds this file as is).
 #include "riptide_amd.h"
 
 #include <algorithm>
 #include <stdexcept>
 
 #include "capi_common.hpp"
+#include "dered_host.hpp"
+#include "fold_host.hpp"
 #include "peaks_host.hpp"
 #include "plan.hpp"
 
@@ -169,6 +173,33 @@ int rt_find_peaks_host(const float* snrs, size_t length, size_t num_widths, cons
         for (size_t iw = 0; iw < num_widths; ++iw)
             counts[iw] = find_peaks_column(snrs + iw, num_widths, length, logf, freqs, coeffs + iw * ncoef,
                                            (uint32_t)ncoef, smin, radius, rows + iw * cap, snr + iw * cap, cap);
+        return RT_OK;
+    });
+}
+
+int rt_fold_shape(size_t size, double factor, size_t bins, size_t subints, size_t* m, size_t* rows)
+{
+    return guarded([&] {
+        const FoldShape s = fold_shape(size, factor, bins, subints);
+        if (m) *m = s.m;
+        if (rows) *rows = s.rows;
+        return RT_OK;
+    });
+}
+
+int rt_fold_workspace_bytes(size_t size, const rt_fold_spec* specs, size_t nspecs, size_t* bytes)
+{
+    return guarded([&] {
+        const size_t need = fold_plan(size, specs, nspecs).ws_bytes;
+        if (bytes) *bytes = need;
+        return RT_OK;
+    });
+}
+
+int rt_deredden_workspace_bytes(size_t size, size_t ws, size_t minpts, size_t batch, size_t* bytes)
+{
+    return guarded([&] {
+        *bytes = dered_ws_bytes(dered_geom(size, ws, minpts, batch, true));
         return RT_OK;
     });
 }

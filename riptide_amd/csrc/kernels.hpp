@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
+#include "dered_host.hpp"
+#include "fold_host.hpp"
 #include "harmonic.hpp"
 
 namespace rt {
@@ -53,9 +55,9 @@ hipError_t launch_deredden_subtract(const float* x, uint64_t n, const float* rme
                                     uint64_t out_stride, uint32_t batch, hipStream_t s, double* slopes = nullptr);
 // dereddening + normalisation with the normalisation's statistics summed by
 // the dereddening kernel (no read pass of their own).  Applies when
-// dered_norm_fusable(); partials: batch * 2 * dered_norm_blocks(n) doubles,
+// dered_norm_fusable(); partials: batch * 2 * dered_norm_blocks(n) doubles
+// (dered_host.hpp),
 // stats: 2 * batch doubles.
-inline uint64_t dered_norm_blocks(uint64_t n) { return (n + 4095) / 4096; }   // 4096 samples per block
 bool dered_norm_fusable(const float* x, uint64_t n, uint64_t n_lo, uint32_t factor, const float* out,
                         uint64_t x_stride, uint64_t out_stride);
 hipError_t launch_deredden_normalise(const float* x, uint64_t n, const float* rmed_lo, uint64_t n_lo,
@@ -70,33 +72,7 @@ hipError_t launch_rollback(const float* x, uint64_t n, uint64_t shift, const flo
 hipError_t launch_circular_prefix_sum(const float* x, uint64_t n, uint64_t nsum, float* out, hipStream_t s);
 
 // fold_kernels.hip
-// What a candidate's result is: the (m, bins) row array itself, its sum over
-// the rows, or the row array downsampled along its first axis.
-constexpr uint32_t kFoldRows = 0, kFoldProfile = 1, kFoldVertical = 2;
-
-// One candidate of a batched fold (folding.py:19-81).  The same descriptor
-// serves both kernels: first_block is the candidate's first block of the
-// launch the table belongs to (the rows table holds every candidate, the
-// subints table those whose mode is not kFoldRows).
-struct FoldCand {
-    double f;             // period / bins / tsamp
-    double vf;            // kFoldVertical: m / subints
-    uint64_t src_off;     // float offset of the candidate's series in d_data
-    uint64_t n_rows_out;  // m * bins
-    uint64_t rows_off;    // float offset of the row array: in d_out (kFoldRows) or in the workspace rows
-    uint64_t out_off;     // float offset of the result in d_out
-    float scale;          // (float)pow(m * f, -0.5)
-    uint32_t bins;
-    uint32_t m;           // whole periods
-    uint32_t sub_rows;    // rows of the subints kernel's output (1 for a profile)
-    uint32_t mode;
-    uint32_t rows_in_ws;
-    uint32_t first_block;
-    uint32_t per_block;   // rows kernel: outputs per block (ds_per_block, or 256 unstaged)
-    uint32_t staged;      // rows kernel: the block's input span is staged in LDS
-    uint32_t pad;
-};
-
+// the candidate descriptor FoldCand and its modes: fold_host.hpp
 hipError_t launch_fold_rows(const float* data, uint64_t n_in, const FoldCand* d_cands, uint32_t num_cands,
                             uint32_t total_blocks, float* out, float* rows_ws, hipStream_t s);
 hipError_t launch_fold_subints(const FoldCand* d_cands, uint32_t num_cands, uint32_t total_blocks, float* out,

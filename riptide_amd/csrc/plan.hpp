@@ -72,7 +72,7 @@ struct ExecPlan {
     uint32_t max_width = 0;          // the widest boxcar the plan was built for (0: unknown; the final units' S/N kind)
     // scratch banks: 2 = odd transform groups use a second copy of the
     // scratch (offset bank_floats), so two groups can run at once on two
-    // streams (capi.cpp run_cone_launches: co-scheduling)
+    // streams (capi_pgram.cpp run_cone_launches: co-scheduling)
     uint32_t banks = 1;
     uint64_t bank_floats = 0;
     uint32_t groups = 0;
@@ -192,7 +192,7 @@ uint32_t checked_plan_widths(const uint64_t* w, size_t nw, size_t bmin);
 // Environment knobs of plan_periodogram's callers: the per-trial scratch budget
 // of one transform group (RIPTIDE_AMD_SCRATCH_MFLOATS, millions of floats per
 // ping/pong buffer) and the scratch banks (RIPTIDE_AMD_COSCHED=1: 2, the
-// groups co-scheduled on two streams, capi.cpp run_cone_launches).
+// groups co-scheduled on two streams, capi_pgram.cpp run_cone_launches).
 uint64_t scratch_budget_floats();
 uint32_t cosched_banks();
 

@@ -698,7 +698,7 @@ def test_full_config_every_row(rt, oracle, golden_full, monkeypatch, name, budge
 
 def test_single_stream_matches_two_streams_cfg2(rt, golden_full, monkeypatch):
     """The two-stream slot-width chains (the default for plans with more than
-    one slot width, capi.cpp run_cone_launches) against every launch on the
+    one slot width, capi_pgram.cpp run_cone_launches) against every launch on the
     caller's stream in plan order (RIPTIDE_AMD_SINGLE_STREAM=1): bit-identical
     S/N on the benchmarked cfg2 schedule, golden input and its reverse."""
     import torch

@@ -557,6 +557,29 @@ def test_asan_schedule_check():
             assert int(r.stdout.split("launches=")[1].split()[0]) <= 16, r.stdout
 
 
+@pytest.mark.parametrize("mode", ["fold", "dered", "harmonic"])
+def test_asan_host_check(mode):
+    """The host planning the C ABI's device files rely on, under
+    AddressSanitizer + UBSan (build/asan/host_check, g++, no HIP), every array
+    a heap block of exact size.  fold: the accept and EINVAL cases of
+    test_fold_host.py and a table of all three modes with staged and unstaged
+    factors, every candidate's rows and result inside the reported workspace
+    and output.  dered: the four workspace regions over (size, width,
+    min_points, batch), scrunch factor 1 and above.  harmonic: the tile
+    resolution against the plain rank-order loop for n in {2, 63, 64, 65, 130}
+    and 1, 7, n - 1 rows per tile, with near pairs, a tile past the near cap,
+    and out-of-range near pairs (the library's own error)."""
+    import subprocess
+    subprocess.check_call(["make", "-s", "-C", os.path.join(REPO, "riptide_amd", "csrc"), "asan"])
+    exe = os.path.join(REPO, "build", "asan", "host_check")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=99",
+               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    r = subprocess.run([exe, mode], env=env, capture_output=True, text=True, timeout=300)
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
+    assert r.returncode == 0, (r.returncode, r.stdout[-3000:], r.stderr[-3000:])
+    assert r.stdout.strip().endswith(f"host_check {mode} OK")
+
+
 def test_bench_pmc_summary_matches_sources(tmp_path, monkeypatch):
     """bench.pmc_traffic takes the newest PMC summary measured on the current
     kernel sources (csrc_sha == source_digest()), not merely the newest file
