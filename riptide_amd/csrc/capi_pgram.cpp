@@ -176,7 +176,7 @@ void cone_launch(const DevicePlan& P, const Launch& L, ConeArgs a, uint32_t batc
     }
     ProfScope prof(s, 0, g_prof.on && prof_each);
     prof.add(L.alg_bytes * batch, L.moved_bytes * batch);
-    ck(launch_cone(a, L.smax, L.rw, L.wide_snr != 0, L.snr, s), "cone_kernel");
+    ck(launch_cone(a, L.smax, L.wide_snr != 0, L.snr, s), "cone_kernel");
     prof.finish();
 }
 

@@ -49,7 +49,7 @@ constexpr int kMaxLevels = 11;              // merge levels of any unit (whole u
 constexpr int kMaxRanges = (1 << (kMaxTileLevels + 1)) - 1;
 constexpr int kMaxWidths = 32;              // boxcar widths handled by the fused S/N epilogue
 constexpr int kSnrChunk = 17;               // S/N epilogue: columns per lane held in registers
-// S/N epilogue (ffa_kernels.hip snr_rows): widths <= kSnrWin from a
+// S/N epilogue (cone_snr.hpp snr_rows): widths <= kSnrWin from a
 // register window; chunk columns per lane of the register-window path
 constexpr int kSnrWin = 12;
 constexpr int kSnrMaxChunk = 17;
@@ -75,7 +75,7 @@ RT_HD constexpr int snr_group(int p)
     while (G < 64 && ((((p + G - 1) / G) | 1) > kSnrMaxChunk)) G <<= 1;
     return G;
 }
-// Segmented S/N (ffa_kernels.hip snr_segments): a final level of <= 64 rows
+// Segmented S/N (cone_snr.hpp snr_segments): a final level of <= 64 rows
 // of 240-264 bins, widths <= 9, one row per lane, each of the 8 waves a
 // segment of kSnrSegCols columns.  Row r lies in an LDS slot of
 // kSnrSegStride floats (odd: 64 rows on distinct banks) at offset
@@ -144,7 +144,7 @@ constexpr int kSlotWords = 544;             // LDS area of a unit's slot tables
 // single steps) and the slot word
 RT_HD constexpr bool resolved_slots(int smax) { return smax == 4 || smax == 5; }
 constexpr int kAuxMetaWords = kBlobHeader + kDescEntries + kMaxRows + kSlotWords;   // the metadata area
-// 4-slot roll table (ffa_kernels.hip row_terms_lut): 2 words per entry
+// 4-slot roll table (cone_merge.hpp row_terms_lut): 2 words per entry
 // x < 256 + 64 at the end of the metadata area, which it extends by kLutPad
 // words (the workgroup's LDS stays inside the same 512-byte granule); every
 // 4-slot row-slot unit's blob LDS part must end at or before kLut4Off
@@ -166,7 +166,7 @@ RT_HD inline int pack_blob_words(int entries, int nb) { return (kBlobHeader + en
 
 // Merge variant for rows of p phase bins: slots per row rounded up to an
 // instantiated width (1..5, 8, 11, 16, 22, 45), or kPack2 for p <= 32 (short rows:
-// (row, 8-bin segment) tasks, ffa_kernels.hip merge_step_tasks); 0 if p is
+// (row, 8-bin segment) tasks, cone_merge.hpp merge_step_tasks); 0 if p is
 // too wide for the LDS engine.  The value is the cone kernel's template
 // argument and launch bucket.
 constexpr int kPack2 = 64;
@@ -185,7 +185,7 @@ RT_HD inline int merge_slots(uint32_t p)
 }
 
 // Row stride of the merge levels above the fill in the short-row variant
-// (kPack2, ffa_kernels.hip merge_step_tasks).  The interleaved tasks (lane
+// (kPack2, cone_merge.hpp merge_step_tasks).  The interleaved tasks (lane
 // (row, segment s) takes bins s + segs*k, k < 8) write up to 8*segs bins per
 // row, so the stride is >= 8*segs; for 16 <= p <= 32 it is the stride with
 // the fewest LDS bank conflicts of those steps' reads over the cfg4
@@ -232,7 +232,7 @@ RT_HD inline int lds_row_capacity(uint32_t p, int smax)
 
 RT_HD inline int lds_row_capacity(uint32_t p) { return lds_row_capacity(p, merge_slots(p)); }
 
-// ---- downsampling ladder (ffa_kernels.hip downsample_ladder_kernel /
+// ---- downsampling ladder (ladder_kernels.hip downsample_ladder_kernel /
 // downsample_fused_kernel; planned on the host: plan.hpp plan_ladder)
 constexpr uint32_t kDsSpanFloats = 4096;   // LDS input stage of the ladder kernels (16 KiB)
 constexpr uint32_t kDsFusedMargin = 512;   // fused ladder: staged floats past the span (rungs with ceil(f) + 2 <= margin)

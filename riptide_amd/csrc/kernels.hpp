@@ -9,7 +9,7 @@
 
 namespace rt {
 
-// ffa_kernels.hip
+// ladder_kernels.hip
 hipError_t launch_downsample_ladder(const float* x, uint64_t n_in, uint64_t x_stride,
                                     const DsRung* d_rungs, uint32_t num_rungs, uint32_t total_blocks,
                                     float* out, uint64_t out_stride, uint32_t batch, hipStream_t s);
@@ -19,9 +19,10 @@ hipError_t launch_downsample_fused(const float* x, uint64_t n_in, uint64_t x_str
                                    uint32_t num_rungs, uint32_t margin, float* out, uint64_t out_stride,
                                    uint32_t batch, hipStream_t s);
 
+// ffa_kernels.hip (the cone kernel's parts: cone_unit.hpp, cone_merge.hpp, cone_snr.hpp)
 // smax: merge_slots() bucket covering every transform of the launch
-hipError_t launch_cone(const ConeArgs& args, uint32_t smax, uint32_t rw, bool wide_snr, uint32_t snr,
-                       hipStream_t s);   // grid (num_items, batch); rw, wide_snr, snr (kSnrNone / kSnrRows / kSnrSeg): the Launch's
+hipError_t launch_cone(const ConeArgs& args, uint32_t smax, bool wide_snr, uint32_t snr,
+                       hipStream_t s);   // grid (num_items, batch); wide_snr, snr (kSnrNone / kSnrRows / kSnrSeg): the Launch's
 hipError_t launch_ffa_level(const float* in, float* out, const uint2* d_nodes, uint32_t num_nodes,
                             uint32_t rows, uint32_t p, hipStream_t s);
 

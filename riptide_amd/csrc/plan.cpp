@@ -298,7 +298,7 @@ static bool wide_snr(const FfaXform& X, int smax, bool snr_epilogue, uint32_t ma
     return true;
 }
 
-// Final tiles of the segmented S/N (ffa_kernels.hip snr_segments): one block
+// Final tiles of the segmented S/N (cone_snr.hpp snr_segments): one block
 // of kSnrSegRows rows; off with the kernel's feature bit
 // (RIPTIDE_AMD_CONE_FLAGS without kConeSnrSeg, A/B).
 static bool seg_snr(const FfaXform& X, int smax, bool snr_epilogue, uint32_t max_width)
@@ -453,7 +453,7 @@ void build_exec_plan(const std::vector<FfaXform>& xforms, bool snr_epilogue, uin
     std::vector<int> smax_of(out.items.size(), 0);
     for (const Launch& L : out.launches) {
         // row-slot tables for the kernel instances that use them (SMAX <= 5)
-        const int rw = L.smax <= 5 ? (L.rw ? (int)L.rw : merge_rows_per_wave((int)L.smax)) : 0;
+        const int rw = L.smax <= 5 ? merge_rows_per_wave((int)L.smax) : 0;
         for (uint32_t i = L.first; i < L.first + L.count; ++i) {
             slot_rw[i] = rw;
             packed[i] = L.smax == (uint32_t)kPack2;
@@ -1018,7 +1018,7 @@ void validate_exec_plan(const ExecPlan& ex, bool snr_epilogue)
             } else if (it.mode == kModeTile && (need.entries > kDescEntries || it.pad == kNoBlob)) {
                 throw std::runtime_error("schedule: tile descriptor table exceeds its LDS area");
             }
-            // the 4/5-slot instances run only row-slot steps (ffa_kernels.hip
+            // the 4/5-slot instances run only row-slot steps (cone_merge.hpp
             // merge_levels): every unit with a merge level has its slot tables
             if (resolved_slots((int)L.smax) && it.levels > 0 &&
                 (it.pad == kNoBlob || ex.blob[it.pad + kHdrSlotWords] == 0))
@@ -1035,7 +1035,7 @@ void validate_exec_plan(const ExecPlan& ex, bool snr_epilogue)
                               it.mode == kModeTile ? (int)(it.s1 - it.s0) : (int)it.node_size))
                 throw std::runtime_error("schedule: segmented S/N on a unit outside its shapes");
             // the launch's kernel instance stages enough register rows for every level
-            const int rw = L.rw ? (int)L.rw : merge_rows_per_wave((int)L.smax);
+            const int rw = merge_rows_per_wave((int)L.smax);
             if (it.pad != kNoBlob) {
                 if ((size_t)it.pad + kBlobHeader > ex.blob.size()) throw std::runtime_error("schedule: blob outside the plan");
                 validate_blob(it, X.p, (int)L.smax, rw, ex.blob.data() + it.pad);

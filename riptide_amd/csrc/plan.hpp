@@ -52,7 +52,6 @@ struct Launch {
     uint32_t first = 0, count = 0;   // item range
     uint32_t group = 0, pass = 0;
     uint32_t smax = 0;               // cone kernel variant: merge_slots() of every transform in the launch
-    uint32_t rw = 0;                 // register rows per wave of the variant (0: merge_rows_per_wave(smax))
     uint32_t wide_snr = 0;           // final units whose S/N reads wide widths as plain LDS windows (WIDE variant)
     // S/N kind of every unit (common.hpp): kSnrNone, a merge-only pass;
     // kSnrRows / kSnrSeg, a final pass with the row-group / segmented fused S/N

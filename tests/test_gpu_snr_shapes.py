@@ -1,6 +1,6 @@
 """The boxcar S/N (snr.hpp:37-65) at every row shape its kernels specialise
 on.  Fused (the cone kernel's epilogue: snr_epilogue / snr_rows / snr_segments
-in ffa_kernels.hip): bins ranges astride every breakpoint of the slot-width
+in cone_snr.hpp): bins ranges astride every breakpoint of the slot-width
 variant (merge_slots), the lane-group size (snr_group) and the chunk template,
 on final tiles and on whole units, with width lists on both sides of the
 register window (kSnrWin) and the chunk (kSnrMaxChunk), with every select

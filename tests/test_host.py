@@ -156,8 +156,8 @@ def test_ladder_oracle_cases_cover_the_kernel():
     classes the ladder kernels branch on, by the plans' own layout: a
     condition on the case list -- if a class goes missing, the list is what
     to fix."""
-    src = open(os.path.join(REPO, "riptide_amd", "csrc", "ffa_kernels.hip")).read()
-    assert int(re.search(r"^#define RT_DS_PAIRS (\d+)$", src, re.M).group(1)) == inputs.LADDER_SPAN
+    src = open(os.path.join(REPO, "riptide_amd", "csrc", "ladder_kernels.hip")).read()
+    assert int(re.search(r"^constexpr uint32_t kDsPairSpan = (\d+);$", src, re.M).group(1)) == inputs.LADDER_SPAN
     names = [c["name"] for c in inputs.LADDER_ORACLE_CASES]
     assert len(set(names)) == len(names)
     lays = {c["name"]: _layout(c["n"], c) for c in inputs.LADDER_ORACLE_CASES}
@@ -309,7 +309,7 @@ def test_snr_shape_sweep_schedules(lib):
 # Restatement of the row-shape tables the fused S/N is specialised by:
 # merge_slots and snr_group (riptide_amd/csrc/common.hpp), the short rows'
 # 4-lane groups and the chunk templates snr_epilogue picks
-# (riptide_amd/csrc/ffa_kernels.hip: kSnrShortG, snr_rows<5|9|17, G>, the
+# (riptide_amd/csrc/cone_snr.hpp: kSnrShortG, snr_rows<5|9|17, G>, the
 # one-wave-per-row loop past 64 x 17 bins), and snr_seg_ok's 240-264 bins.
 def _merge_slots(p):
     if p <= 32:

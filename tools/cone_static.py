@@ -6,7 +6,7 @@ kernel descriptors' metadata, code size, and counts of VALU instructions,
 lane reads / writes (the SGPR-spill traffic) and s_nop in the body.
 
 usage: python tools/cone_static.py listing.s [out.json]
-With --spills INSTANCE (e.g. "4,0,0,2": SMAX,RWT,WIDE,SNR) prints, for that
+With --spills INSTANCE (e.g. "4,0,2": SMAX,WIDE,SNR) prints, for that
 instance, every basic block of the listing that holds lane reads / writes,
 with their counts and the block's instruction count.
 """
@@ -16,7 +16,7 @@ import sys
 
 
 def instance(sym):
-    """Template arguments of a mangled cone_kernel instance: 'SMAX,RWT,WIDE,SNR'
+    """Template arguments of a mangled cone_kernel instance: 'SMAX,WIDE,SNR'
     (integral arguments only: L<type><value>E)."""
     return ",".join(re.findall(r"L[a-z](\d+)E", sym.split("cone_kernel", 1)[1]))
 

@@ -1,5 +1,5 @@
 // Host tool: final-pass (S/N) units of a config's schedule -- output rows per
-// unit and whether they fit the wide S/N stride (ffa_kernels.hip
+// unit and whether they fit the wide S/N stride (common.hpp
 // snr_wide_stride) for a widest boxcar wmax.
 // hipcc -O2 -I riptide_amd/csrc tools/final_rows.cpp riptide_amd/csrc/plan.cpp -o /tmp/final_rows
 // /tmp/final_rows N TSAMP PMIN PMAX BMIN BMAX WMAX

@@ -26,7 +26,7 @@ int main(int argc, char** argv)
     double issued = 0, useful = 0, ideal = 0, steps = 0, units = 0;
     std::map<int, double> by_rw_issued, by_rw_useful;
     for (const Launch& L : ex.launches) {
-        const int rw = L.rw ? (int)L.rw : merge_rows_per_wave((int)L.smax);
+        const int rw = merge_rows_per_wave((int)L.smax);
         const int S = slot_count((int)L.smax);
         for (uint32_t i = L.first; i < L.first + L.count; ++i) {
             const ConeItem& it = ex.items[i];

@@ -38,7 +38,7 @@ int main(int argc, char** argv)
     uint64_t steps = 0, kinds[4] = {};
     for (const Launch& L : ex.launches) {
         if (L.smax != 4 && L.smax != 5) continue;
-        const int rw = L.rw ? (int)L.rw : merge_rows_per_wave((int)L.smax);
+        const int rw = merge_rows_per_wave((int)L.smax);
         const int Q = (rw + 1) / 2;
         for (uint32_t k = L.first; k < L.first + L.count; ++k) {
             const ConeItem& it = ex.items[k];
