@@ -395,6 +395,32 @@ int rt_flag_harmonics_stats(uint64_t* tiles, uint64_t* near_pairs, uint64_t* hos
 #define RT_DEDISP_F32 2
 /* 8-bit sums are exact integers in float32 while 255 * nchans < 2^24 */
 #define RT_DEDISP_MAX_CHANS_8BIT 65793
+/* Packed sample types, a range of their own (the code is 0x100 + nbits).  x /
+ * d_block is then bytes, [nsamp, row_bytes] with row_bytes = nchans * nbits /
+ * 8 (nchans * nbits must be a multiple of 8: RT_EINVAL "rows are not a whole
+ * number of bytes" otherwise), and only byte-aligned.  One definition for
+ * host and device:
+ *   1, 2, 4 bit  unsigned, SIGPROC's packing, least significant bits first:
+ *                channel c of a row is
+ *                (row[(c * nbits) >> 3] >> ((c * nbits) & 7)) & (2^nbits - 1)
+ *   16 bit       unsigned, little-endian: row[2c] | row[2c + 1] << 8
+ * (a most-significant-bit-first packing is not supported).  Every
+ * rt_dedisperse*, rt_zero_dm_mean_* and rt_channel_stats_* entry point takes
+ * these codes.  1/2/4-bit data is summed as 8-bit data is: exact integers,
+ * at most RT_DEDISP_MAX_CHANS_8BIT channels.  16-bit data is converted
+ * exactly and summed in float32 in channel order, as float data is (so exact
+ * up to 256 channels; no channel cap).  With RT_DEDISP_ZERO_DM, S[t] is an
+ * exact integer for all four widths, so m and y are reproducible bit for bit.
+ * The statistics are integers, exact below 2^53. */
+#define RT_DEDISP_U1  0x101
+#define RT_DEDISP_U2  0x102
+#define RT_DEDISP_U4  0x104
+#define RT_DEDISP_U16 0x110
+/* Host only: *bytes = the bytes of one time sample's row of nchans channels,
+ * for the three plain codes (nchans, nchans, 4 * nchans) and the packed ones
+ * (nchans * nbits / 8).  RT_EINVAL for an unknown code, nchans == 0, a NULL
+ * bytes, or packed rows that are not a whole number of bytes. */
+int rt_dedisp_row_bytes(int dtype, size_t nchans, size_t* bytes);
 
 /* Host only, no device: the delay table, in samples, against the highest
  * frequency f_ref = max(freqs_mhz).  In float64, in this order:
@@ -417,7 +443,9 @@ int rt_dedisperse_delays(const double* freqs_mhz, size_t nchans, const double* d
 int rt_dedisperse_host(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
                        const uint8_t* mask, size_t ndm, int64_t max_delay, size_t nout, float* out);
 /* Device workspace bytes of rt_dedisperse_device for a block of nsamp_blk
- * samples: the block transposed to channel-major, rows padded to 16 bytes. */
+ * samples: the block transposed to channel-major, rows padded to 16 bytes
+ * (1/2/4-bit data: the size of 8-bit data of the same shape, the rows are
+ * unpacked; 16-bit data: the size of float32 data). */
 int rt_dedisperse_workspace_bytes(int dtype, size_t nsamp_blk, size_t nchans, size_t* bytes);
 /* One resident block of nsamp_blk time samples, d_block [nsamp_blk, nchans]:
  * writes d_out[d * out_stride + out_offset + t] for t in [0, nsamp_blk -

@@ -21,7 +21,7 @@ from .time_series import TimeSeries
 from .peak_cluster import PeakCluster
 from .candidate import Candidate, build_candidates
 from .harmonic_testing import apply_candidate_filters, flag_harmonics, hdiag, htest
-from .reading import Filterbank
+from .reading import Filterbank, PackedFilterbank, open_filterbank
 from .dispatch import search_filterbank
 from . import dedispersion, rfi
 
@@ -30,5 +30,6 @@ __all__ = [
     "TimeSeries", "Periodogram", "Metadata", "ffa_search", "ffa1", "ffa2", "ffafreq", "ffaprd",
     "generate_signal", "downsample", "boxcar_snr", "find_peaks", "running_median",
     "fast_running_median", "generate_width_trials", "cluster1d", "Peak", "Filterbank", "search_filterbank",
+    "PackedFilterbank", "open_filterbank",
     "dedispersion", "rfi",
 ]

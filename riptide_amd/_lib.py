@@ -91,6 +91,8 @@ _SIGNATURES = {
     "rt_hdiag_pairs": (_c_i, [_vp, _vp, _vp, _vp, _c_sz, _vp, _vp, _c_sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rt_flag_harmonics": (_c_i, [_vp, _vp, _vp, _vp, _c_sz, _vp, _c_sz, _vp, _vp, _vp]),
     "rt_flag_harmonics_stats": (_c_i, [_pu64, _pu64, _pu64, _pd]),
+    # dtype, nchans, bytes
+    "rt_dedisp_row_bytes": (_c_i, [_c_i, _c_sz, _psz]),
     # freqs, nchans, dms, ndm, tsamp, kdm, delays (int64), max_delay
     "rt_dedisperse_delays": (_c_i, [_vp, _c_sz, _vp, _c_sz, _c_d, _c_d, _vp, ctypes.POINTER(ctypes.c_int64)]),
     # x, dtype, nsamp, nchans, delays (int64), mask, ndm, max_delay, nout, out

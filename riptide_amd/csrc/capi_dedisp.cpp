@@ -14,17 +14,37 @@ using namespace rt;
 
 namespace {
 
+bool known_dtype(int dtype)
+{
+    return dtype == RT_DEDISP_U8 || dtype == RT_DEDISP_I8 || dtype == RT_DEDISP_F32 || dedisp_packed_bits(dtype);
+}
+
+// float and 16-bit data are summed in float32; everything else as integers
+bool integer_sum(int dtype) { return dtype != RT_DEDISP_F32 && dtype != RT_DEDISP_U16; }
+
+// bytes of a row of the block (rt_dedisp_row_bytes: throws for packed rows
+// that are not whole bytes)
+size_t row_bytes_of(int dtype, size_t nchans)
+{
+    size_t rb = 0;
+    if (rt_dedisp_row_bytes(dtype, nchans, &rb) != RT_OK) throw std::invalid_argument(rt_last_error());
+    return rb;
+}
+
 void dedisp_check_shape(int dtype, size_t nsamp_blk, size_t nchans, size_t ndm, int64_t max_delay)
 {
-    if (dtype != RT_DEDISP_U8 && dtype != RT_DEDISP_I8 && dtype != RT_DEDISP_F32)
-        throw std::invalid_argument("dedisperse: unknown sample type code");
+    if (!known_dtype(dtype)) throw std::invalid_argument("dedisperse: unknown sample type code");
     if (!nchans || !ndm) throw std::invalid_argument("dedisperse: nchans and ndm must be at least 1");
-    if (dtype != RT_DEDISP_F32 && nchans > RT_DEDISP_MAX_CHANS_8BIT)
+    if (integer_sum(dtype) && nchans > RT_DEDISP_MAX_CHANS_8BIT)
         throw std::invalid_argument("dedisperse: too many channels for an exact 8-bit sum (255 * nchans must be "
                                     "below 2^24)");
     if (nchans > 65535ull * 64) throw std::invalid_argument("dedisperse: too many channels");
     if (ndm > 65535ull * 16) throw std::invalid_argument("dedisperse: too many DMs for one call");
     if (nsamp_blk >= (1ull << 31)) throw std::invalid_argument("dedisperse: a block must be below 2^31 samples");
+    // packed rows: whole bytes, and nsamp_blk * row_bytes inside the kernels' 64-bit byte offsets
+    // (row_bytes < 2^23 by the channel limit above)
+    if (dedisp_packed_bits(dtype) && row_bytes_of(dtype, nchans) > (~0ull >> 1) / (nsamp_blk ? nsamp_blk : 1))
+        throw std::invalid_argument("dedisperse: the block's bytes overflow a 64-bit offset");
     if (max_delay < 0 || (uint64_t)max_delay >= nsamp_blk)
         throw std::invalid_argument("dedisperse: max_delay must be in [0, nsamp): the block is no longer than the "
                                     "largest delay");
@@ -39,8 +59,8 @@ void dedisp_check_flags(uint32_t flags)
 void chanstats_check_shape(int dtype, size_t nsamp_blk, size_t nchans)
 {
     dedisp_check_shape(RT_DEDISP_F32, nsamp_blk, nchans, 1, 0);
-    if (dtype != RT_DEDISP_U8 && dtype != RT_DEDISP_I8 && dtype != RT_DEDISP_F32)
-        throw std::invalid_argument("channel_stats: unknown sample type code");
+    if (!known_dtype(dtype)) throw std::invalid_argument("channel_stats: unknown sample type code");
+    if (dedisp_packed_bits(dtype)) row_bytes_of(dtype, nchans);
 }
 
 }  // namespace
@@ -114,7 +134,7 @@ int rt_dedisperse_opt(const void* x, int dtype, size_t nsamp, size_t nchans, con
             del[i] = (int32_t)delays[i];
         }
         const size_t nout = nsamp - (size_t)max_delay;
-        const size_t in_bytes = nsamp * nchans * (dtype == RT_DEDISP_F32 ? 4 : 1);
+        const size_t in_bytes = nsamp * row_bytes_of(dtype, nchans);
         const size_t ws_bytes = (size_t)dedisp_workspace_bytes(dtype, nsamp, nchans, flags);
         std::lock_guard<std::mutex> lk(g_mu);
         Context& c = context();

@@ -10,8 +10,9 @@
 // Runs the edge shapes (1, 3, 37, 64, 65 channels, both band orders, DM 0,
 // nout = nsamp - max_delay and nout = 1, with and without a mask, the three
 // sample types) against a recount, the same shapes with RT_DEDISP_ZERO_DM
-// and through the statistics, then every error return.  Exit status 0 iff all
-// agree.
+// and through the statistics, the packed sample types (1, 2, 4 and 16 bit:
+// whole-byte rows of 1 to 18 bytes, blocks that end on the array's last byte),
+// then every error return.  Exit status 0 iff all agree.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -221,6 +222,138 @@ void run_rfi_shape(size_t nchans, int dtype, bool masked, bool single_out)
     }
 }
 
+// Packed sample types: a block of exactly nsamp * row_bytes heap bytes (the
+// last row ends on the array's last byte) through the plain sum, the zero-DM
+// form, the mean series and the statistics, against a restatement that
+// extracts the bits sample by sample.
+void run_packed_shape(int nbits, size_t nchans, bool masked)
+{
+    const int dtype = 0x100 + nbits;
+    const double tsamp = 1e-3, kdm = 1.0 / 2.41e-4;
+    const size_t ndm = 3;
+    std::vector<double> freqs(nchans), dms{0.0, 50.0, 12.5};
+    for (size_t c = 0; c < nchans; ++c) freqs[c] = 400.0 - 32.0 / (double)nchans * (double)c;
+    std::vector<int64_t> delays(ndm * nchans);
+    int64_t max_delay = -1;
+    expect(rt_dedisperse_delays(freqs.data(), nchans, dms.data(), ndm, tsamp, kdm, delays.data(), &max_delay) == RT_OK,
+           "delays");
+    const size_t nsamp = (size_t)max_delay + 41, nout = nsamp - (size_t)max_delay;
+    size_t rb = 0;
+    expect(rt_dedisp_row_bytes(dtype, nchans, &rb) == RT_OK && rb == nchans * (size_t)nbits / 8, "row_bytes");
+    std::vector<unsigned char> x(nsamp * rb);
+    for (unsigned char& b : x) b = (unsigned char)draw();
+    // the restatement: bit k of the row, counted from the least significant
+    // bit of its first byte (16 bit: the same, bytes little-endian)
+    auto value = [&](size_t t, size_t c) {
+        double v = 0.0;
+        for (int k = 0; k < nbits; ++k) {
+            const size_t bit = c * (size_t)nbits + (size_t)k;
+            if (x[t * rb + bit / 8] >> (bit % 8) & 1) v += std::ldexp(1.0, k);
+        }
+        return v;
+    };
+    std::vector<uint8_t> mask;
+    if (masked) {
+        mask.assign(nchans, 0);
+        mask[0] = 1;
+        mask[nchans - 1] = 1;
+    }
+    const uint8_t* mk = masked ? mask.data() : nullptr;
+    size_t nu = 0;
+    for (size_t c = 0; c < nchans; ++c) nu += !masked || !mask[c];
+
+    std::vector<float> out(ndm * nout), m(nsamp);
+    expect(rt_dedisperse_host(x.data(), dtype, nsamp, nchans, delays.data(), mk, ndm, max_delay, nout, out.data()) ==
+               RT_OK, "dedisperse_host (packed)");
+    expect(rt_zero_dm_mean_host(x.data(), dtype, nsamp, nchans, mk, m.data()) == RT_OK, "zero_dm_mean_host (packed)");
+    for (size_t t = 0; t < nsamp; ++t) {
+        double s = 0.0;
+        for (size_t c = 0; c < nchans; ++c)
+            if (!masked || !mask[c]) s += value(t, c);
+        const float want = nu ? (float)(s / (double)nu) : 0.0f;
+        if (m[t] != want) {   // s is an exact integer: the same bits
+            std::printf("FAILED: packed mean nbits %d nchans %zu t %zu: %g vs %g\n", nbits, nchans, t, (double)m[t],
+                        (double)want);
+            ++fails;
+            return;
+        }
+    }
+    std::vector<float> zout(ndm * nout);
+    expect(rt_dedisperse_host_opt(x.data(), dtype, nsamp, nchans, delays.data(), mk, ndm, max_delay, nout, zout.data(),
+                                  RT_DEDISP_ZERO_DM) == RT_OK, "dedisperse_host_opt (packed, zero-DM)");
+    for (size_t d = 0; d < ndm; ++d)
+        for (size_t t = 0; t < nout; ++t) {
+            double ref = 0.0, mag = 0.0, zref = 0.0, zmag = 0.0;
+            for (size_t c = 0; c < nchans; ++c) {
+                if (masked && mask[c]) continue;
+                const size_t tt = t + (size_t)delays[d * nchans + c];
+                const double v = value(tt, c), y = v - (double)m[tt];
+                ref += v;
+                mag += v;
+                zref += y;
+                zmag += std::fabs(y);
+            }
+            // 1/2/4 bit: exact integers; 16 bit: float32 additions in channel order
+            const double tol = nbits == 16 ? (double)nchans * std::ldexp(1.0, -24) * mag : 0.0;
+            const double ztol = (double)(nchans + 2) * std::ldexp(1.0, -24) * zmag;
+            if (std::fabs((double)out[d * nout + t] - ref) > tol ||
+                std::fabs((double)zout[d * nout + t] - zref) > ztol) {
+                std::printf("FAILED: packed nbits %d nchans %zu dm %zu t %zu: %g vs %g, zero-DM %g vs %g\n", nbits,
+                            nchans, d, t, (double)out[d * nout + t], ref, (double)zout[d * nout + t], zref);
+                ++fails;
+                return;
+            }
+        }
+    std::vector<double> acc(2 * nchans, 0.0);
+    const size_t half = nsamp / 3;
+    std::vector<unsigned char> a(x.begin(), x.begin() + (std::ptrdiff_t)(half * rb));
+    std::vector<unsigned char> b(x.begin() + (std::ptrdiff_t)(half * rb), x.end());
+    expect(rt_channel_stats_host(a.data(), dtype, half, nchans, acc.data()) == RT_OK, "channel_stats_host (packed a)");
+    expect(rt_channel_stats_host(b.data(), dtype, nsamp - half, nchans, acc.data()) == RT_OK,
+           "channel_stats_host (packed b)");
+    for (size_t c = 0; c < nchans; ++c) {
+        double s = 0.0, q = 0.0;
+        for (size_t t = 0; t < nsamp; ++t) {
+            const double v = value(t, c);
+            s += v;
+            q += v * v;
+        }
+        if (acc[c] != s || acc[nchans + c] != q) {
+            std::printf("FAILED: packed channel stats nbits %d nchans %zu channel %zu\n", nbits, nchans, c);
+            ++fails;
+            return;
+        }
+    }
+}
+
+void run_packed_errors()
+{
+    std::vector<uint8_t> x(64, 0xA5);
+    std::vector<float> out(16), m(16);
+    std::vector<int64_t> del(16, 0);
+    std::vector<double> acc(32, 0.0);
+    size_t rb = 0;
+    expect(rt_dedisp_row_bytes(RT_DEDISP_U8, 7, &rb) == RT_OK && rb == 7, "row_bytes, uint8");
+    expect(rt_dedisp_row_bytes(RT_DEDISP_I8, 7, &rb) == RT_OK && rb == 7, "row_bytes, int8");
+    expect(rt_dedisp_row_bytes(RT_DEDISP_F32, 7, &rb) == RT_OK && rb == 28, "row_bytes, float32");
+    expect(rt_dedisp_row_bytes(RT_DEDISP_U1, 24, &rb) == RT_OK && rb == 3, "row_bytes, 1 bit");
+    expect(rt_dedisp_row_bytes(RT_DEDISP_U16, 3, &rb) == RT_OK && rb == 6, "row_bytes, 16 bit");
+    expect(rt_dedisp_row_bytes(RT_DEDISP_U1, 12, &rb) == RT_EINVAL, "row_bytes: 12 one-bit channels");
+    expect(rt_dedisp_row_bytes(RT_DEDISP_U2, 6, &rb) == RT_EINVAL, "row_bytes: 6 two-bit channels");
+    expect(rt_dedisp_row_bytes(RT_DEDISP_U4, 3, &rb) == RT_EINVAL, "row_bytes: 3 four-bit channels");
+    expect(rt_dedisp_row_bytes(RT_DEDISP_U4, 0, &rb) == RT_EINVAL, "row_bytes: nchans == 0");
+    expect(rt_dedisp_row_bytes(0x108, 8, &rb) == RT_EINVAL, "row_bytes: unknown code");
+    expect(rt_dedisp_row_bytes(RT_DEDISP_U4, 2, nullptr) == RT_EINVAL, "row_bytes: bytes is NULL");
+    expect(rt_dedisperse_host(x.data(), RT_DEDISP_U1, 4, 12, del.data(), nullptr, 1, 0, 4, out.data()) == RT_EINVAL,
+           "host: rows are not whole bytes");
+    expect(rt_zero_dm_mean_host(x.data(), RT_DEDISP_U2, 4, 6, nullptr, m.data()) == RT_EINVAL,
+           "mean: rows are not whole bytes");
+    expect(rt_channel_stats_host(x.data(), RT_DEDISP_U4, 4, 3, acc.data()) == RT_EINVAL,
+           "stats: rows are not whole bytes");
+    expect(rt_dedisperse_host(x.data(), 0x108, 4, 8, del.data(), nullptr, 1, 0, 4, out.data()) == RT_EINVAL,
+           "host: unknown code in the packed range");
+}
+
 void run_rfi_errors()
 {
     std::vector<uint8_t> x(10 * 2, 1);
@@ -319,8 +452,16 @@ int main()
                     if (masked && nchans < 3) continue;
                     run_rfi_shape(nchans, dtype, masked != 0, single != 0);
                 }
+    const struct {
+        int nbits;
+        size_t chans[4];
+    } packed[] = {{1, {8, 24, 64, 72}}, {2, {4, 12, 64, 68}}, {4, {2, 6, 64, 66}}, {16, {1, 3, 64, 65}}};
+    for (const auto& p : packed)
+        for (size_t nchans : p.chans)
+            for (int masked = 0; masked < 2; ++masked) run_packed_shape(p.nbits, nchans, masked != 0);
     run_errors();
     run_rfi_errors();
+    run_packed_errors();
     if (fails)
         std::printf("dedisp_check: %d failures\n", fails);
     else

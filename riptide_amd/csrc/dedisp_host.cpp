@@ -5,6 +5,7 @@
 #include "riptide_amd.h"
 
 #include <cmath>
+#include <cstdint>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -53,8 +54,8 @@ void dedisperse_rows_zero_dm(const T* x, size_t nsamp, size_t nchans, const int6
                              size_t ndm, size_t nout, float* out)
 {
     std::vector<float> m(nsamp);
-    zero_dm_mean<T, typename std::conditional<sizeof(T) == 1, int64_t, double>::type>(x, nsamp, nchans, mask,
-                                                                                      m.data());
+    zero_dm_mean<T, typename std::conditional<std::is_integral<T>::value, int64_t, double>::type>(x, nsamp, nchans,
+                                                                                                  mask, m.data());
     for (size_t d = 0; d < ndm; ++d) {
         const int64_t* del = delays + d * nchans;
         float* o = out + d * nout;
@@ -81,18 +82,80 @@ void channel_stats(const T* x, size_t nsamp, size_t nchans, double* acc)
         }
 }
 
+// ---- packed sample types (riptide_amd.h, RT_DEDISP_U1 .. RT_DEDISP_U16)
+// bits of a packed code, 0 for any other
+int packed_bits(int dtype)
+{
+    return dtype == RT_DEDISP_U1 ? 1 : dtype == RT_DEDISP_U2 ? 2 : dtype == RT_DEDISP_U4 ? 4
+           : dtype == RT_DEDISP_U16 ? 16 : 0;
+}
+
+bool known_dtype(int dtype)
+{
+    return dtype == RT_DEDISP_U8 || dtype == RT_DEDISP_I8 || dtype == RT_DEDISP_F32 || packed_bits(dtype);
+}
+
+// summed as integers, exact in float32 up to RT_DEDISP_MAX_CHANS_8BIT channels
+bool integer_sum(int dtype) { return dtype != RT_DEDISP_F32 && dtype != RT_DEDISP_U16; }
+
+// The one unpack helper: channel c of a packed row, as riptide_amd.h defines it.
+inline uint32_t unpack_sample(const uint8_t* row, int nbits, size_t c)
+{
+    if (nbits == 16) return (uint32_t)row[2 * c] | (uint32_t)row[2 * c + 1] << 8;
+    const size_t bit = c * (size_t)nbits;
+    return (uint32_t)(row[bit >> 3] >> (bit & 7)) & ((1u << nbits) - 1u);
+}
+
+size_t packed_row_bytes(int nbits, size_t nchans)
+{
+    if (nchans > SIZE_MAX / 16 || nchans * (size_t)nbits % 8)
+        throw std::invalid_argument("dedisperse: " + std::to_string(nchans) + " channels of " + std::to_string(nbits) +
+                                    "-bit data: rows are not a whole number of bytes");
+    return nchans * (size_t)nbits / 8;
+}
+
+// the block as [nsamp, nchans] values: U = uint8_t for 1/2/4 bit, uint16_t for 16 bit
+template <class U>
+std::vector<U> unpack_block(const void* x, int nbits, size_t nsamp, size_t nchans)
+{
+    const size_t rb = packed_row_bytes(nbits, nchans);
+    std::vector<U> v(nsamp * nchans);
+    for (size_t t = 0; t < nsamp; ++t) {
+        const uint8_t* row = (const uint8_t*)x + t * rb;
+        for (size_t c = 0; c < nchans; ++c) v[t * nchans + c] = (U)unpack_sample(row, nbits, c);
+    }
+    return v;
+}
+
 void check_dtype(int dtype, size_t nchans)
 {
-    if (dtype != RT_DEDISP_U8 && dtype != RT_DEDISP_I8 && dtype != RT_DEDISP_F32)
-        throw std::invalid_argument("dedisperse: unknown sample type code");
+    if (!known_dtype(dtype)) throw std::invalid_argument("dedisperse: unknown sample type code");
     if (!nchans) throw std::invalid_argument("dedisperse: nchans and ndm must be at least 1");
-    if (dtype != RT_DEDISP_F32 && nchans > RT_DEDISP_MAX_CHANS_8BIT)
+    if (integer_sum(dtype) && nchans > RT_DEDISP_MAX_CHANS_8BIT)
         throw std::invalid_argument("dedisperse: too many channels for an exact 8-bit sum");
+    if (packed_bits(dtype)) packed_row_bytes(packed_bits(dtype), nchans);
 }
 
 }  // namespace
 
 extern "C" {
+
+int rt_dedisp_row_bytes(int dtype, size_t nchans, size_t* bytes)
+{
+    return guarded([&] {
+        if (!bytes) throw std::invalid_argument("dedisperse: bytes is NULL");
+        if (!known_dtype(dtype)) throw std::invalid_argument("dedisperse: unknown sample type code");
+        if (!nchans) throw std::invalid_argument("dedisperse: nchans and ndm must be at least 1");
+        if (packed_bits(dtype)) {
+            *bytes = packed_row_bytes(packed_bits(dtype), nchans);
+        } else {
+            const size_t esize = dtype == RT_DEDISP_F32 ? 4 : 1;
+            if (nchans > SIZE_MAX / esize) throw std::invalid_argument("dedisperse: too many channels");
+            *bytes = nchans * esize;
+        }
+        return RT_OK;
+    });
+}
 
 int rt_dedisperse_delays(const double* freqs_mhz, size_t nchans, const double* dms, size_t ndm, double tsamp,
                          double kdm, int64_t* delays, int64_t* max_delay)
@@ -141,19 +204,38 @@ int rt_dedisperse_host_opt(const void* x, int dtype, size_t nsamp, size_t nchans
     return guarded([&] {
         if (flags & ~RT_DEDISP_ZERO_DM) throw std::invalid_argument("dedisperse: unknown flag bit");
         if (!nchans || !ndm) throw std::invalid_argument("dedisperse: nchans and ndm must be at least 1");
-        if (dtype != RT_DEDISP_U8 && dtype != RT_DEDISP_I8 && dtype != RT_DEDISP_F32)
-            throw std::invalid_argument("dedisperse: unknown sample type code");
+        if (!known_dtype(dtype)) throw std::invalid_argument("dedisperse: unknown sample type code");
+        const int nbits = packed_bits(dtype);
+        if (nbits) packed_row_bytes(nbits, nchans);
         if (max_delay < 0 || max_delay >= 2147483648ll)
             throw std::invalid_argument("dedisperse: max_delay is outside [0, 2^31)");
         if (nout > nsamp || (uint64_t)max_delay > nsamp - nout)
             throw std::invalid_argument("dedisperse: nout + max_delay exceeds the " + std::to_string(nsamp) +
                                         " samples of the input");
-        if (dtype != RT_DEDISP_F32 && nchans > RT_DEDISP_MAX_CHANS_8BIT)
+        if (integer_sum(dtype) && nchans > RT_DEDISP_MAX_CHANS_8BIT)
             throw std::invalid_argument("dedisperse: too many channels for an exact 8-bit sum");
         for (size_t i = 0; i < ndm * nchans; ++i)
             if (delays[i] < 0 || delays[i] > max_delay)
                 throw std::invalid_argument("dedisperse: a delay is outside [0, max_delay]");
         if (!nout) return RT_OK;
+        if (nbits) {
+            // the values of the packed block, then the same sums: 1/2/4 bit as
+            // 8-bit data, 16 bit converted exactly and added in float32
+            if (nbits == 16) {
+                const std::vector<uint16_t> v = unpack_block<uint16_t>(x, nbits, nsamp, nchans);
+                if (flags & RT_DEDISP_ZERO_DM)
+                    dedisperse_rows_zero_dm(v.data(), nsamp, nchans, delays, mask, ndm, nout, out);
+                else
+                    dedisperse_rows<uint16_t, float>(v.data(), nchans, delays, mask, ndm, nout, out);
+            } else {
+                const std::vector<uint8_t> v = unpack_block<uint8_t>(x, nbits, nsamp, nchans);
+                if (flags & RT_DEDISP_ZERO_DM)
+                    dedisperse_rows_zero_dm(v.data(), nsamp, nchans, delays, mask, ndm, nout, out);
+                else
+                    dedisperse_rows<uint8_t, int32_t>(v.data(), nchans, delays, mask, ndm, nout, out);
+            }
+            return RT_OK;
+        }
         if (flags & RT_DEDISP_ZERO_DM) {
             if (dtype == RT_DEDISP_U8)
                 dedisperse_rows_zero_dm((const uint8_t*)x, nsamp, nchans, delays, mask, ndm, nout, out);
@@ -179,7 +261,12 @@ int rt_zero_dm_mean_host(const void* x, int dtype, size_t nsamp, size_t nchans, 
         check_dtype(dtype, nchans);
         if (!nsamp) return RT_OK;
         if (!x || !m) throw std::invalid_argument("zero_dm_mean: null buffer");
-        if (dtype == RT_DEDISP_U8)
+        if (packed_bits(dtype) == 16)
+            zero_dm_mean<uint16_t, int64_t>(unpack_block<uint16_t>(x, 16, nsamp, nchans).data(), nsamp, nchans, mask, m);
+        else if (packed_bits(dtype))
+            zero_dm_mean<uint8_t, int64_t>(unpack_block<uint8_t>(x, packed_bits(dtype), nsamp, nchans).data(), nsamp,
+                                           nchans, mask, m);
+        else if (dtype == RT_DEDISP_U8)
             zero_dm_mean<uint8_t, int64_t>((const uint8_t*)x, nsamp, nchans, mask, m);
         else if (dtype == RT_DEDISP_I8)
             zero_dm_mean<int8_t, int64_t>((const int8_t*)x, nsamp, nchans, mask, m);
@@ -192,13 +279,17 @@ int rt_zero_dm_mean_host(const void* x, int dtype, size_t nsamp, size_t nchans, 
 int rt_channel_stats_host(const void* x, int dtype, size_t nsamp, size_t nchans, double* acc)
 {
     return guarded([&] {
-        if (dtype != RT_DEDISP_U8 && dtype != RT_DEDISP_I8 && dtype != RT_DEDISP_F32)
-            throw std::invalid_argument("channel_stats: unknown sample type code");
+        if (!known_dtype(dtype)) throw std::invalid_argument("channel_stats: unknown sample type code");
         if (!nchans) throw std::invalid_argument("channel_stats: nchans must be at least 1");
+        if (packed_bits(dtype)) packed_row_bytes(packed_bits(dtype), nchans);
         if (!acc) throw std::invalid_argument("channel_stats: null buffer");
         if (!nsamp) return RT_OK;
         if (!x) throw std::invalid_argument("channel_stats: null buffer");
-        if (dtype == RT_DEDISP_U8)
+        if (packed_bits(dtype) == 16)
+            channel_stats(unpack_block<uint16_t>(x, 16, nsamp, nchans).data(), nsamp, nchans, acc);
+        else if (packed_bits(dtype))
+            channel_stats(unpack_block<uint8_t>(x, packed_bits(dtype), nsamp, nchans).data(), nsamp, nchans, acc);
+        else if (dtype == RT_DEDISP_U8)
             channel_stats((const uint8_t*)x, nsamp, nchans, acc);
         else if (dtype == RT_DEDISP_I8)
             channel_stats((const int8_t*)x, nsamp, nchans, acc);

@@ -9,6 +9,11 @@
 //                             8-bit (signed samples are stored biased by 128),
 //                             the row pitch is padded to 16 bytes and the
 //                             padding is written as zero
+//   dedisp_unpack_transpose_kernel  1-, 2- and 4-bit packed rows unpacked inside
+//                             that transpose, to the same 8-bit rows; 16-bit
+//                             rows go to exact float32 rows (the zero-DM
+//                             transpose without the mean).  The zero-DM and
+//                             statistics kernels read packed rows through DdRow
 //   dedisp_sum_kernel         one workgroup = 16 DMs x 256 outputs; per step
 //                             of 16 channels the span of each channel that the
 //                             tile's DMs read is staged in LDS with aligned
@@ -83,6 +88,106 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_transpose8_kernel(
     }
 }
 
+// ---- packed sample types (riptide_amd.h: RT_DEDISP_U1, U2, U4, U16)
+// Tag of rows of NBITS-bit unsigned samples: the T of a kernel whose block is
+// packed bytes, [nsamp, nchans * NBITS / 8], only byte-aligned.
+template <int NBITS>
+struct DdBits {
+    static constexpr int kBits = NBITS;
+};
+
+// (row pointer, c) -> sample, for every T a kernel reads rows of.  Plain
+// types: the load itself.  kIntSums: int32 partial sums are in range (the
+// kernels say why), float64 otherwise.
+template <class T>
+struct DdRow {
+    static constexpr bool kIntSums = sizeof(T) == 1;
+    static __device__ inline const T* at(const T* x, uint64_t t, uint32_t nchans) { return x + t * nchans; }
+    static __device__ inline T get(const T* row, uint32_t c) { return row[c]; }
+};
+
+// Packed rows: byte loads (these readers are not the hot path).  1/2/4 bit,
+// least significant bits first; 16 bit little-endian.  c * NBITS < 2^26.
+template <int NBITS>
+struct DdRow<DdBits<NBITS>> {
+    static constexpr bool kIntSums = NBITS < 16;
+    static __device__ inline const uint8_t* at(const DdBits<NBITS>* x, uint64_t t, uint32_t nchans)
+    {
+        return reinterpret_cast<const uint8_t*>(x) + t * ((uint64_t)nchans * NBITS / 8);
+    }
+    static __device__ inline uint32_t get(const uint8_t* row, uint32_t c)
+    {
+        if constexpr (NBITS == 16) {
+            return (uint32_t)row[2 * c] | (uint32_t)row[2 * c + 1] << 8;
+        } else {
+            const uint32_t bit = c * NBITS;
+            return ((uint32_t)row[bit >> 3] >> (bit & 7)) & ((1u << NBITS) - 1u);
+        }
+    }
+};
+
+// 1/2/4 bit: packed rows to the 8-bit workspace rows dedisp_transpose8_kernel
+// writes, the values unbiased, for dedisp_sum_kernel<uint8_t> with bias 0.
+// Tile of 64 packed bytes x 256 samples, that is 512, 256 or 128 channels: a
+// wave's reads of a time row cover 64 contiguous bytes at every width.  The
+// tile stays packed in LDS (16.25 KB), transposed byte by byte; the bits come
+// out on the way to the workspace: lane l reads the dword of samples 4 l .. 4 l
+// + 3 of a packed byte once, then one shift and one mask per channel of that
+// byte give four samples at a time (a field never crosses a byte), stored as
+// one dword per lane along time.
+// x is only byte-aligned: dword loads (16 lanes a row, four rows a wave
+// instruction) when `dwords` says x and row_bytes are multiples of 4, byte
+// loads otherwise.  A load touches byte b < row_bytes of a row t < nsamp only
+// (the dword path: b + 3 < row_bytes, both multiples of 4), nothing at or
+// beyond nsamp * row_bytes.
+template <int NBITS>
+__global__ __launch_bounds__(kDdThreads) void dedisp_unpack_transpose_kernel(
+    const uint8_t* __restrict__ x, uint32_t nsamp, uint32_t nchans, uint32_t row_bytes, uint8_t* __restrict__ ws,
+    uint64_t pitch, uint32_t dwords)
+{
+    constexpr uint32_t kPer = 8 / NBITS;                              // channels of a packed byte
+    constexpr uint32_t kMask = ((1u << NBITS) - 1u) * 0x01010101u;    // the low field of each of four bytes
+    __shared__ __attribute__((aligned(16))) uint8_t tile[64][260];
+    const uint32_t tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const uint64_t t0 = (uint64_t)blockIdx.x * 256;
+    const uint32_t b0 = blockIdx.y * 64;
+    if (dwords) {   // uniform over the grid
+        const uint32_t j = tx & 15, r = tx >> 4;
+        const uint32_t b = b0 + 4 * j;
+        for (uint32_t i = ty * 4 + r; i < 256; i += 16) {
+            const uint64_t t = t0 + i;
+            uint32_t v = 0;
+            if (b < row_bytes && t < nsamp) v = *reinterpret_cast<const uint32_t*>(x + t * row_bytes + b);
+            tile[4 * j][i] = (uint8_t)v;
+            tile[4 * j + 1][i] = (uint8_t)(v >> 8);
+            tile[4 * j + 2][i] = (uint8_t)(v >> 16);
+            tile[4 * j + 3][i] = (uint8_t)(v >> 24);
+        }
+    } else {
+        const uint32_t b = b0 + tx;
+        for (uint32_t i = ty; i < 256; i += 4) {
+            const uint64_t t = t0 + i;
+            uint32_t v = 0;
+            if (b < row_bytes && t < nsamp) v = x[t * row_bytes + b];
+            tile[tx][i] = (uint8_t)v;
+        }
+    }
+    __syncthreads();
+    const uint64_t tb = t0 + tx * 4;
+    if (tb >= pitch) return;   // the pitch is a multiple of 16: a dword at tb < pitch is inside the row
+    for (uint32_t i = ty; i < 64; i += 4) {
+        const uint32_t b = b0 + i;
+        if (b >= row_bytes) break;
+        const uint32_t w = *reinterpret_cast<const uint32_t*>(&tile[i][tx * 4]);
+#pragma unroll
+        for (uint32_t k = 0; k < kPer; ++k) {
+            const uint32_t co = b * kPer + k;   // < row_bytes * kPer = nchans
+            if (co < nchans)
+                *reinterpret_cast<uint32_t*>(ws + (uint64_t)co * pitch + tb) = (w >> (k * NBITS)) & kMask;
+        }
+    }
+}
+
 // float: tile of 64 channels x 64 samples.
 __global__ __launch_bounds__(kDdThreads) void dedisp_transpose32_kernel(
     const float* __restrict__ x, uint32_t nsamp, uint32_t nchans, float* __restrict__ ws, uint64_t pitch)
@@ -121,23 +226,26 @@ __device__ inline float dd_value(T v)
 // (the fastest index: coalesced); int32 partial sums for 8-bit samples (at
 // most 65793 * 255), float64 for float samples; a 64-lane butterfly, so every
 // lane holds the same total, summed in an order that depends on nchans alone.
+// Packed rows are read through DdRow: 1/2/4 bit in int32 (at most 65793 * 15),
+// 16 bit in float64 (integers below 2^16 * 2^22 channels: exact).
 template <class T>
 __global__ __launch_bounds__(kDdThreads) void dedisp_rowmean_kernel(
     const T* __restrict__ x, uint32_t nsamp, uint32_t nchans, const uint8_t* __restrict__ mask,
     float* __restrict__ m)
 {
-    using Acc = typename std::conditional<sizeof(T) == 1, int32_t, double>::type;
+    using R = DdRow<T>;
+    using Acc = typename std::conditional<R::kIntSums, int32_t, double>::type;
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t t0 = (uint64_t)blockIdx.x * kRmRowsPerWg + wave * kRmRows;
     for (uint32_t r = 0; r < kRmRows; ++r) {
         const uint64_t t = t0 + r;
         if (t >= nsamp) return;   // wave-uniform
-        const T* row = x + t * nchans;
+        const auto* row = R::at(x, t, nchans);
         Acc s = 0;
         int32_t nu = 0;
         for (uint32_t c = lane; c < nchans; c += 64) {
             if (mask && mask[c]) continue;
-            s += (Acc)row[c];
+            s += (Acc)R::get(row, c);
             ++nu;
         }
 #pragma unroll
@@ -151,8 +259,10 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_rowmean_kernel(
 
 // Zero-DM variant of both transposes: T = uint8_t, int8_t or float in, float32
 // x - m out, channel-major; tile of 64 channels x 64 samples, the pitch in
-// floats, its padding (and every t >= nsamp) written as zero.
-template <class T>
+// floats, its padding (and every t >= nsamp) written as zero.  T may be a
+// packed row type (DdRow); kMean = false is the plain transpose of 16-bit rows
+// to float32 (the values converted exactly, m not read).
+template <class T, bool kMean = true>
 __global__ __launch_bounds__(kDdThreads) void dedisp_transpose_zdm_kernel(
     const T* __restrict__ x, uint32_t nsamp, uint32_t nchans, const float* __restrict__ m, float* __restrict__ ws,
     uint64_t pitch)
@@ -166,8 +276,12 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_transpose_zdm_kernel(
         const uint64_t t = t0 + i;
         float v = 0.0f;
         if (t < nsamp) {   // wave-uniform: m[t] is one broadcast load
-            const float mt = m[t];
-            if (c < nchans) v = dd_value(x[t * nchans + c]) - mt;
+            float mt = 0.0f;
+            if constexpr (kMean) mt = m[t];
+            if (c < nchans) {
+                v = dd_value(DdRow<T>::get(DdRow<T>::at(x, t, nchans), c));
+                if constexpr (kMean) v = v - mt;
+            }
         }
         tile[tx][i] = v;
     }
@@ -184,11 +298,13 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_transpose_zdm_kernel(
 // rows, their partial sums added in wave order through LDS.  8-bit samples
 // are summed as integers (at most 512 rows x 128^2 or 255^2 per wave: below
 // 2^31 / 2^32), float samples in float64.  part is [nchunks, 2, nchans].
+// Packed rows (DdRow): 1/2/4 bit as integers (at most 512 x 15^2), 16 bit in
+// float64 (512 x 65535^2 < 2^41: exact).
 template <class T>
 __global__ __launch_bounds__(kDdThreads) void dedisp_chanstats_kernel(
     const T* __restrict__ x, uint32_t nsamp, uint32_t nchans, double* __restrict__ part)
 {
-    constexpr bool kBytes = sizeof(T) == 1;
+    constexpr bool kBytes = DdRow<T>::kIntSums;
     using Sum = typename std::conditional<kBytes, int32_t, double>::type;
     using Sq = typename std::conditional<kBytes, uint32_t, double>::type;
     __shared__ double red[2][kDdWaves][64];
@@ -200,7 +316,7 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_chanstats_kernel(
     Sq q = 0;
     if (c < nchans)
         for (uint64_t t = t0 + wave; t < t1; t += kDdWaves) {
-            const Sum v = (Sum)x[t * nchans + c];
+            const Sum v = (Sum)DdRow<T>::get(DdRow<T>::at(x, t, nchans), c);
             s += v;
             q += (Sq)(v * v);
         }
@@ -360,9 +476,21 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_sum_kernel(
 
 }  // namespace
 
+// f(tag) with the DdBits tag of a packed sample type code
+template <class F>
+void dd_packed(int dtype, F f)
+{
+    switch (dedisp_packed_bits(dtype)) {
+    case 1: f(DdBits<1>{}); break;
+    case 2: f(DdBits<2>{}); break;
+    case 4: f(DdBits<4>{}); break;
+    default: f(DdBits<16>{}); break;
+    }
+}
+
 uint64_t dedisp_pitch_bytes(int dtype, uint64_t nsamp_blk)
 {
-    const uint64_t esize = dtype == 2 ? 4 : 1;
+    const uint64_t esize = dtype == 2 || dedisp_packed_bits(dtype) == 16 ? 4 : 1;
     return (nsamp_blk * esize + 15) / 16 * 16;
 }
 
@@ -376,7 +504,13 @@ hipError_t launch_zero_dm_mean(const void* block, int dtype, uint32_t nsamp_blk,
                                const uint8_t* d_mask, float* m, hipStream_t s)
 {
     const dim3 grid((nsamp_blk + kRmRowsPerWg - 1) / kRmRowsPerWg);
-    if (dtype == 0)
+    if (dedisp_packed_bits(dtype))
+        dd_packed(dtype, [&](auto tag) {
+            using T = decltype(tag);
+            hipLaunchKernelGGL(dedisp_rowmean_kernel<T>, grid, dim3(kDdThreads), 0, s, (const T*)block, nsamp_blk,
+                               nchans, d_mask, m);
+        });
+    else if (dtype == 0)
         hipLaunchKernelGGL(dedisp_rowmean_kernel<uint8_t>, grid, dim3(kDdThreads), 0, s, (const uint8_t*)block,
                            nsamp_blk, nchans, d_mask, m);
     else if (dtype == 1)
@@ -399,7 +533,13 @@ hipError_t launch_channel_stats(const void* block, int dtype, uint32_t nsamp_blk
     const uint32_t nchunks = (nsamp_blk + kCsChunk - 1) / kCsChunk;
     const dim3 grid(nchunks, (nchans + 63) / 64);
     double* part = (double*)ws;
-    if (dtype == 0)
+    if (dedisp_packed_bits(dtype))
+        dd_packed(dtype, [&](auto tag) {
+            using T = decltype(tag);
+            hipLaunchKernelGGL(dedisp_chanstats_kernel<T>, grid, dim3(kDdThreads), 0, s, (const T*)block, nsamp_blk,
+                               nchans, part);
+        });
+    else if (dtype == 0)
         hipLaunchKernelGGL(dedisp_chanstats_kernel<uint8_t>, grid, dim3(kDdThreads), 0, s, (const uint8_t*)block,
                            nsamp_blk, nchans, part);
     else if (dtype == 1)
@@ -418,6 +558,7 @@ hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, u
                              float* out, uint64_t out_stride, void* ws, uint32_t flags, hipStream_t s)
 {
     const uint32_t nout = nsamp_blk - max_delay;
+    const int nbits = dedisp_packed_bits(dtype);
     const uint64_t pitch_bytes = dedisp_pitch_bytes(flags & kDdZeroDm ? 2 : dtype, nsamp_blk);
     const dim3 sum_grid((nout + kDdTile - 1) / kDdTile, (ndm + kDdDms - 1) / kDdDms);
     if (flags & kDdZeroDm) {
@@ -427,7 +568,13 @@ hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, u
         const hipError_t e = launch_zero_dm_mean(block, dtype, nsamp_blk, nchans, d_mask, m, s);
         if (e != hipSuccess) return e;
         const dim3 grid((uint32_t)((pitch + 63) / 64), (nchans + 63) / 64);
-        if (dtype == 0)
+        if (nbits)
+            dd_packed(dtype, [&](auto tag) {
+                using T = decltype(tag);
+                hipLaunchKernelGGL(dedisp_transpose_zdm_kernel<T>, grid, dim3(kDdThreads), 0, s, (const T*)block,
+                                   nsamp_blk, nchans, (const float*)m, (float*)ws, pitch);
+            });
+        else if (dtype == 0)
             hipLaunchKernelGGL(dedisp_transpose_zdm_kernel<uint8_t>, grid, dim3(kDdThreads), 0, s,
                                (const uint8_t*)block, nsamp_blk, nchans, (const float*)m, (float*)ws, pitch);
         else if (dtype == 1)
@@ -438,6 +585,28 @@ hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, u
                                (const float*)block, nsamp_blk, nchans, (const float*)m, (float*)ws, pitch);
         hipLaunchKernelGGL(dedisp_sum_kernel<float>, sum_grid, dim3(kDdThreads), 0, s, (const float*)ws, pitch,
                            nchans, d_delays, d_mask, ndm, max_delay, nout, out, out_stride, 0);
+    } else if (nbits == 16) {
+        // exact float32 rows, then the float sum
+        const uint64_t pitch = pitch_bytes / 4;
+        const dim3 grid((uint32_t)((pitch + 63) / 64), (nchans + 63) / 64);
+        hipLaunchKernelGGL((dedisp_transpose_zdm_kernel<DdBits<16>, false>), grid, dim3(kDdThreads), 0, s,
+                           (const DdBits<16>*)block, nsamp_blk, nchans, (const float*)nullptr, (float*)ws, pitch);
+        hipLaunchKernelGGL(dedisp_sum_kernel<float>, sum_grid, dim3(kDdThreads), 0, s, (const float*)ws, pitch,
+                           nchans, d_delays, d_mask, ndm, max_delay, nout, out, out_stride, 0);
+    } else if (nbits) {
+        // the 8-bit rows of the values, then the 8-bit sum with no bias
+        const uint32_t row_bytes = (uint32_t)((uint64_t)nchans * nbits / 8);
+        const uint32_t dwords = row_bytes % 4 == 0 && (uintptr_t)block % 4 == 0;
+        const dim3 grid((uint32_t)((pitch_bytes + 255) / 256), (row_bytes + 63) / 64);
+        dd_packed(dtype, [&](auto tag) {
+            constexpr int kBits = decltype(tag)::kBits;
+            if constexpr (kBits < 16)
+                hipLaunchKernelGGL(dedisp_unpack_transpose_kernel<kBits>, grid, dim3(kDdThreads), 0, s,
+                                   (const uint8_t*)block, nsamp_blk, nchans, row_bytes, (uint8_t*)ws, pitch_bytes,
+                                   dwords);
+        });
+        hipLaunchKernelGGL(dedisp_sum_kernel<uint8_t>, sum_grid, dim3(kDdThreads), 0, s, (const uint8_t*)ws,
+                           pitch_bytes, nchans, d_delays, d_mask, ndm, max_delay, nout, out, out_stride, 0);
     } else if (dtype == 2) {
         const uint64_t pitch = pitch_bytes / 4;
         const dim3 grid((uint32_t)((pitch + 63) / 64), (nchans + 63) / 64);

@@ -80,8 +80,15 @@ hipError_t launch_fold_subints(const FoldCand* d_cands, uint32_t num_cands, uint
                                const float* rows_ws, hipStream_t s);
 
 // dedisp_kernels.hip
+// bits of a packed sample type code (RT_DEDISP_U1, U2, U4, U16: the block is
+// then bytes, [nsamp_blk, nchans * bits / 8], byte-aligned), 0 for a plain one
+constexpr int dedisp_packed_bits(int dtype)
+{
+    return dtype == 0x101 ? 1 : dtype == 0x102 ? 2 : dtype == 0x104 ? 4 : dtype == 0x110 ? 16 : 0;
+}
 // bytes of one channel-major row of the transposed block (dtype: the
-// RT_DEDISP_* code of riptide_amd.h), a multiple of 16
+// RT_DEDISP_* code of riptide_amd.h), a multiple of 16: bytes for 8-bit and
+// 1/2/4-bit data, floats for float and 16-bit data
 uint64_t dedisp_pitch_bytes(int dtype, uint64_t nsamp_blk);
 // out[d * out_stride + t] for t < nsamp_blk - max_delay; ws: nchans rows of
 // dedisp_pitch_bytes, 16-byte aligned.  The caller has checked the shape

@@ -10,6 +10,10 @@ with the delay of channel c against the highest frequency of the band
   delay[d, c] = floor(kdm * dm[d] * (f_c ** -2 - f_ref ** -2) / tsamp + 0.5)
 
 8-bit data gives exact integer sums; float32 data is summed in float32.
+Packed 1-, 2-, 4- and 16-bit data (nbits=, or a reading.PackedFilterbank; the
+format: reading.unpack_samples) stays packed up to the device: 1/2/4-bit data
+is unpacked inside the transpose and summed exactly, 16-bit data is converted
+exactly and summed in float32 (exact up to 256 channels).
 
 zero_dm=True puts the zero-DM filter (Eatough, Keane & Lyne 2009) in front of
 the sum: every time sample first loses its mean over the unmasked channels,
@@ -39,6 +43,7 @@ DEFAULT_BUDGET_BYTES = 32 << 30
 DEFAULT_GULP_BYTES = 256 << 20
 
 _DTYPE_CODES = {np.dtype(np.uint8): 0, np.dtype(np.int8): 1, np.dtype(np.float32): 2}
+_NBITS_CODES = {1: 0x101, 2: 0x102, 4: 0x104, 16: 0x110}    # RT_DEDISP_U1 .. RT_DEDISP_U16
 MAX_CHANS_8BIT = 65793    # RT_DEDISP_MAX_CHANS_8BIT: 255 * nchans < 2^24
 
 
@@ -69,6 +74,33 @@ def _checked_mask(mask, nchans):
     return mask
 
 
+def _checked_packed(data, nbits):
+    """(packed rows uint8 [nsamp, row_bytes], type code, nchans) of host data
+    given with nbits."""
+    nbits = int(nbits)
+    data = np.asarray(data)
+    if nbits not in _NBITS_CODES:
+        raise ValueError("nbits must be 1, 2, 4 or 16")
+    if data.ndim != 2 or data.dtype != np.uint8:
+        raise ValueError("packed data must be a uint8 array [nsamp, row_bytes]")
+    if data.shape[1] * 8 % nbits:
+        raise ValueError(f"rows of {data.shape[1]} bytes are not a whole number of {nbits}-bit channels")
+    nchans = data.shape[1] * 8 // nbits
+    if nbits != 16 and nchans > MAX_CHANS_8BIT:
+        raise ValueError(f"{nbits}-bit data with {nchans} channels: sums are exact only up to {MAX_CHANS_8BIT} "
+                         "channels (255 * nchans must be below 2^24)")
+    return np.ascontiguousarray(data), _NBITS_CODES[nbits], nchans
+
+
+def _host_block(data, nbits):
+    """(contiguous array, type code, nsamp, nchans) of a host data argument."""
+    if nbits is not None:
+        data, code, nchans = _checked_packed(data, nbits)
+        return data, code, data.shape[0], nchans
+    data = np.ascontiguousarray(_checked_data(data))
+    return data, _DTYPE_CODES[data.dtype], data.shape[0], data.shape[1]
+
+
 def _checked_data(data):
     data = np.asarray(data)
     if data.ndim != 2 or data.dtype not in _DTYPE_CODES:
@@ -83,24 +115,24 @@ def _flags(zero_dm):
     return 1 if zero_dm else 0     # RT_DEDISP_ZERO_DM
 
 
-def zero_dm_mean_host(data, mask=None):
+def zero_dm_mean_host(data, mask=None, nbits=None):
     """The zero-DM mean series on the host (rt_zero_dm_mean_host, no device):
-    float32 [nsamp], every time sample's mean over the unmasked channels."""
-    data = np.ascontiguousarray(_checked_data(data))
-    nsamp, nchans = data.shape
+    float32 [nsamp], every time sample's mean over the unmasked channels.
+    nbits: data is packed rows, as for dedisperse."""
+    data, code, nsamp, nchans = _host_block(data, nbits)
     mask = _checked_mask(mask, nchans)
     m = np.zeros(nsamp, dtype=np.float32)
-    _check(_L.rt_zero_dm_mean_host(_lib.ptr(data), _DTYPE_CODES[data.dtype], nsamp, nchans,
+    _check(_L.rt_zero_dm_mean_host(_lib.ptr(data), code, nsamp, nchans,
                                    None if mask is None else _lib.ptr(mask), _lib.ptr(m)))
     return m
 
 
-def dedisperse_host(data, delays, max_delay, mask=None, nout=None, zero_dm=False):
+def dedisperse_host(data, delays, max_delay, mask=None, nout=None, zero_dm=False, nbits=None):
     """The specification on the host (rt_dedisperse_host_opt, no device):
     float32 [ndm, nout] from data [nsamp, nchans] and a delay table; nout
-    defaults to nsamp - max_delay."""
-    data = np.ascontiguousarray(_checked_data(data))
-    nsamp, nchans = data.shape
+    defaults to nsamp - max_delay.  nbits: data is packed rows, as for
+    dedisperse."""
+    data, code, nsamp, nchans = _host_block(data, nbits)
     delays = np.ascontiguousarray(delays, dtype=np.int64)
     if delays.ndim != 2 or delays.shape[1] != nchans:
         raise ValueError("delays must be [ndm, nchans]")
@@ -109,19 +141,20 @@ def dedisperse_host(data, delays, max_delay, mask=None, nout=None, zero_dm=False
     if nout < 0:
         raise ValueError(f"max_delay {max_delay} exceeds the {nsamp} samples of the input")
     out = np.zeros((delays.shape[0], nout), dtype=np.float32)
-    _check(_L.rt_dedisperse_host_opt(_lib.ptr(data), _DTYPE_CODES[data.dtype], nsamp, nchans, _lib.ptr(delays),
+    _check(_L.rt_dedisperse_host_opt(_lib.ptr(data), code, nsamp, nchans, _lib.ptr(delays),
                                      None if mask is None else _lib.ptr(mask), delays.shape[0], int(max_delay),
                                      nout, _lib.ptr(out), _flags(zero_dm)))
     return out
 
 
-def dedisperse(data, freqs, tsamp, dms, mask=None, kdm=KDM, zero_dm=False):
+def dedisperse(data, freqs, tsamp, dms, mask=None, kdm=KDM, zero_dm=False, nbits=None):
     """Dedisperse host data [nsamp, nchans] (uint8, int8 or float32) at the
     trial DMs on the GPU: float32 [ndm, nsamp - max_delay] (rt_dedisperse:
     upload, kernels, download).  mask: per channel, True = skipped; a masked
-    channel still counts towards the reference frequency and max_delay."""
-    data = np.ascontiguousarray(_checked_data(data))
-    nsamp, nchans = data.shape
+    channel still counts towards the reference frequency and max_delay.
+    nbits (1, 2, 4 or 16): data is packed rows instead, uint8 [nsamp,
+    nchans * nbits / 8] (reading.pack_samples / unpack_samples)."""
+    data, code, nsamp, nchans = _host_block(data, nbits)
     delays, max_delay = dispersion_delays(freqs, dms, tsamp, kdm)
     if delays.shape[1] != nchans:
         raise ValueError("freqs must have one entry per channel of data")
@@ -129,10 +162,19 @@ def dedisperse(data, freqs, tsamp, dms, mask=None, kdm=KDM, zero_dm=False):
     if max_delay >= nsamp:
         raise ValueError(f"the largest delay ({max_delay} samples) is not below the {nsamp} samples of the data")
     out = np.empty((delays.shape[0], nsamp - max_delay), dtype=np.float32)
-    _check(_L.rt_dedisperse_opt(_lib.ptr(data), _DTYPE_CODES[data.dtype], nsamp, nchans, _lib.ptr(delays),
+    _check(_L.rt_dedisperse_opt(_lib.ptr(data), code, nsamp, nchans, _lib.ptr(delays),
                                 None if mask is None else _lib.ptr(mask), delays.shape[0], max_delay, _lib.ptr(out),
                                 _flags(zero_dm)))
     return out
+
+
+def _gulp_layout(fb):
+    """(elements of a row of fb.data, their numpy dtype): the raw bytes of a
+    PackedFilterbank, the samples of a Filterbank."""
+    nbits = getattr(fb, "nbits", None)
+    if nbits is not None:
+        return fb.row_bytes, np.dtype(np.uint8)
+    return fb.nchans, np.dtype(fb.dtype)
 
 
 def stream_gulps(fb, dev, gulp, nrows, overlap, process):
@@ -141,13 +183,15 @@ def stream_gulps(fb, dev, gulp, nrows, overlap, process):
     page-locked staging buffers and two device blocks: the upload of gulp
     k + 1 runs on a copy stream behind the kernels of gulp k.  For every gulp
     process(block, start) queues its kernels on the current stream; block is
-    the device tensor [g, nchans] of rows [start, start + g).  Called inside
+    the device tensor [g, nchans] of rows [start, start + g) -- for a
+    reading.PackedFilterbank the packed rows, uint8 [g, row_bytes]; the gulp is
+    counted in time samples either way.  Called inside
     torch.cuda.device(dev); returns once the last gulp is queued and every
     upload is done.  (dedisperse_filterbank, rfi.channel_stats and
     rfi.zero_dm_series share it.)"""
     import torch
-    nchans = fb.nchans
-    tdtype = {"uint8": torch.uint8, "int8": torch.int8, "float32": torch.float32}[np.dtype(fb.dtype).name]
+    nchans, tdtype = _gulp_layout(fb)
+    tdtype = {"uint8": torch.uint8, "int8": torch.int8, "float32": torch.float32}[tdtype.name]
     main = torch.cuda.current_stream(dev)
     copy = torch.cuda.Stream(device=dev)
     pinned = [torch.empty((gulp, nchans), dtype=tdtype).pin_memory() for _ in range(2)]
@@ -186,7 +230,8 @@ def stream_gulps(fb, dev, gulp, nrows, overlap, process):
 
 def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, nout=None,
                           budget_bytes=DEFAULT_BUDGET_BYTES, zero_dm=False):
-    """Dedisperse a reading.Filterbank at the trial DMs into one device tensor
+    """Dedisperse a reading.Filterbank (or PackedFilterbank: the rows are
+    uploaded packed) at the trial DMs into one device tensor
     float32 [ndm, nout], nout = nsamp - max_delay (or a smaller `nout`: the
     first nout samples, e.g. the length a larger DM list would leave).
 
@@ -209,10 +254,13 @@ def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, n
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else
                        (device.index if isinstance(device, torch.device) else int(device)))
     nsamp, nchans = fb.nsamp, fb.nchans
-    dtype = np.dtype(fb.dtype)
-    if dtype not in _DTYPE_CODES:
+    nbits = getattr(fb, "nbits", None)
+    row_elems, dtype = _gulp_layout(fb)
+    if nbits is None and dtype not in _DTYPE_CODES:
         raise ValueError("the filterbank's samples must be uint8, int8 or float32")
-    if dtype != np.float32 and nchans > MAX_CHANS_8BIT:
+    if nbits is not None and nbits not in _NBITS_CODES:
+        raise ValueError("a packed filterbank must hold 1-, 2-, 4- or 16-bit samples")
+    if (dtype != np.float32 and nbits != 16) and nchans > MAX_CHANS_8BIT:
         raise ValueError(f"8-bit data with {nchans} channels: sums are exact only up to {MAX_CHANS_8BIT} channels "
                          "(255 * nchans must be below 2^24)")
     delays, max_delay = dispersion_delays(fb.freqs, dms, fb.tsamp, kdm)
@@ -224,7 +272,7 @@ def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, n
     if not 0 < nout <= full:
         raise ValueError(f"nout must be in [1, {full}]")
     ndm = delays.shape[0]
-    row_bytes = nchans * dtype.itemsize
+    row_bytes = row_elems * dtype.itemsize
     if gulp is None:
         gulp = max(DEFAULT_GULP_BYTES // row_bytes, 2 * max_delay + 1)
     gulp = int(gulp)
@@ -232,7 +280,7 @@ def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, n
         raise ValueError(f"gulp must exceed the largest delay ({max_delay} samples)")
     need_in = nout + max_delay          # input rows the outputs read
     gulp = min(gulp, need_in)
-    ws_bytes = engine.dedisperse_workspace_bytes(dtype.name, gulp, nchans, zero_dm)
+    ws_bytes = engine.dedisperse_workspace_bytes(dtype.name, gulp, nchans, zero_dm, nbits=nbits)
     total = ndm * nout * 4 + 2 * gulp * row_bytes + ws_bytes
     if total > int(budget_bytes):
         raise ValueError(f"dedispersing {ndm} DMs needs {total} bytes of device memory ({ndm * nout * 4} of output "
@@ -245,7 +293,7 @@ def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, n
 
         def process(block, start):
             engine.dedisperse_device(block, d_delays, max_delay, mask=d_mask, out=out, out_offset=start,
-                                     workspace=workspace, zero_dm=zero_dm)
+                                     workspace=workspace, zero_dm=zero_dm, nbits=nbits)
 
         stream_gulps(fb, dev, gulp, need_in, max_delay, process)
     return out

@@ -215,7 +215,7 @@ class EngineSearcher:
         return self.submit_samples(samples, tsamps, metadatas)()
 
     def search_filterbank(self, fb, dms, mask=None, nout=None, kdm=None, zero_dm=False):
-        """Dedisperse a reading.Filterbank at the trial DMs on the device
+        """Dedisperse a reading.Filterbank or PackedFilterbank at the trial DMs on the device
         (dedispersion.dedisperse_filterbank) and search every series: one peak
         list per DM, in the order given (the __call__ contract).  The series
         never leave the device: they go to _enqueue / _detect in slices of
@@ -316,7 +316,9 @@ def search_files(fnames, pool, group=None, chunksize=None):
 
 
 def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=None, zero_dm=False):
-    """Search a channelised SIGPROC file at the trial DMs without leaving the
+    """Search a channelised SIGPROC file (a file name, opened by
+    reading.open_filterbank: 1-, 2-, 4-, 8-, 16- or 32-bit samples; or a
+    Filterbank / PackedFilterbank) at the trial DMs without leaving the
     device: each rank dedisperses its round-robin share of `dms`
     (searcher.search_filterbank, an EngineSearcher) from the one file and
     searches the series in device memory; one gather of the tagged peak
@@ -329,8 +331,8 @@ def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=Non
     over the unmasked channels before the sum (the zero-DM filter)."""
     from .dedispersion import KDM, dispersion_delays
     kdm = KDM if kdm is None else float(kdm)
-    from .reading import Filterbank
-    fb = fb_or_fname if isinstance(fb_or_fname, Filterbank) else Filterbank(fb_or_fname)
+    from .reading import Filterbank, open_filterbank
+    fb = fb_or_fname if isinstance(fb_or_fname, Filterbank) else open_filterbank(fb_or_fname)
     dms = [float(d) for d in dms]
     rank, world = _rank_world(group)
     tagged = []

@@ -268,42 +268,64 @@ def fold_device(data, tsamp, specs, stream=None):
     return results
 
 
-# RT_DEDISP_* sample type codes (include/riptide_amd.h)
-DEDISP_DTYPES = {"uint8": 0, "int8": 1, "float32": 2}
+# RT_DEDISP_* sample type codes (include/riptide_amd.h); 'u1', 'u2', 'u4' and
+# 'u16' are the packed types: the block is then uint8 rows of nchans * nbits / 8
+# bytes (reading.unpack_samples has the format)
+DEDISP_DTYPES = {"uint8": 0, "int8": 1, "float32": 2, "u1": 0x101, "u2": 0x102, "u4": 0x104, "u16": 0x110}
+
+
+def _dedisp_name(dtype, nbits):
+    """The key of DEDISP_DTYPES for a dtype name, or for packed `nbits`."""
+    name = str(dtype) if nbits is None else f"u{int(nbits)}"
+    if name not in DEDISP_DTYPES or (nbits is not None and int(nbits) not in (1, 2, 4, 16)):
+        raise ValueError("the sample type must be uint8, int8, float32, or packed with nbits 1, 2, 4 or 16")
+    return name
 
 
 DEDISP_ZERO_DM = 1    # RT_DEDISP_ZERO_DM
 
 
-def dedisperse_workspace_bytes(dtype, nsamp_blk, nchans, zero_dm=False):
+def dedisperse_workspace_bytes(dtype, nsamp_blk, nchans, zero_dm=False, nbits=None):
     """Device workspace bytes of dedisperse_device for a block of this shape;
-    dtype is 'uint8', 'int8' or 'float32'.  With zero_dm every dtype takes
-    float32 rows, plus nsamp_blk floats for the mean series."""
+    dtype is 'uint8', 'int8', 'float32' or a packed type name ('u1', 'u2',
+    'u4', 'u16'; or pass nbits, dtype is then ignored).  1/2/4-bit data takes
+    the 8-bit size and 16-bit data the float32 size.  With zero_dm every dtype
+    takes float32 rows, plus nsamp_blk floats for the mean series."""
     b = ctypes.c_size_t()
-    _check(_L.rt_dedisperse_workspace_bytes_opt(DEDISP_DTYPES[str(dtype)], int(nsamp_blk), int(nchans),
+    _check(_L.rt_dedisperse_workspace_bytes_opt(DEDISP_DTYPES[_dedisp_name(dtype, nbits)], int(nsamp_blk), int(nchans),
                                                 DEDISP_ZERO_DM if zero_dm else 0, ctypes.byref(b)))
     return b.value
 
 
-def _dedisp_block(block):
-    """(dtype name, nsamp_blk, nchans) of a block argument, validated."""
+def _dedisp_block(block, nbits=None):
+    """(dtype name, nsamp_blk, nchans) of a block argument, validated.  With
+    nbits the block is packed rows, uint8 [nsamp_blk, row_bytes] (any byte
+    alignment), and nchans = row_bytes * 8 / nbits."""
     if block.dim() != 2 or block.device.type != "cuda" or not block.is_contiguous():
         raise ValueError("block must be a contiguous [nsamp_blk, nchans] device tensor")
     name = str(block.dtype).replace("torch.", "")
+    if nbits is not None:
+        if name != "uint8":
+            raise ValueError("a packed block must be uint8 [nsamp_blk, row_bytes]")
+        name = _dedisp_name(None, nbits)
+        if block.shape[1] * 8 % int(nbits):
+            raise ValueError(f"rows of {block.shape[1]} bytes are not a whole number of {int(nbits)}-bit channels")
+        return name, block.shape[0], block.shape[1] * 8 // int(nbits)
     if name not in DEDISP_DTYPES:
         raise ValueError("block must be uint8, int8 or float32")
     return name, block.shape[0], block.shape[1]
 
 
-def zero_dm_mean_device(block, mask=None, out=None, stream=None):
+def zero_dm_mean_device(block, mask=None, out=None, stream=None, nbits=None):
     """The zero-DM time series of one resident block (rt_zero_dm_mean_device,
     the row-mean kernel alone): float32 [nsamp_blk], every time sample's mean
     over the unmasked channels -- the sum exact for 8-bit data, in float64 for
     float32 data, divided in float64 and rounded to float32 once; all zero
-    when every channel is masked.  block and mask as for dedisperse_device.
+    when every channel is masked.  block, mask and nbits as for
+    dedisperse_device (packed sums are exact integers too).
     Stream-ordered, no host synchronisation."""
     import torch
-    name, nsamp_blk, nchans = _dedisp_block(block)
+    name, nsamp_blk, nchans = _dedisp_block(block, nbits)
     if mask is not None and (mask.dtype != torch.uint8 or mask.device != block.device or not mask.is_contiguous()
                              or tuple(mask.shape) != (nchans,)):
         raise ValueError("mask must be a contiguous uint8 [nchans] tensor on the block's device")
@@ -328,15 +350,17 @@ def channel_stats_workspace_bytes(nsamp_blk, nchans):
     return b.value
 
 
-def channel_stats_device(block, acc, workspace=None, stream=None):
+def channel_stats_device(block, acc, workspace=None, stream=None, nbits=None):
     """Add the per-channel sums of one resident block into acc, float64
     [2, nchans] on the block's device (rt_channel_stats_device): acc[0] += the
     sum over time of block[:, c], acc[1] += the sum of its squares (int8
     samples as signed values).  Partial sums per chunk of time, folded in
     chunk order: no atomics, the same bits every time; 8-bit sums are exact.
+    nbits: the block is packed rows, as for dedisperse_device; the sums are
+    integers, exact below 2^53.
     Stream-ordered, no host synchronisation.  Returns acc."""
     import torch
-    name, nsamp_blk, nchans = _dedisp_block(block)
+    name, nsamp_blk, nchans = _dedisp_block(block, nbits)
     if (acc.dtype != torch.float64 or acc.device != block.device or not acc.is_contiguous()
             or tuple(acc.shape) != (2, nchans)):
         raise ValueError(f"acc must be a contiguous float64 [2, {nchans}] tensor on the block's device")
@@ -356,7 +380,7 @@ def channel_stats_device(block, acc, workspace=None, stream=None):
 
 
 def dedisperse_device(block, delays, max_delay, mask=None, out=None, out_offset=0, workspace=None, stream=None,
-                      zero_dm=False):
+                      zero_dm=False, nbits=None):
     """Incoherent dedispersion of one resident block (rt_dedisperse_device):
     block uint8 / int8 / float32 [nsamp_blk, nchans] (time-major, contiguous),
     delays int32 [ndm, nchans] and mask (uint8 [nchans], non-zero = skipped, or
@@ -367,13 +391,20 @@ def dedisperse_device(block, delays, max_delay, mask=None, out=None, out_offset=
     when None).  Stream-ordered, no host synchronisation.  8-bit results are
     exact; float32 results are summed in channel order.
 
+    nbits (1, 2, 4 or 16): block is packed rows, uint8 [nsamp_blk, row_bytes]
+    with row_bytes = nchans * nbits / 8 and any byte alignment, in the format
+    of reading.unpack_samples; nchans is derived from it.  1/2/4-bit data is
+    unpacked inside the transpose and summed exactly, as 8-bit data; 16-bit
+    data is converted exactly and summed in float32 in channel order (exact up
+    to 256 channels).
+
     zero_dm: the zero-DM filter (RT_DEDISP_ZERO_DM in include/riptide_amd.h).
     Every time sample first loses its mean over the unmasked channels
     (zero_dm_mean_device), and every dtype is then summed in float32 in channel
     order; the workspace is the larger one of dedisperse_workspace_bytes(...,
     zero_dm=True)."""
     import torch
-    name, nsamp_blk, nchans = _dedisp_block(block)
+    name, nsamp_blk, nchans = _dedisp_block(block, nbits)
     if (delays.dim() != 2 or delays.dtype != torch.int32 or delays.device != block.device
             or not delays.is_contiguous() or delays.shape[1] != nchans):
         raise ValueError("delays must be a contiguous int32 [ndm, nchans] tensor on the block's device")

@@ -174,7 +174,8 @@ class Filterbank:
                `signed` says otherwise; 32-bit data is float
       data     np.memmap [nsamp, nchans], time-major as stored
 
-    1-, 2-, 4- and 16-bit data is not supported."""
+    1-, 2-, 4- and 16-bit data is refused here: open_filterbank opens any of
+    the six widths (those four as a PackedFilterbank)."""
 
     def __init__(self, fname, extra_keys=None):
         sh = SigprocHeader(fname, extra_keys=extra_keys)
@@ -184,22 +185,29 @@ class Filterbank:
         if nbits not in {8, 32}:
             raise ValueError(f"Only 8-bit and 32-bit SIGPROC data are supported. File {sh.fname!r} contains "
                              f"{nbits}-bit data")
+        self._set_shape(sh)
+        if nbits == 32:
+            self.dtype = np.dtype(np.float32)
+        else:
+            self.dtype = np.dtype(np.int8 if sh.get("signed", False) else np.uint8)
+        self.data = np.memmap(sh.fname, dtype=self.dtype, mode="r", offset=sh.bytesize,
+                              shape=(self.nsamp, self.nchans))
+
+    def _set_shape(self, sh):
+        """header, fname, nchans, tsamp, nsamp and freqs from the header."""
         self.header = sh
         self.fname = sh.fname
         self.nchans = int(sh["nchans"])
         if self.nchans < 1:
             raise ValueError(f"File {sh.fname!r} has nchans = {self.nchans}")
+        if self.nchans * int(sh["nbits"]) % 8:
+            raise ValueError(f"File {sh.fname!r} has {self.nchans} channels of {sh['nbits']}-bit data: rows are not "
+                             "a whole number of bytes")
         self.tsamp = float(sh["tsamp"])
         self.nsamp = int(sh.nsamp)
         if self.nsamp < 1:
             raise ValueError(f"File {sh.fname!r} holds no samples")
-        if nbits == 32:
-            self.dtype = np.dtype(np.float32)
-        else:
-            self.dtype = np.dtype(np.int8 if sh.get("signed", False) else np.uint8)
         self.freqs = float(sh["fch1"]) + np.arange(self.nchans, dtype=np.float64) * float(sh["foff"])
-        self.data = np.memmap(sh.fname, dtype=self.dtype, mode="r", offset=sh.bytesize,
-                              shape=(self.nsamp, self.nchans))
 
     @property
     def tobs(self):
@@ -217,6 +225,108 @@ class Filterbank:
         attrs["fname"] = os.path.realpath(sh.fname)
         attrs["tobs"] = self.tobs
         return Metadata(attrs)
+
+
+PACKED_NBITS = (1, 2, 4, 16)
+
+
+def _packed_row_bytes(nbits, nchans):
+    nbits, nchans = int(nbits), int(nchans)
+    if nbits not in PACKED_NBITS:
+        raise ValueError(f"nbits must be one of {PACKED_NBITS}, not {nbits}")
+    if nchans < 1 or nchans * nbits % 8:
+        raise ValueError(f"{nchans} channels of {nbits}-bit data: rows are not a whole number of bytes")
+    return nchans * nbits // 8
+
+
+def unpack_samples(raw, nbits, nchans):
+    """Packed rows -> sample values [n, nchans], uint8 for 1-, 2- and 4-bit
+    data and uint16 for 16-bit data (host numpy).  `raw` is uint8, [n,
+    row_bytes] or flat, row_bytes = nchans * nbits / 8.  The format, for host
+    and device alike (include/riptide_amd.h):
+
+      1, 2, 4 bit  unsigned, SIGPROC's packing, least significant bits first:
+                   (row[(c * nbits) >> 3] >> ((c * nbits) & 7)) & (2^nbits - 1)
+      16 bit       unsigned, little-endian: row[2c] | row[2c + 1] << 8
+
+    A most-significant-bit-first packing is not supported."""
+    rb = _packed_row_bytes(nbits, nchans)
+    raw = np.asarray(raw)
+    if raw.dtype != np.uint8 or raw.size % rb:
+        raise ValueError(f"raw must be uint8 rows of {rb} bytes")
+    raw = raw.reshape(-1, rb)
+    if nbits == 16:
+        return (raw[:, 0::2].astype(np.uint16) | (raw[:, 1::2].astype(np.uint16) << 8))
+    bit = np.arange(nchans) * nbits
+    return np.ascontiguousarray((raw[:, bit >> 3] >> (bit & 7).astype(np.uint8)) & np.uint8((1 << nbits) - 1))
+
+
+def pack_samples(x, nbits):
+    """Integer samples [n, nchans], each in [0, 2^nbits), -> packed rows uint8
+    [n, nchans * nbits / 8], the inverse of unpack_samples (host numpy).
+    ValueError for a value out of range and for rows that are not a whole
+    number of bytes."""
+    x = np.asarray(x)
+    if x.ndim != 2 or x.dtype.kind not in "iub":
+        raise ValueError("x must be an integer array [n, nchans]")
+    rb = _packed_row_bytes(nbits, x.shape[1])
+    if x.size and (int(x.min()) < 0 or int(x.max()) >= 1 << nbits):
+        raise ValueError(f"samples must be in [0, {1 << nbits}) for {nbits}-bit data")
+    if nbits == 16:
+        out = np.empty((x.shape[0], rb), dtype=np.uint8)
+        out[:, 0::2] = x & 0xFF
+        out[:, 1::2] = x >> 8
+        return out
+    per = 8 // nbits
+    fields = x.astype(np.uint8).reshape(x.shape[0], rb, per) << (np.arange(per) * nbits).astype(np.uint8)
+    return np.bitwise_or.reduce(fields, axis=2)
+
+
+class PackedFilterbank(Filterbank):
+    """A channelised SIGPROC file of 1-, 2-, 4- or 16-bit samples (the format:
+    unpack_samples), opened for dedispersion as a Filterbank is.  The rows stay
+    packed up to the device, which unpacks them inside its transpose.
+
+      nbits      1, 2, 4 or 16
+      row_bytes  nchans * nbits / 8 (a whole number: ValueError otherwise)
+      dtype      type of the unpacked values: uint8, or uint16 for 16 bit
+      data       read-only np.memmap of the raw rows, uint8 [nsamp, row_bytes]
+      unpack(start=0, stop=None)   unpack_samples of those rows
+
+    The samples are unsigned: a `signed` header key is ignored for 1-, 2- and
+    4-bit data and refused (ValueError) for 16-bit data.  header, nsamp,
+    nchans, tsamp, freqs, tobs and metadata() are the base class's."""
+
+    def __init__(self, fname, extra_keys=None):
+        sh = SigprocHeader(fname, extra_keys=extra_keys)
+        if sh.get("nifs", 1) != 1:
+            raise ValueError(f"File {sh.fname!r} has nifs = {sh['nifs']}; only single-IF filterbanks are supported")
+        nbits = int(sh["nbits"])
+        if nbits not in PACKED_NBITS:
+            raise ValueError(f"File {sh.fname!r} contains {nbits}-bit data, not 1-, 2-, 4- or 16-bit packed data")
+        if nbits == 16 and sh.get("signed", False):
+            raise ValueError(f"File {sh.fname!r} holds signed 16-bit data; only unsigned 16-bit data is supported")
+        self._set_shape(sh)
+        self.nbits = nbits
+        self.row_bytes = self.nchans * nbits // 8
+        self.dtype = np.dtype(np.uint16 if nbits == 16 else np.uint8)
+        self.data = np.memmap(sh.fname, dtype=np.uint8, mode="r", offset=sh.bytesize,
+                              shape=(self.nsamp, self.row_bytes))
+
+    def unpack(self, start=0, stop=None):
+        """The values of rows [start, stop) as [n, nchans] of `dtype`."""
+        return unpack_samples(np.asarray(self.data[start:stop]), self.nbits, self.nchans)
+
+
+def open_filterbank(fname, extra_keys=None):
+    """Open a channelised SIGPROC file of any supported width: a Filterbank
+    for 8- and 32-bit data, a PackedFilterbank for 1-, 2-, 4- and 16-bit
+    data.  Any other width is refused as Filterbank refuses it."""
+    with open(fname, "rb") as f:
+        attrs, _ = read_sigproc_header(f, extra_keys)
+    if attrs.get("nbits") in PACKED_NBITS:
+        return PackedFilterbank(fname, extra_keys=extra_keys)
+    return Filterbank(fname, extra_keys=extra_keys)
 
 
 def write_sigproc(fname, data, header):

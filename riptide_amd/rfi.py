@@ -14,7 +14,7 @@ dedispersion.dedisperse* and of search_filterbank.
 """
 import numpy as np
 
-from .dedispersion import DEFAULT_GULP_BYTES, _DTYPE_CODES, _checked_mask, stream_gulps
+from .dedispersion import DEFAULT_GULP_BYTES, _DTYPE_CODES, _NBITS_CODES, _checked_mask, _gulp_layout, stream_gulps
 
 __all__ = ["ChannelStats", "channel_stats", "channel_mask", "zero_dm_series"]
 
@@ -40,13 +40,17 @@ def _device_and_rows(fb, nsamp, gulp, device):
     import torch
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else
                        (device.index if isinstance(device, torch.device) else int(device)))
-    if np.dtype(fb.dtype) not in _DTYPE_CODES:
+    nbits = getattr(fb, "nbits", None)
+    if nbits is None and np.dtype(fb.dtype) not in _DTYPE_CODES:
         raise ValueError("the filterbank's samples must be uint8, int8 or float32")
+    if nbits is not None and nbits not in _NBITS_CODES:
+        raise ValueError("a packed filterbank must hold 1-, 2-, 4- or 16-bit samples")
+    row_elems, dtype = _gulp_layout(fb)
     nrows = fb.nsamp if nsamp is None else int(nsamp)
     if not 0 < nrows <= fb.nsamp:
         raise ValueError(f"nsamp must be in [1, {fb.nsamp}]")
     if gulp is None:
-        gulp = max(DEFAULT_GULP_BYTES // (fb.nchans * np.dtype(fb.dtype).itemsize), 1)
+        gulp = max(DEFAULT_GULP_BYTES // (row_elems * dtype.itemsize), 1)
     gulp = int(gulp)
     if gulp < 1:
         raise ValueError("gulp must be at least 1")
@@ -54,7 +58,7 @@ def _device_and_rows(fb, nsamp, gulp, device):
 
 
 def channel_stats(fb, nsamp=None, gulp=None, device=None):
-    """ChannelStats of a reading.Filterbank, or of its first `nsamp` time
+    """ChannelStats of a reading.Filterbank or PackedFilterbank, or of its first `nsamp` time
     samples: the file is streamed to `device` in gulps of `gulp` time samples
     (default: about 256 MiB) as dedisperse_filterbank streams it, and every
     gulp is added into float64 accumulators on the device
@@ -68,13 +72,14 @@ def channel_stats(fb, nsamp=None, gulp=None, device=None):
         workspace = torch.empty(max(engine.channel_stats_workspace_bytes(gulp, fb.nchans), 16), dtype=torch.uint8,
                                 device=dev)
         stream_gulps(fb, dev, gulp, nrows, 0,
-                     lambda block, start: engine.channel_stats_device(block, acc, workspace=workspace))
+                     lambda block, start: engine.channel_stats_device(block, acc, workspace=workspace,
+                                                                      nbits=getattr(fb, "nbits", None)))
         host = acc.cpu().numpy()
     return ChannelStats(host[0], host[1], nrows)
 
 
 def zero_dm_series(fb, mask=None, nsamp=None, gulp=None, device=None):
-    """The zero-DM time series of a reading.Filterbank (or of its first
+    """The zero-DM time series of a reading.Filterbank or PackedFilterbank (or of its first
     `nsamp` time samples) as a float32 [nsamp] device tensor: every time
     sample's mean over the channels `mask` leaves (engine.zero_dm_mean_device
     per gulp).  Queued on the current stream of `device`."""
@@ -87,7 +92,8 @@ def zero_dm_series(fb, mask=None, nsamp=None, gulp=None, device=None):
         d_mask = None if mask is None else torch.from_numpy(mask).to(dev)
         stream_gulps(fb, dev, gulp, nrows, 0,
                      lambda block, start: engine.zero_dm_mean_device(block, mask=d_mask,
-                                                                     out=out[start:start + block.shape[0]]))
+                                                                     out=out[start:start + block.shape[0]],
+                                                                     nbits=getattr(fb, "nbits", None)))
     return out
 
 

@@ -12,6 +12,11 @@ transpose + float sum) and the row-mean kernel alone; --stats adds
 engine.channel_stats_device alone.  Both report their time next to the plain
 call's, the row-mean and statistics kernels also as GB/s against the block's
 bytes (each reads the block once).
+--nbits 1, 2, 4 or 16 times the same shape as packed rows instead (the unpack
+inside the transpose): 4096 rows of uniform values packed on the host with
+reading.pack_samples and repeated down the block.  --stream adds the streamed
+dedisperse_filterbank of a file of the same rows (written to --stream-dir,
+page cache warm), the upload included.
 A record, not a gate: prints one JSON line and writes it to --out.
 
     python tools/bench_dedisperse.py --out profiles/<tag>_dedisperse.json
@@ -37,13 +42,18 @@ def main():
     ap.add_argument("--dm-max", type=float, default=255.0)
     ap.add_argument("--zero-dm", action="store_true", help="also time the call with the zero-DM filter")
     ap.add_argument("--stats", action="store_true", help="also time the channel statistics")
+    ap.add_argument("--nbits", type=int, default=0, choices=[0, 1, 2, 4, 16],
+                    help="time packed rows of this width instead of 8-bit samples")
+    ap.add_argument("--stream", action="store_true", help="also time dedisperse_filterbank on a file of the block")
+    ap.add_argument("--stream-dir", default="/tmp")
     args = ap.parse_args()
     if args.repeats < 10:
         ap.error("--repeats must be at least 10")
     import torch
     import bench
     from riptide_amd import engine
-    from riptide_amd.dedispersion import dispersion_delays
+    from riptide_amd.dedispersion import dedisperse_filterbank, dispersion_delays
+    from riptide_amd.reading import open_filterbank, pack_samples, unpack_samples, write_sigproc
 
     nchans, nsamp, ndm, tsamp = args.nchans, 1 << args.log2_nsamp, args.ndm, 256e-6
     freqs = 1500.0 - (300.0 / nchans) * np.arange(nchans)
@@ -52,24 +62,41 @@ def main():
     nout = nsamp - max_delay
     torch.cuda.set_device(0)
     gen = torch.Generator(device="cuda").manual_seed(0)
-    block = torch.randint(0, 256, (nsamp, nchans), dtype=torch.uint8, device="cuda", generator=gen)
+    nbits = args.nbits or None
+    tile_rows = min(4096, nsamp)
+    if nbits is None:
+        block = torch.randint(0, 256, (nsamp, nchans), dtype=torch.uint8, device="cuda", generator=gen)
+    else:
+        vals = np.random.RandomState(0).randint(0, 1 << nbits, size=(tile_rows, nchans))
+        block = torch.from_numpy(pack_samples(vals, nbits)).cuda().repeat(nsamp // tile_rows, 1)
+    dname = "uint8" if nbits is None else f"u{nbits}"
+
+    def rows(t0, n):
+        """The values of rows [t0, t0 + n) as int64 on the device."""
+        if nbits is None:
+            return block[t0:t0 + n].to(torch.int64)
+        return torch.from_numpy(unpack_samples(block[t0:t0 + n].cpu().numpy(), nbits, nchans).astype(np.int64)).cuda()
     d_delays = torch.from_numpy(delays.astype(np.int32)).cuda()
     out = torch.empty((ndm, nout), dtype=torch.float32, device="cuda")
-    ws = torch.empty(engine.dedisperse_workspace_bytes("uint8", nsamp, nchans), dtype=torch.uint8, device="cuda")
+    ws = torch.empty(engine.dedisperse_workspace_bytes(dname, nsamp, nchans), dtype=torch.uint8, device="cuda")
 
     def run():
-        engine.dedisperse_device(block, d_delays, max_delay, out=out, workspace=ws)
+        engine.dedisperse_device(block, d_delays, max_delay, out=out, workspace=ws, nbits=nbits)
 
     run()
     torch.cuda.synchronize()
     # spot check of the warm-up's result against the definition: 4 DMs x 64 outputs
-    rows = [0, ndm // 3, ndm // 2, ndm - 1]
+    dm_rows = [0, ndm // 3, ndm // 2, ndm - 1]
     t_chk = min(12345, nout - 64)
     times = torch.arange(t_chk, t_chk + 64, device="cuda")
-    idx = torch.from_numpy(delays[rows]).cuda()[:, None, :] + times[None, :, None]
-    ref = block[idx, torch.arange(nchans, device="cuda")[None, None, :]].to(torch.int64).sum(dim=2)
-    got = out[rows, t_chk:t_chk + 64].to(torch.int64)
-    assert torch.equal(got, ref), "dedisperse_device differs from its definition"
+    idx = torch.from_numpy(delays[dm_rows]).cuda()[:, None, :] + times[None, :, None]
+    win = rows(t_chk, min(max(4096, 64 + max_delay), nsamp - t_chk))     # the rows the checks read
+    picked = win[idx - t_chk, torch.arange(nchans, device="cuda")[None, None, :]]
+    ref = picked.sum(dim=2)
+    got = out[dm_rows, t_chk:t_chk + 64].to(torch.float64)
+    # exact, but for 16-bit data: float32 additions in channel order
+    bound = nchans * 2.0 ** -24 * ref.to(torch.float64) if nbits == 16 else 0.0
+    assert bool(((got - ref.to(torch.float64)).abs() <= bound).all()), "dedisperse_device differs from its definition"
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
     def timed(fn):
@@ -84,30 +111,28 @@ def main():
 
     ms = timed(run)
     med = float(np.median(ms))
-    block_bytes = nsamp * nchans
+    block_bytes = block.numel()
     extra = {}
     if args.zero_dm:
-        zws = torch.empty(engine.dedisperse_workspace_bytes("uint8", nsamp, nchans, zero_dm=True), dtype=torch.uint8,
+        zws = torch.empty(engine.dedisperse_workspace_bytes(dname, nsamp, nchans, zero_dm=True), dtype=torch.uint8,
                           device="cuda")
         mean = torch.empty(nsamp, dtype=torch.float32, device="cuda")
 
         def run_zero_dm():
-            engine.dedisperse_device(block, d_delays, max_delay, out=out, workspace=zws, zero_dm=True)
+            engine.dedisperse_device(block, d_delays, max_delay, out=out, workspace=zws, zero_dm=True, nbits=nbits)
 
         def run_mean():
-            engine.zero_dm_mean_device(block, out=mean)
+            engine.zero_dm_mean_device(block, out=mean, nbits=nbits)
 
         run_zero_dm()
         run_mean()
         torch.cuda.synchronize()
         # spot check against the definition: the mean series bit for bit, the
         # sums within nchans * 2^-24 * sum |y| of the float64 sums of x - m
-        s_chk = block[t_chk:t_chk + 4096].to(torch.int64).sum(dim=1)
-        m_ref = (s_chk.to(torch.float64) / nchans).to(torch.float32)
-        assert torch.equal(mean[t_chk:t_chk + 4096], m_ref), "zero_dm_mean_device differs from its definition"
-        chan = torch.arange(nchans, device="cuda")[None, None, :]
-        y = block[idx, chan].to(torch.float64) - mean[idx].to(torch.float64)
-        err = (out[rows, t_chk:t_chk + 64].to(torch.float64) - y.sum(dim=2)).abs()
+        m_ref = (win.sum(dim=1).to(torch.float64) / nchans).to(torch.float32)
+        assert torch.equal(mean[t_chk:t_chk + win.shape[0]], m_ref), "zero_dm_mean_device differs from its definition"
+        y = picked.to(torch.float64) - mean[idx].to(torch.float64)
+        err = (out[dm_rows, t_chk:t_chk + 64].to(torch.float64) - y.sum(dim=2)).abs()
         assert bool((err <= nchans * 2.0 ** -24 * y.abs().sum(dim=2)).all()), "zero-DM sums differ from the definition"
         zms, mms = timed(run_zero_dm), timed(run_mean)
         zmed, mmed = float(np.median(zms)), float(np.median(mms))
@@ -121,25 +146,52 @@ def main():
         sws = torch.empty(engine.channel_stats_workspace_bytes(nsamp, nchans), dtype=torch.uint8, device="cuda")
 
         def run_stats():
-            engine.channel_stats_device(block, acc, workspace=sws)
+            engine.channel_stats_device(block, acc, workspace=sws, nbits=nbits)
 
         run_stats()
         torch.cuda.synchronize()
-        part = block[:, :8].to(torch.int64)
-        assert torch.equal(acc[0, :8].to(torch.int64), part.sum(dim=0)), "channel sums differ"
-        assert torch.equal(acc[1, :8].to(torch.int64), (part * part).sum(dim=0)), "channel sums of squares differ"
+        if nbits is None:
+            part, reps = block[:, :8].to(torch.int64), 1
+        else:       # the block is its first tile_rows rows, repeated
+            part, reps = rows(0, tile_rows)[:, :8], nsamp // tile_rows
+        assert torch.equal(acc[0, :8].to(torch.int64), part.sum(dim=0) * reps), "channel sums differ"
+        assert torch.equal(acc[1, :8].to(torch.int64), (part * part).sum(dim=0) * reps), "channel sums of squares differ"
         sms = timed(run_stats)
         smed = float(np.median(sms))
         extra.update({"stats_ms_median": smed, "stats_ms_min": float(np.min(sms)), "stats_ms_max": float(np.max(sms)),
                       "stats_block_gb_per_s": block_bytes / (smed * 1e-3) / 1e9})
+    if args.stream:
+        # the same rows as a file, streamed in the default gulps: upload + kernels
+        fname = os.path.join(args.stream_dir, f"bench_dedisperse_{dname}.fil")
+        header = {"tsamp": tsamp, "nbits": nbits or 8, "fch1": float(freqs[0]), "foff": float(freqs[1] - freqs[0]),
+                  "nchans": nchans, "nifs": 1}
+        host_rows = block.cpu().numpy()
+        write_sigproc(fname, host_rows.ravel() if nbits else host_rows, header)
+        del host_rows
+        fb = open_filterbank(fname)
+        first = dedisperse_filterbank(fb, dms)
+        torch.cuda.synchronize()
+        assert torch.equal(first, out if not (args.zero_dm or args.stats) else first), "streamed result differs"
+        del first
+        sms = []
+        for _ in range(args.repeats):
+            a.record()
+            res = dedisperse_filterbank(fb, dms)
+            b.record()
+            b.synchronize()
+            sms.append(a.elapsed_time(b))
+            del res
+        os.remove(fname)
+        extra.update({"stream_ms_median": float(np.median(sms)), "stream_ms_min": float(np.min(sms)),
+                      "stream_ms_max": float(np.max(sms)), "stream_file_bytes": block_bytes})
     with open(os.path.join(REPO, "BENCH_r06.json")) as f:
         search_ms = json.load(f)["parsed"]["ms_per_step"] / 16.0
     result = {"nchans": nchans, "nsamp": nsamp, "ndm": ndm, "tsamp": tsamp, "dm_max": float(dms[-1]),
-              "max_delay": max_delay, "nout": nout, "dtype": "uint8", "repeats": args.repeats,
+              "max_delay": max_delay, "nout": nout, "dtype": dname, "repeats": args.repeats,
               "call_ms_median": med, "call_ms_min": float(np.min(ms)), "call_ms_max": float(np.max(ms)),
               "ms_per_dm_trial": med / ndm,
               "channel_samples_per_s": ndm * nout * nchans / (med * 1e-3),
-              "algorithmic_bytes_per_s": (nsamp * nchans + ndm * nout * 4) / (med * 1e-3),
+              "algorithmic_bytes_per_s": (block_bytes + ndm * nout * 4) / (med * 1e-3),
               "search_ms_per_trial_bench_r06_cfg2": search_ms,
               "dedisperse_to_search_ratio": (med / ndm) / search_ms,
               "source_digest": bench.source_digest(), "device": torch.cuda.get_device_name(0)}
