@@ -220,6 +220,43 @@ int rt_deredden_normalise_device(const float* d_in, size_t size, size_t batch, s
                                  float* d_out, size_t out_stride, void* d_workspace, size_t workspace_bytes,
                                  void* stream);
 
+/* Host-only, no device: the kernel form each stage of
+ * rt_deredden_normalise_device takes for rows of `size` samples whose first
+ * row starts in_align / out_align bytes past a 16-byte boundary (the device
+ * addresses mod 16), with rows in_stride / out_stride floats apart.  A stage
+ * the call does not run reports 0.  The environment switches
+ * (RIPTIDE_AMD_INTERP_PER_SAMPLE, RIPTIDE_AMD_NORM_UNFUSED,
+ * RIPTIDE_AMD_NORM_SCALAR, RIPTIDE_AMD_RMED_COUNTING), which the launchers
+ * read per call, are not reflected.  Validates like the device call. */
+enum {
+    RT_SCRUNCH_STAGED_VEC = 1,   /* scrunch2_kernel, 16-byte staging loads */
+    RT_SCRUNCH_STAGED = 2,       /* scrunch2_kernel, 4-byte staging loads */
+    RT_SCRUNCH_GENERAL = 3,      /* scrunch_kernel (explicit-stack pairwise sum) */
+    RT_RMED_SMALL = 1,           /* rmed_run_kernel: width <= 255 */
+    RT_RMED_LARGE = 2,           /* rmed_large_kernel */
+    RT_SUBTRACT_PER_SAMPLE = 1,  /* deredden_subtract_kernel: scrunch factor 1, or 2^31 samples and more */
+    RT_SUBTRACT_SLOPE1 = 2,      /* deredden_slope1_kernel: rows off 16 bytes */
+    RT_SUBTRACT_SLOPE4 = 3,      /* deredden_slope_kernel: four-sample groups */
+    RT_NORM_SCALAR = 1,          /* norm_partial_kernel / norm_apply_kernel */
+    RT_NORM_VEC = 2              /* norm_partial4_kernel / norm_apply4_kernel */
+};
+typedef struct rt_dered_forms {
+    uint64_t scrunch_factor;   /* 1: no scrunch */
+    uint64_t n_lo;             /* samples the running median runs over */
+    uint64_t rmed_width;
+    uint32_t scrunch;          /* RT_SCRUNCH_* */
+    uint32_t scrunch_chunks;   /* runs of 8192 samples a block's sum is formed from (numpy's buffered reduction) */
+    uint32_t rmed;             /* RT_RMED_* */
+    uint32_t subtract;         /* RT_SUBTRACT_* */
+    uint32_t fused;            /* 1: the subtraction also sums the normalisation's statistics */
+    uint32_t norm_partial;     /* RT_NORM_*: the two statistics passes (0 when fused) */
+    uint32_t norm_passes;      /* 2: a thread of the statistics grid loads more than once (1 otherwise) */
+    uint32_t norm_apply;       /* RT_NORM_* */
+} rt_dered_forms;
+int rt_deredden_forms(size_t size, size_t width_samples, size_t min_points, int deredden, int normalise,
+                      unsigned in_align, unsigned out_align, size_t in_stride, size_t out_stride,
+                      rt_dered_forms* forms);
+
 /* ------------------------- peak detection (device) ------------------------ */
 /* The data-parallel stages of riptide.peak_detection.find_peaks
  * (peak_detection.py:37-142) over a batch of device periodograms in the

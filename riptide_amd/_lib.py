@@ -63,6 +63,8 @@ _SIGNATURES = {
     "rt_periodogram_passes_device": (_c_i, [_vp, _c_sz, _vp, _c_sz, _vp, _c_sz, _vp]),
     "rt_plan_check": (_c_i, [_vp, _vp]),
     "rt_deredden_workspace_bytes": (_c_i, [_c_sz, _c_sz, _c_sz, _c_sz, _psz]),
+    # size, width, min_points, deredden, normalise, in / out address mod 16, in / out stride, rt_dered_forms*
+    "rt_deredden_forms": (_c_i, [_c_sz, _c_sz, _c_sz, _c_i, _c_i, ctypes.c_uint, ctypes.c_uint, _c_sz, _c_sz, _vp]),
     "rt_deredden_normalise_device": (_c_i, [_vp, _c_sz, _c_sz, _c_sz, _c_sz, _c_sz, _c_i, _c_i, _vp, _c_sz,
                                             _vp, _c_sz, _vp]),
     "rt_profile_enable": (_c_i, [_c_i]),

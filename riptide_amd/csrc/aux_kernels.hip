@@ -105,8 +105,7 @@ hipError_t launch_snr_rows(const float* x, uint64_t rows, uint32_t cols, const u
 // statistic of x[clamp(i - w/2 + j, 0, n-1)], j in [0, w).  Exact: the result
 // is one of the window's values, as with the reference's quickselect.
 // ---------------------------------------------------------------------------
-constexpr int kRmedTile = 256;
-constexpr int kRmedSmallMax = 255;
+constexpr int kRmedTile = 256;   // (kRmedSmallMax, the widest staged window: dered_host.hpp)
 
 // Small windows: the block stages its span in LDS; one thread per output
 // counts, for each candidate, how many window values are < and <= it.
@@ -341,11 +340,11 @@ hipError_t launch_running_median(const float* x, uint64_t n, uint32_t width, flo
                                  uint64_t out_stride, uint32_t batch, hipStream_t s)
 {
     if (!n || !batch) return hipSuccess;
-    if (width <= (uint32_t)kRmedSmallMax && std::getenv("RIPTIDE_AMD_RMED_COUNTING")) {
+    if (rmed_small(width) && std::getenv("RIPTIDE_AMD_RMED_COUNTING")) {
         // A/B: one counting search per output
         hipLaunchKernelGGL(rmed_small_kernel, dim3((uint32_t)((n + kRmedTile - 1) / kRmedTile), batch),
                            dim3(kRmedTile), 0, s, x, n, (int)width, out, x_stride, out_stride);
-    } else if (width <= (uint32_t)kRmedSmallMax) {
+    } else if (rmed_small(width)) {
         // read per launch (like RIPTIDE_AMD_RMED_COUNTING), so one process
         // can test every run length
         const char* e = std::getenv("RIPTIDE_AMD_RMED_RUN");
@@ -426,15 +425,9 @@ __device__ float np_pairwise_sum(const float* a, int n)
 }
 
 // np_pairwise_sum for the counts whose halving tree has one level (n <= 128,
-// or both halves <= 128: np_pairwise_split2), without the general form's
-// explicit stack (private arrays indexed at run time live in scratch memory)
-__host__ __device__ inline bool np_pairwise_split2(int n)
-{
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    return n <= 128 || n - n2 <= 128;
-}
-
+// or both halves <= 128: np_pairwise_split2, dered_host.hpp), without the
+// general form's explicit stack (private arrays indexed at run time live in
+// scratch memory)
 __device__ __forceinline__ float np_pairwise_sum2(const float* a, int n)
 {
     if (n <= 128) return np_pairwise_leaf(a, n);
@@ -444,13 +437,12 @@ __device__ __forceinline__ float np_pairwise_sum2(const float* a, int n)
     return __fadd_rn(left, np_pairwise_leaf(a + n2, n - n2));
 }
 
-// scrunch_kernel for np_pairwise_split2(factor) <= kScrunchMaxFactor: 64
+// scrunch_kernel for scrunch_staged(factor) (dered_host.hpp): 64
 // outputs per block, their 64 * factor input samples staged in LDS by the
 // block's four waves with coalesced (16-byte where aligned) loads -- one
 // thread per output reading its own block straight from global memory
 // touched 64 cache lines per load instruction and re-fetched them from L2 --
 // then one lane per output sums its block from LDS in numpy's pairwise order.
-constexpr uint32_t kScrunchMaxFactor = 256;
 
 __global__ __launch_bounds__(256) void scrunch2_kernel(const float* __restrict__ x, uint64_t n_out, uint32_t factor,
                                                        float* __restrict__ out, uint64_t x_stride, uint64_t out_stride,
@@ -477,6 +469,9 @@ __global__ __launch_bounds__(256) void scrunch2_kernel(const float* __restrict__
 
 // scrunch(): mean of consecutive blocks of `factor` samples; numpy divides the
 // float32 sum by an np.intp count, i.e. in float64, then casts to float32.
+// The sum: numpy's buffered reduction hands its pairwise loop runs of
+// kNpBufSize samples (the last one shorter) and adds their sums in turn, so a
+// block longer than that is not one pairwise recursion.
 __global__ __launch_bounds__(256) void scrunch_kernel(const float* __restrict__ x, uint64_t n_out, uint32_t factor,
                                                       float* __restrict__ out, uint64_t x_stride, uint64_t out_stride)
 {
@@ -484,7 +479,9 @@ __global__ __launch_bounds__(256) void scrunch_kernel(const float* __restrict__ 
     if (i >= n_out) return;
     x += (uint64_t)blockIdx.y * x_stride + i * factor;
     out += (uint64_t)blockIdx.y * out_stride;
-    const float s = np_pairwise_sum(x, (int)factor);
+    float s = np_pairwise_sum(x, (int)(factor < kNpBufSize ? factor : kNpBufSize));
+    for (uint32_t off = kNpBufSize; off < factor; off += kNpBufSize)
+        s = __fadd_rn(s, np_pairwise_sum(x + off, (int)(factor - off < kNpBufSize ? factor - off : kNpBufSize)));
     out[i] = (float)((double)s / (double)factor);
 }
 
@@ -492,8 +489,8 @@ hipError_t launch_scrunch(const float* x, uint64_t n_out, uint32_t factor, float
                           uint64_t out_stride, uint32_t batch, hipStream_t s)
 {
     if (!n_out || !batch) return hipSuccess;
-    if (factor <= kScrunchMaxFactor && np_pairwise_split2((int)factor)) {
-        const int vec = ((uintptr_t)x % 16) == 0 && x_stride % 4 == 0 && (64 * factor) % 4 == 0;
+    if (scrunch_staged(factor)) {
+        const int vec = scrunch_vec((uintptr_t)x, x_stride, factor);
         hipLaunchKernelGGL(scrunch2_kernel, dim3((uint32_t)((n_out + 63) / 64), batch), dim3(256),
                            64 * factor * sizeof(float), s, x, n_out, factor, out, x_stride, out_stride, vec);
     }
@@ -735,12 +732,10 @@ hipError_t launch_deredden_subtract(const float* x, uint64_t n, const float* rme
                                     uint64_t out_stride, uint32_t batch, hipStream_t s, double* slopes)
 {
     if (!n || !batch) return hipSuccess;
-    if (slopes && factor > 1 && n_lo > 1 && n < (1ull << 31) && !std::getenv("RIPTIDE_AMD_INTERP_PER_SAMPLE")) {
+    if (dered_use_slopes(slopes != nullptr, n, n_lo, factor) && !std::getenv("RIPTIDE_AMD_INTERP_PER_SAMPLE")) {
         hipLaunchKernelGGL(interp_slope_kernel, dim3((uint32_t)((n_lo + 255) / 256), batch), dim3(256), 0, s, rmed_lo,
                            n_lo, factor, slopes, lo_stride);
-        const bool vec = ((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0 && x_stride % 4 == 0 &&
-                         out_stride % 4 == 0 && n < (1ull << 30);
-        if (vec)
+        if (dered_slope_vec((uintptr_t)x, (uintptr_t)out, n, x_stride, out_stride))
             hipLaunchKernelGGL(deredden_slope_kernel<false>, dim3((uint32_t)dered_norm_blocks(n), batch), dim3(256), 0,
                                s, x, (uint32_t)n, rmed_lo, (const double*)slopes, (uint32_t)n_lo, factor, out, x_stride,
                                lo_stride, out_stride, nullptr);
@@ -913,7 +908,7 @@ hipError_t launch_normalise(const float* x, uint64_t n, float* out, double* d_pa
 {
     if (!n || !batch) return hipSuccess;
     double* stats = d_partials + (uint64_t)batch * nblocks;
-    const bool vec_in = ((uintptr_t)x % 16) == 0 && x_stride % 4 == 0 && !std::getenv("RIPTIDE_AMD_NORM_SCALAR");
+    const bool vec_in = norm_vec_in((uintptr_t)x, x_stride) && !std::getenv("RIPTIDE_AMD_NORM_SCALAR");
     for (int mode = 0; mode < 2; ++mode) {
         if (vec_in)
             hipLaunchKernelGGL(norm_partial4_kernel, dim3(nblocks, batch), dim3(kNormBlock), 0, s, x, n, x_stride,
@@ -924,7 +919,7 @@ hipError_t launch_normalise(const float* x, uint64_t n, float* out, double* d_pa
         hipLaunchKernelGGL(norm_finalize_kernel, dim3(batch), dim3(kNormBlock), 0, s, d_partials, nblocks, n,
                            stats, mode);
     }
-    if (((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0 && x_stride % 4 == 0 && out_stride % 4 == 0)
+    if (norm_vec_apply((uintptr_t)x, (uintptr_t)out, x_stride, out_stride))
         hipLaunchKernelGGL(norm_apply4_kernel, dim3((uint32_t)((n + 1023) / 1024), batch), dim3(256), 0, s, x, n,
                            stats, out, x_stride, out_stride);
     else
@@ -936,9 +931,8 @@ hipError_t launch_normalise(const float* x, uint64_t n, float* out, double* d_pa
 bool dered_norm_fusable(const float* x, uint64_t n, uint64_t n_lo, uint32_t factor, const float* out,
                         uint64_t x_stride, uint64_t out_stride)
 {
-    return factor > 1 && n_lo > 1 && n < (1ull << 30) && ((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0 &&
-           x_stride % 4 == 0 && out_stride % 4 == 0 && !std::getenv("RIPTIDE_AMD_INTERP_PER_SAMPLE") &&
-           !std::getenv("RIPTIDE_AMD_NORM_UNFUSED");
+    return dered_norm_fusable_geom((uintptr_t)x, (uintptr_t)out, n, n_lo, factor, x_stride, out_stride) &&
+           !std::getenv("RIPTIDE_AMD_INTERP_PER_SAMPLE") && !std::getenv("RIPTIDE_AMD_NORM_UNFUSED");
 }
 
 hipError_t launch_deredden_normalise(const float* x, uint64_t n, const float* rmed_lo, uint64_t n_lo,

@@ -204,4 +204,31 @@ int rt_deredden_workspace_bytes(size_t size, size_t ws, size_t minpts, size_t ba
     });
 }
 
+int rt_deredden_forms(size_t size, size_t ws, size_t minpts, int deredden, int normalise, unsigned in_align,
+                      unsigned out_align, size_t in_stride, size_t out_stride, rt_dered_forms* forms)
+{
+    return guarded([&] {
+        if (!forms) throw std::invalid_argument("rt_deredden_forms: forms is NULL");
+        if (in_align >= 16 || out_align >= 16 || in_align % 4 || out_align % 4)
+            throw std::invalid_argument("rt_deredden_forms: an alignment is a float address mod 16");
+        const DeredGeom g = dered_geom(size, ws, minpts, 1, deredden != 0);
+        const DeredForms f =
+            dered_forms(g, size, deredden != 0, normalise != 0, in_align, out_align, in_stride, out_stride);
+        rt_dered_forms o{};
+        o.scrunch_factor = g.sf;
+        o.n_lo = g.n_lo;
+        o.rmed_width = g.rmed_w;
+        o.scrunch = f.scrunch;
+        o.scrunch_chunks = f.scrunch_chunks;
+        o.rmed = f.rmed;
+        o.subtract = f.subtract;
+        o.fused = f.fused;
+        o.norm_partial = f.norm_partial;
+        o.norm_passes = f.norm_passes;
+        o.norm_apply = f.norm_apply;
+        *forms = o;
+        return RT_OK;
+    });
+}
+
 }  // extern "C"

@@ -1,7 +1,8 @@
 // Host-only checker of the planning that the C ABI's device files rely on,
 // built with AddressSanitizer + UBSan by `make -C riptide_amd/csrc asan`:
 //   fold      fold_plan / fold_check_ranges / rt_fold_workspace_bytes (fold_host.hpp)
-//   dered     dered_geom / dered_ws_layout / dered_ws_bytes (dered_host.hpp)
+//   dered     dered_geom / dered_ws_layout / dered_ws_bytes / dered_forms and
+//             rt_deredden_forms (dered_host.hpp)
 //   harmonic  hresolve_tile (harmonic_host.hpp)
 // Every array is a heap block of exactly the size the code may touch.  No
 // device call, and none linked.  Usage: host_check [fold|dered|harmonic]
@@ -149,6 +150,87 @@ void check_fold()
 }
 
 // ---- dered
+// rt_deredden_forms against the predicates it is built from, each record a
+// heap block of exact size: over scrunch factors on both sides of every
+// switch, both alignments of either buffer, strides that keep and break the
+// 16-byte rows, and the three stage selections.
+void check_dered_forms()
+{
+    const size_t factors[] = {1, 2, 4, 128, 129, 248, 249, 255, 256, 257, 773, 8192, 8193, 16385};
+    const size_t minpts[] = {1, 3, 255, 257};
+    size_t seen_scrunch[4] = {0, 0, 0, 0}, seen_sub[4] = {0, 0, 0, 0}, fused = 0, two_pass = 0, calls = 0;
+    for (size_t sf : factors)
+        for (size_t mp : minpts)
+            for (size_t n_lo : {mp + 1, mp + 70})
+                for (size_t tail : {(size_t)0, sf - 1})
+                    for (unsigned ia : {0u, 4u})
+                        for (unsigned oa : {0u, 12u})
+                            for (size_t pad : {(size_t)0, (size_t)1, (size_t)4})
+                                for (int mode = 1; mode < 4; ++mode) {
+                                    const size_t n = n_lo * sf + tail, ws = sf * mp;
+                                    const bool dered = mode & 1, norm = mode & 2;
+                                    const bool in16 = ia == 0 && (n + pad) % 4 == 0, out16 = oa == 0 && (n + 2 * pad) % 4 == 0;
+                                    std::unique_ptr<rt_dered_forms> f(new rt_dered_forms);
+                                    std::memset(f.get(), 0xff, sizeof(rt_dered_forms));
+                                    const int rc = rt_deredden_forms(n, ws, mp, dered, norm, ia, oa, n + pad, n + 2 * pad,
+                                                                     f.get());
+                                    expect(rc == RT_OK, "dered forms: accepted");
+                                    if (rc != RT_OK) continue;
+                                    ++calls;
+                                    const DeredGeom g = dered_geom(n, ws, mp, 1, dered);
+                                    expect(f->scrunch_factor == g.sf && f->n_lo == g.n_lo && f->rmed_width == g.rmed_w,
+                                           "dered forms: geometry");
+                                    expect(f->scrunch <= RT_SCRUNCH_GENERAL && f->subtract <= RT_SUBTRACT_SLOPE4 &&
+                                               f->rmed <= RT_RMED_LARGE && f->fused <= 1 && f->norm_partial <= RT_NORM_VEC &&
+                                               f->norm_apply <= RT_NORM_VEC && f->norm_passes <= 2,
+                                           "dered forms: values in range");
+                                    ++seen_scrunch[f->scrunch];
+                                    ++seen_sub[f->subtract];
+                                    fused += f->fused;
+                                    two_pass += f->norm_passes == 2;
+                                    if (!dered) {
+                                        expect(!f->scrunch && !f->rmed && !f->subtract && !f->fused && f->scrunch_factor == 1,
+                                               "dered forms: no dereddening stage");
+                                    } else {
+                                        expect((f->scrunch == 0) == (g.sf == 1) &&
+                                                   (f->scrunch == RT_SCRUNCH_GENERAL) == (g.sf > 1 && !scrunch_staged((uint32_t)g.sf)) &&
+                                                   f->scrunch_chunks == (g.sf > 1 ? scrunch_chunks((uint32_t)g.sf) : 0),
+                                               "dered forms: scrunch");
+                                        if (f->scrunch == RT_SCRUNCH_STAGED_VEC)
+                                            expect(in16, "dered forms: staged loads aligned");
+                                        expect((f->rmed == RT_RMED_SMALL) == (g.rmed_w <= 255), "dered forms: rmed");
+                                        expect((f->subtract == RT_SUBTRACT_PER_SAMPLE) == (g.sf == 1), "dered forms: per sample");
+                                        if (f->subtract == RT_SUBTRACT_SLOPE4)
+                                            expect(in16 && out16, "dered forms: groups aligned");
+                                        expect(f->fused == (norm && f->subtract == RT_SUBTRACT_SLOPE4), "dered forms: fused");
+                                    }
+                                    expect((f->norm_apply != 0) == norm && (f->norm_partial != 0) == (norm && !f->fused),
+                                           "dered forms: normalisation stages");
+                                    if (f->norm_apply == RT_NORM_VEC)
+                                        expect(out16 && (dered || in16), "dered forms: apply aligned");
+                                }
+    expect(calls > 5000 && seen_scrunch[0] && seen_scrunch[1] && seen_scrunch[2] && seen_scrunch[3] && seen_sub[1] &&
+               seen_sub[2] && seen_sub[3] && fused && two_pass,
+           "dered forms: the sweep reaches every form");
+    // the statistics grid's second load: n / 4 and n against kNormBlocks * 256
+    for (size_t n : {(size_t)131072, (size_t)131073, (size_t)524291, (size_t)524292}) {
+        std::unique_ptr<rt_dered_forms> v(new rt_dered_forms), s(new rt_dered_forms);
+        const size_t stride = (n + 3) / 4 * 4;
+        expect(rt_deredden_forms(n, 5, 3, 0, 1, 0, 0, stride, stride, v.get()) == RT_OK &&
+                   rt_deredden_forms(n, 5, 3, 0, 1, 4, 0, stride, stride, s.get()) == RT_OK,
+               "dered forms: normalise only");
+        expect(v->norm_partial == RT_NORM_VEC && v->norm_passes == (n / 4 > 131072 ? 2u : 1u) &&
+                   s->norm_partial == RT_NORM_SCALAR && s->norm_passes == (n > 131072 ? 2u : 1u),
+               "dered forms: norm_passes");
+    }
+    std::unique_ptr<rt_dered_forms> f(new rt_dered_forms);
+    expect(rt_deredden_forms(1000, 100, 4, 1, 1, 0, 0, 1000, 1000, f.get()) == RT_EINVAL &&
+               rt_deredden_forms(1000, 100, 3, 1, 1, 2, 0, 1000, 1000, f.get()) == RT_EINVAL &&
+               rt_deredden_forms(1000, 100, 3, 1, 1, 0, 16, 1000, 1000, f.get()) == RT_EINVAL &&
+               rt_deredden_forms(1000, 100, 3, 1, 1, 0, 0, 1000, 1000, nullptr) == RT_EINVAL,
+           "dered forms: refusals");
+}
+
 void check_dered()
 {
     const size_t sizes[] = {30011, 32768, 4097, 1000};   // 30011: the GPU dereddening tests' series
@@ -193,6 +275,7 @@ void check_dered()
                         }
                     }
     expect(cases > 100 && sf1 > 0 && sfn > 0, "dered: the sweep covers sf == 1 and sf > 1");
+    check_dered_forms();
 }
 
 // ---- harmonic

@@ -200,6 +200,33 @@ def deredden_workspace_bytes(size, width_samples, min_points, batch):
     return b.value
 
 
+# rt_dered_forms and its RT_* values (include/riptide_amd.h)
+DERED_FORMS_DTYPE = np.dtype([("scrunch_factor", np.uint64), ("n_lo", np.uint64), ("rmed_width", np.uint64),
+                              ("scrunch", np.uint32), ("scrunch_chunks", np.uint32), ("rmed", np.uint32),
+                              ("subtract", np.uint32), ("fused", np.uint32), ("norm_partial", np.uint32),
+                              ("norm_passes", np.uint32), ("norm_apply", np.uint32)])
+SCRUNCH_STAGED_VEC, SCRUNCH_STAGED, SCRUNCH_GENERAL = 1, 2, 3
+RMED_SMALL, RMED_LARGE = 1, 2
+SUBTRACT_PER_SAMPLE, SUBTRACT_SLOPE1, SUBTRACT_SLOPE4 = 1, 2, 3
+NORM_SCALAR, NORM_VEC = 1, 2
+
+
+def deredden_forms(size, width_samples, min_points=101, deredden=True, normalise=True, in_align=0, out_align=0,
+                   in_stride=None, out_stride=None):
+    """The kernel form each stage of deredden_normalise takes for rows of
+    `size` samples at device addresses in_align / out_align bytes past a
+    16-byte boundary, in_stride / out_stride floats apart (default: size), as
+    a dict of DERED_FORMS_DTYPE's fields (rt_deredden_forms; host only, no
+    device).  A stage that does not run is 0; the environment switches are not
+    reflected."""
+    rec = np.zeros(1, dtype=DERED_FORMS_DTYPE)
+    _check(_L.rt_deredden_forms(int(size), int(width_samples), int(min_points), int(bool(deredden)),
+                                int(bool(normalise)), int(in_align), int(out_align),
+                                int(size if in_stride is None else in_stride),
+                                int(size if out_stride is None else out_stride), _lib.ptr(rec)))
+    return {k: int(rec[k][0]) for k in DERED_FORMS_DTYPE.names}
+
+
 def deredden_normalise(data, width_samples, min_points=101, deredden=True, normalise=True, out=None,
                        workspace=None, stream=None):
     """TimeSeries.deredden(...).normalise() for a batch [B, N] of device series."""

@@ -211,6 +211,81 @@ def test_ladder_oracle_cases_cover_the_kernel():
     assert any(c["n"] % 2 for c in inputs.LADDER_ORACLE_CASES) and clipped >= 8
 
 
+def test_dered_cases_cover_the_kernels(lib):
+    """dered_common.CASES x LAYOUTS (tests/test_gpu_dered.py) really reaches
+    every kernel form of dereddening and normalisation, by the launchers' own
+    predicates (rt_deredden_forms): a condition on the case table -- if a
+    form goes missing, the table is what to fix."""
+    import dered_common as dc
+    from riptide_amd import engine as E
+    assert len(set(dc.CASE_NAMES)) == len(dc.CASES)
+    src = open(os.path.join(REPO, "riptide_amd", "csrc", "dered_host.hpp")).read()
+    assert int(re.search(r"^constexpr uint32_t kNpBufSize = (\d+);$", src, re.M).group(1)) == 8192
+    assert int(re.search(r"^constexpr uint32_t kNormBlocks = (\d+);$", src, re.M).group(1)) * 256 == 131072
+    seen = {}          # (mode, field) -> values
+    by_factor = {}     # scrunch factor -> [(n_lo, tail)]
+    for c in dc.CASES:
+        assert c["n"] <= 1100000 + 16385, c["name"]
+        for lay in dc.LAYOUTS:
+            for mode, (dered, norm) in {"dered": (1, 0), "both": (1, 1), "norm": (0, 1)}.items():
+                f = E.deredden_forms(c["n"], c["ws"], c["mp"], dered, norm, **dc.forms_args(c, lay))
+                for k, v in f.items():
+                    seen.setdefault((mode, k), set()).add(v)
+                if mode == "dered":
+                    assert f["scrunch_factor"] == dc.factor(c) and f["n_lo"] == (c["n"] // dc.factor(c))
+                    by_factor.setdefault(f["scrunch_factor"], set()).add((f["n_lo"], c["n"] % f["scrunch_factor"]))
+                    # the forms' own definitions, restated
+                    sf = f["scrunch_factor"]
+                    n2 = sf // 2 - sf // 2 % 8
+                    staged = sf <= 256 and (sf <= 128 or sf - n2 <= 128)
+                    assert (f["scrunch"] == 0) == (sf == 1) and (f["scrunch"] == E.SCRUNCH_GENERAL) == (sf > 1 and not staged)
+                    assert f["scrunch_chunks"] == (0 if sf == 1 else -(-sf // 8192))
+                    assert f["rmed"] == (E.RMED_SMALL if f["rmed_width"] <= 255 else E.RMED_LARGE)
+                    assert (f["subtract"] == E.SUBTRACT_PER_SAMPLE) == (sf == 1)
+    # every form of every stage
+    assert seen["dered", "scrunch"] == {0, E.SCRUNCH_STAGED_VEC, E.SCRUNCH_STAGED, E.SCRUNCH_GENERAL}
+    assert seen["dered", "rmed"] == {E.RMED_SMALL, E.RMED_LARGE}
+    assert seen["dered", "subtract"] == {E.SUBTRACT_PER_SAMPLE, E.SUBTRACT_SLOPE1, E.SUBTRACT_SLOPE4}
+    assert seen["dered", "fused"] == {0} and seen["both", "fused"] == {0, 1} and seen["norm", "subtract"] == {0}
+    for mode in ("both", "norm"):
+        assert seen[mode, "norm_partial"] >= {E.NORM_SCALAR, E.NORM_VEC}
+        assert seen[mode, "norm_apply"] == {E.NORM_SCALAR, E.NORM_VEC} and seen[mode, "norm_passes"] >= {1, 2}
+    # the statistics kernels' loops on each side of one grid: n / 4 and n against 131072
+    long = next(c for c in dc.CASES if c["name"] == "long_f5")
+    assert long["n"] // 4 > 2 * 131072 and long["n"] % 4 == 3 and (long["n"] // 4) % 131072 not in (0, 131071)
+    for lay, part in (("aligned", E.NORM_VEC), ("in_off", E.NORM_SCALAR)):
+        f = E.deredden_forms(long["n"], long["ws"], long["mp"], 0, 1, **dc.forms_args(long, lay))
+        assert (f["norm_partial"], f["norm_passes"]) == (part, 2)
+    assert sum(c["n"] // 4 <= 131072 for c in dc.CASES) > 100
+    # the scrunch: every factor of dc.FACTORS, each with n_lo = min_points + 1 and n_lo past a 64-output
+    # block, and tails of 0, 1 and factor - 1 samples; staged factors at 129-248, 256 (64 KiB of LDS),
+    # the general kernel at 249-255 and above 256, and on each side of numpy's buffer size
+    for sf in dc.FACTORS:
+        los, tails = {lo for lo, _ in by_factor[sf]}, {t for _, t in by_factor[sf]}
+        assert min(los) <= 6 and max(los) >= 67 and tails >= {0, 1, sf - 1}, sf
+    general = {sf for sf in by_factor if sf > 1 and not (sf <= 128 or (sf <= 256 and sf - (sf // 2 - sf // 2 % 8) <= 128))}
+    assert {249, 255, 257, 773} <= general and {129, 200, 248, 256} & general == set()
+    assert seen["dered", "scrunch_chunks"] >= {0, 1, 2, 3} and {8192, 8193} <= set(by_factor)
+    # the interpolation's edges: one slope, even and odd factors from 2 up, the first factors of the
+    # two-segment path, every n mod 4 below one 4096-sample block, and a four-sample group over xp[0] and xp[last]
+    small = [c for c in dc.CASES if c["n"] < 4096]
+    assert any(c["n"] // dc.factor(c) == 2 for c in small)
+    assert {c["n"] % 4 for c in small if dc.factor(c) in (4, 5)} == {0, 1, 2, 3}
+    assert {2, 3, 4, 5} <= set(by_factor)
+    last_in_group = {(((c["n"] // dc.factor(c)) - 1) * dc.factor(c) + (dc.factor(c) - 1) // 2) % 4
+                     for c in dc.CASES if dc.factor(c) >= 4}
+    assert last_in_group == {0, 1, 2, 3}
+    # refusals, as the device call's
+    rec = np.zeros(1, dtype=E.DERED_FORMS_DTYPE)
+    from riptide_amd._lib import ptr
+    assert lib.rt_deredden_forms(1000, 100, 3, 1, 1, 0, 0, 1000, 1000, ptr(rec)) == 0
+    for bad in ((1000, 100, 4, 1, 1, 0, 0),      # even min_points
+                (99, 99, 99, 1, 1, 0, 0),         # width not below size
+                (1000, 100, 3, 1, 1, 2, 0), (1000, 100, 3, 1, 1, 0, 16)):   # no float address mod 16
+        assert lib.rt_deredden_forms(*bad, 1000, 1000, ptr(rec)) == 1, bad
+    assert lib.rt_deredden_forms(1000, 100, 3, 1, 1, 0, 0, 1000, 1000, None) == 1
+
+
 def test_version(lib):
     assert b"gfx950" in lib.rt_version()
 
@@ -565,7 +640,9 @@ def test_asan_host_check(mode):
     test_fold_host.py and a table of all three modes with staged and unstaged
     factors, every candidate's rows and result inside the reported workspace
     and output.  dered: the four workspace regions over (size, width,
-    min_points, batch), scrunch factor 1 and above.  harmonic: the tile
+    min_points, batch), scrunch factor 1 and above, and rt_deredden_forms
+    against the launchers' predicates over factors, alignments, strides and
+    stage selections.  harmonic: the tile
     resolution against the plain rank-order loop for n in {2, 63, 64, 65, 130}
     and 1, 7, n - 1 rows per tile, with near pairs, a tile past the near cap,
     and out-of-range near pairs (the library's own error)."""
