@@ -537,6 +537,44 @@ int rt_dedisperse_device_opt(const void* d_block, int dtype, size_t nsamp_blk, s
                              size_t workspace_bytes, void* stream, uint32_t flags);
 int rt_dedisperse_opt(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
                       const uint8_t* mask, size_t ndm, int64_t max_delay, float* out, uint32_t flags);
+/* ---- sub-band sums: every band of a table from one pass over the block */
+/* A band is a half-open channel range [lo, hi); bands is uint32 [nbands][2].
+ * Bands may overlap, be empty, come in any order and cover the whole file:
+ *   out[d, b, t] = sum over unmasked c in [lo_b, hi_b) of x[t + delay[d, c], c]
+ * The delays are those of the plain call, against the highest frequency of the
+ * whole file, so the bands stay aligned with each other.  The sums are the
+ * plain call's: exact integers for 8-bit and 1/2/4-bit data, float32 additions
+ * in ascending channel order within the band for float and 16-bit data; the
+ * row of the band [0, nchans) is the plain call's row, bit for bit.  With
+ * RT_DEDISP_ZERO_DM m[t] is still the mean over the unmasked channels of the
+ * whole file, and y is summed in float32 over the band.  A band with no
+ * unmasked channel gives zeros.
+ * The device call takes at most RT_DEDISP_MAX_BANDS bands (a grid layer each). */
+#define RT_DEDISP_MAX_BANDS 65535
+/* Host only, no device: the specification.  rt_dedisperse_host_opt with a band
+ * table, out [ndm, nbands, nout].  RT_EINVAL for a band with lo > hi or hi >
+ * nchans, a NULL bands with nbands > 0, and everything rt_dedisperse_host_opt
+ * refuses; nbands == 0 writes nothing. */
+int rt_dedisperse_bands_host(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
+                             const uint8_t* mask, size_t ndm, const uint32_t* bands, size_t nbands,
+                             int64_t max_delay, size_t nout, float* out, uint32_t flags);
+/* rt_dedisperse_device_opt with a band table in device memory, d_bands uint32
+ * [nbands][2] (4-byte aligned): writes d_out[(d * nbands + b) * out_stride +
+ * out_offset + t] for t in [0, nsamp_blk - max_delay).  The band edges are
+ * clamped as they are read, hi to nchans and lo to hi, as delays are clamped:
+ * no load leaves the block or the workspace.  The workspace is that of
+ * rt_dedisperse_workspace_bytes_opt.  RT_EINVAL (nothing is launched) for
+ * nbands == 0, nbands > RT_DEDISP_MAX_BANDS, ndm * nbands >= 2^32, a NULL
+ * d_bands, and everything rt_dedisperse_device_opt refuses. */
+int rt_dedisperse_bands_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans,
+                               const int32_t* d_delays, const uint8_t* d_mask, size_t ndm, const uint32_t* d_bands,
+                               size_t nbands, int64_t max_delay, float* d_out, size_t out_stride, size_t out_offset,
+                               void* d_workspace, size_t workspace_bytes, void* stream, uint32_t flags);
+/* Host-buffer form, as rt_dedisperse_opt: out [ndm, nbands, nsamp - max_delay].
+ * Synchronous.  Also RT_EINVAL for a band with lo > hi or hi > nchans. */
+int rt_dedisperse_bands(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
+                        const uint8_t* mask, size_t ndm, const uint32_t* bands, size_t nbands, int64_t max_delay,
+                        float* out, uint32_t flags);
 /* Host only, no device: the zero-DM mean series m [nsamp] of x [nsamp, nchans]
  * as defined above (mask NULL or [nchans], non-zero = channel skipped).
  * RT_EINVAL for an unknown type code, nchans == 0, or 8-bit data of more than

@@ -113,6 +113,13 @@ _SIGNATURES = {
     "rt_dedisperse_device_opt": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _c_sz, ctypes.c_int64, _vp, _c_sz, _c_sz,
                                         _vp, _c_sz, _vp, ctypes.c_uint32]),
     "rt_dedisperse_opt": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _c_sz, ctypes.c_int64, _vp, ctypes.c_uint32]),
+    # the band forms: bands (uint32 [nbands, 2]) and nbands behind ndm, flags last
+    "rt_dedisperse_bands_host": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _c_sz, _vp, _c_sz, ctypes.c_int64, _c_sz,
+                                        _vp, ctypes.c_uint32]),
+    "rt_dedisperse_bands_device": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _c_sz, _vp, _c_sz, ctypes.c_int64, _vp,
+                                          _c_sz, _c_sz, _vp, _c_sz, _vp, ctypes.c_uint32]),
+    "rt_dedisperse_bands": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _c_sz, _vp, _c_sz, ctypes.c_int64, _vp,
+                                   ctypes.c_uint32]),
     # x, dtype, nsamp, nchans, mask, m
     "rt_zero_dm_mean_host": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp]),
     # block, dtype, nsamp_blk, nchans, mask, m, stream

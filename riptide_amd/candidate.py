@@ -2,11 +2,16 @@
 the stage that builds them from peak clusters (pipeline/pipeline.py:86-133,
 292-333).  Each DM trial is loaded, dereddened and normalised once, and all
 of its clusters are folded by one batched device call (folding.fold_many).
+build_candidates_filterbank starts from the channelised file instead: it
+dedisperses, normalises and folds on the device, and its candidates also carry
+the fold of every sub-band, the frequency-phase diagnostic.
 Plotting is not part of this module.
 """
 import logging
 import traceback
-from collections import defaultdict
+from collections import defaultdict, namedtuple
+
+import numpy as np
 
 from .folding import check_fold_args, fold_many, fold_shape
 
@@ -32,13 +37,19 @@ class Candidate:
     peaks: pandas.DataFrame of the member peaks of its cluster.
     subints: folded sub-integrations, (num_subints, num_bins), or (num_bins,)
         for a single one.
+    subbands: None, or the same fold of every sub-band of the channelised
+        data, float32 (num_bands, num_subints, num_bins), or (num_bands,
+        num_bins) for a single sub-integration (build_candidates_filterbank).
+    band_freqs: None, or the mean channel frequency of each sub-band in MHz.
     """
 
-    def __init__(self, params, tsmeta, peaks, subints):
+    def __init__(self, params, tsmeta, peaks, subints, subbands=None, band_freqs=None):
         self.params = params
         self.tsmeta = tsmeta
         self.peaks = peaks
         self.subints = subints
+        self.subbands = subbands
+        self.band_freqs = band_freqs
 
     @property
     def profile(self):
@@ -51,12 +62,26 @@ class Candidate:
         best = self.peaks.copy().groupby("dm").max()
         return best.index.values, best.snr.values
 
+    @property
+    def freq_phase(self):
+        """Frequency against phase, (num_bands, num_bins): every sub-band's
+        folded profile.  None without sub-bands."""
+        if self.subbands is None:
+            return None
+        return self.subbands if self.subbands.ndim == 2 else self.subbands.sum(axis=1)
+
     def to_dict(self):
-        return {"params": self.params, "tsmeta": self.tsmeta, "peaks": self.peaks, "subints": self.subints}
+        items = {"params": self.params, "tsmeta": self.tsmeta, "peaks": self.peaks, "subints": self.subints}
+        if self.subbands is not None:
+            items["subbands"] = self.subbands
+        if self.band_freqs is not None:
+            items["band_freqs"] = self.band_freqs
+        return items
 
     @classmethod
     def from_dict(cls, items):
-        return cls(items["params"], items["tsmeta"], items["peaks"], items["subints"])
+        return cls(items["params"], items["tsmeta"], items["peaks"], items["subints"],
+                   subbands=items.get("subbands"), band_freqs=items.get("band_freqs"))
 
     @classmethod
     def from_folded(cls, ts, peak_cluster, subints_array):
@@ -147,6 +172,96 @@ def build_candidates(clusters, load_series, range_confs, deredden_params):
                 log.error(traceback.format_exc())
         for cl, arr in zip(todo, fold_many(ts, specs)):
             candidates.append(Candidate.from_folded(ts, cl, arr))
+    candidates.sort(key=lambda c: c.params["snr"], reverse=True)
+    log.info(f"Total candidates: {len(candidates)}")
+    return candidates
+
+
+class _SeriesShape(namedtuple("_SeriesShape", "nsamp tsamp")):
+    """What candidate_fold_spec asks of a TimeSeries, for series that stay on
+    the device."""
+
+    @property
+    def length(self):
+        return self.nsamp * self.tsamp
+
+
+def build_candidates_filterbank(clusters, fb_or_fname, range_confs, deredden_params, nsub=32, mask=None,
+                                zero_dm=False, kdm=None, nout=None, budget_bytes=None, device=None):
+    """Candidates of a list of PeakClusters, by decreasing S/N, straight from
+    the channelised file (a name for reading.open_filterbank, or a Filterbank /
+    PackedFilterbank): build_candidates without a load_series, and every
+    Candidate also carries `subbands`, the fold of each of `nsub` contiguous
+    sub-bands (dedispersion.band_edges), and `band_freqs`.
+
+    The distinct centre DMs are taken in batches sized by budget_bytes (default:
+    dedispersion.DEFAULT_BUDGET_BYTES; the band series and their normalised copy
+    are counted).  A batch is one pass over the file: dedispersion.band_series
+    gives every DM's nsub sub-bands and, as the last band, the full band,
+    dereddened (deredden_params: rmed_width, rmed_minpts) and normalised; one
+    engine.fold_device call then folds every (cluster, band) with the bins /
+    subints of the cluster's period range.  `subints` is the full-band fold,
+    what build_candidates gives for the same series; a sub-band with no
+    unmasked channel folds to zeros.
+
+    nout: samples of every series (default: nsamp minus the largest delay over
+    those DMs; pass the search's own nout to fold exactly what was searched).
+    mask, zero_dm, kdm: as for search_filterbank.  tsmeta is the file's
+    metadata with `dm` set, as search_filterbank's trials have it.  A cluster
+    that cannot be folded is logged and left out."""
+    import torch
+    from . import engine
+    from .dedispersion import DEFAULT_BUDGET_BYTES, KDM, band_edges, band_series, dispersion_delays
+    from .reading import Filterbank, open_filterbank
+    fb = fb_or_fname if isinstance(fb_or_fname, Filterbank) else open_filterbank(fb_or_fname)
+    kdm = KDM if kdm is None else float(kdm)
+    budget_bytes = DEFAULT_BUDGET_BYTES if budget_bytes is None else int(budget_bytes)
+    ordered = sorted(clusters, key=lambda c: c.centre.snr, reverse=True)
+    if not ordered:
+        log.info("No clusters: no candidates to build")
+        return []
+    by_dm = defaultdict(list)
+    for cl in ordered:
+        by_dm[float(cl.centre.dm)].append(cl)
+    dms = list(by_dm)
+    log.debug(f"{len(ordered)} candidates to build from {len(dms)} DMs of {fb.header.fname}")
+    _, max_delay = dispersion_delays(fb.freqs, dms, fb.tsamp, kdm)
+    if max_delay >= fb.nsamp:
+        raise ValueError(f"the largest delay ({max_delay} samples) is not below the {fb.nsamp} samples of the file")
+    nout = fb.nsamp - max_delay if nout is None else int(nout)
+    bands = np.concatenate([band_edges(fb.nchans, nsub), np.array([[0, fb.nchans]], dtype=np.uint32)])
+    nbands = bands.shape[0]
+    band_freqs = np.array([fb.freqs[lo:hi].mean() for lo, hi in bands[:nsub]])
+    shape = _SeriesShape(nout, fb.tsamp)
+    # the raw band series of a DM and their normalised copy, half the budget: the
+    # rest is left to the gulp buffers and the dereddening workspace
+    per_dm = 2 * nbands * nout * 4
+    batch = max(1, int(budget_bytes // 2 // per_dm))
+
+    candidates = []
+    for b0 in range(0, len(dms), batch):
+        group = dms[b0:b0 + batch]
+        series, _ = band_series(fb, group, bands, deredden_params, nout, mask=mask, zero_dm=zero_dm, kdm=kdm,
+                                device=device, budget_bytes=budget_bytes)
+        todo, specs = [], []
+        for i, dm in enumerate(group):
+            for cl in by_dm[dm]:
+                try:
+                    period, bins, subints = candidate_fold_spec(shape, cl, range_confs)
+                    if bins < 2:
+                        raise ValueError("the device fold needs bins >= 2")
+                except Exception as err:
+                    log.error(err)
+                    log.error(traceback.format_exc())
+                    continue
+                todo.append((cl, dm))
+                specs += [(i * nbands + b, period, bins, subints) for b in range(nbands)]
+        folds = engine.fold_device(series.view(len(group) * nbands, nout), fb.tsamp, specs)
+        for k, (cl, dm) in enumerate(todo):
+            # a cluster's band folds have one shape: one download
+            arrs = torch.stack(folds[k * nbands:(k + 1) * nbands]).cpu().numpy()
+            candidates.append(Candidate(cl.centre.summary_dict(), fb.metadata(dm), cl.summary_dataframe(),
+                                        arrs[-1].copy(), subbands=arrs[:-1].copy(), band_freqs=band_freqs))
     candidates.sort(key=lambda c: c.params["snr"], reverse=True)
     log.info(f"Total candidates: {len(candidates)}")
     return candidates

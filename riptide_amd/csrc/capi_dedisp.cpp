@@ -5,6 +5,7 @@
 
 #include <mutex>
 #include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "capi_device.hpp"
@@ -53,6 +54,17 @@ void dedisp_check_shape(int dtype, size_t nsamp_blk, size_t nchans, size_t ndm, 
 void dedisp_check_flags(uint32_t flags)
 {
     if (flags & ~RT_DEDISP_ZERO_DM) throw std::invalid_argument("dedisperse: unknown flag bit");
+}
+
+// the band forms: every band a grid layer, every (DM, band) a row of out
+void dedisp_check_bands(size_t ndm, size_t nbands)
+{
+    if (!nbands) throw std::invalid_argument("dedisperse: nbands must be at least 1");
+    if (nbands > RT_DEDISP_MAX_BANDS)
+        throw std::invalid_argument("dedisperse: too many bands for one call (at most " +
+                                    std::to_string(RT_DEDISP_MAX_BANDS) + ")");
+    if (ndm * nbands > 0xFFFFFFFFull)   // ndm < 2^20, nbands < 2^16: no overflow here
+        throw std::invalid_argument("dedisperse: ndm * nbands rows overflow 32 bits");
 }
 
 // the statistics have no exactness limit on the channel count of 8-bit data
@@ -150,6 +162,76 @@ int rt_dedisperse_opt(const void* x, int dtype, size_t nsamp, size_t nchans, con
                              (uint32_t)max_delay, dz, nout, dw, flags, c.stream),
            "dedisperse");
         d2h(out, dz, ndm * nout * 4, c.stream);
+        sync(c.stream);
+        return RT_OK;
+    });
+}
+
+int rt_dedisperse_bands_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans,
+                               const int32_t* d_delays, const uint8_t* d_mask, size_t ndm, const uint32_t* d_bands,
+                               size_t nbands, int64_t max_delay, float* d_out, size_t out_stride, size_t out_offset,
+                               void* d_ws, size_t ws_bytes, void* stream, uint32_t flags)
+{
+    return guarded([&] {
+        dedisp_check_flags(flags);
+        dedisp_check_shape(dtype, nsamp_blk, nchans, ndm, max_delay);
+        dedisp_check_bands(ndm, nbands);
+        const size_t nout = nsamp_blk - (size_t)max_delay;
+        if (out_offset > out_stride || nout > out_stride - out_offset)
+            throw std::invalid_argument("dedisperse: out_stride is shorter than out_offset plus the block's outputs");
+        if (!d_block || !d_delays || !d_out || !d_ws) throw std::invalid_argument("dedisperse: null device pointer");
+        if (!d_bands) throw std::invalid_argument("dedisperse: d_bands is NULL");
+        if ((uintptr_t)d_ws % 16 || (uintptr_t)d_bands % 4 || (dtype == RT_DEDISP_F32 && (uintptr_t)d_block % 4))
+            throw std::invalid_argument("dedisperse: misaligned device pointer");
+        if (ws_bytes < dedisp_workspace_bytes(dtype, nsamp_blk, nchans, flags))
+            throw std::invalid_argument("workspace too small");
+        ck(launch_dedisperse(d_block, dtype, (uint32_t)nsamp_blk, (uint32_t)nchans, d_delays, d_mask, (uint32_t)ndm,
+                             (uint32_t)max_delay, d_out + out_offset, out_stride, d_ws, flags, (hipStream_t)stream,
+                             d_bands, (uint32_t)nbands),
+           "dedisperse");
+        return RT_OK;
+    });
+}
+
+int rt_dedisperse_bands(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
+                        const uint8_t* mask, size_t ndm, const uint32_t* bands, size_t nbands, int64_t max_delay,
+                        float* out, uint32_t flags)
+{
+    return guarded([&] {
+        dedisp_check_flags(flags);
+        dedisp_check_shape(dtype, nsamp, nchans, ndm, max_delay);
+        dedisp_check_bands(ndm, nbands);
+        if (!x || !delays || !out || !bands) throw std::invalid_argument("dedisperse: null buffer");
+        for (size_t b = 0; b < nbands; ++b)
+            if (bands[2 * b] > bands[2 * b + 1] || bands[2 * b + 1] > nchans)
+                throw std::invalid_argument("dedisperse: band " + std::to_string(b) + " [" +
+                                            std::to_string(bands[2 * b]) + ", " + std::to_string(bands[2 * b + 1]) +
+                                            ") is not a channel range lo <= hi <= " + std::to_string(nchans));
+        std::vector<int32_t> del(ndm * nchans);
+        for (size_t i = 0; i < del.size(); ++i) {
+            if (delays[i] < 0 || delays[i] > max_delay)
+                throw std::invalid_argument("dedisperse: a delay is outside [0, max_delay]");
+            del[i] = (int32_t)delays[i];
+        }
+        const size_t nout = nsamp - (size_t)max_delay;
+        const size_t in_bytes = nsamp * row_bytes_of(dtype, nchans);
+        const size_t ws_bytes = (size_t)dedisp_workspace_bytes(dtype, nsamp, nchans, flags);
+        std::lock_guard<std::mutex> lk(g_mu);
+        Context& c = context();
+        void* dx = c.buf[0].get(in_bytes);
+        float* dz = dev<float>(c, 1, ndm * nbands * nout);
+        void* dw = c.buf[2].get(ws_bytes);
+        int32_t* dd = dev<int32_t>(c, 3, del.size());
+        uint8_t* dm = mask ? dev<uint8_t>(c, 4, nchans) : nullptr;
+        uint32_t* db = dev<uint32_t>(c, 5, 2 * nbands);
+        h2d(dx, x, in_bytes, c.stream);
+        h2d(dd, del.data(), del.size() * 4, c.stream);
+        if (mask) h2d(dm, mask, nchans, c.stream);
+        h2d(db, bands, 2 * nbands * 4, c.stream);
+        ck(launch_dedisperse(dx, dtype, (uint32_t)nsamp, (uint32_t)nchans, dd, dm, (uint32_t)ndm,
+                             (uint32_t)max_delay, dz, nout, dw, flags, c.stream, db, (uint32_t)nbands),
+           "dedisperse");
+        d2h(out, dz, ndm * nbands * nout * 4, c.stream);
         sync(c.stream);
         return RT_OK;
     });

@@ -17,18 +17,31 @@ using namespace rt;
 
 namespace {
 
+// A band table of the band forms (rt_dedisperse_bands_host): row (d, b) of out
+// sums the channels [lo_b, hi_b) alone.  No table (bands == nullptr, the plain
+// forms) is the one band [0, nchans).
+struct Bands {
+    const uint32_t* bands = nullptr;
+    size_t nbands = 1;
+    size_t lo(size_t b, size_t) const { return bands ? bands[2 * b] : 0; }
+    size_t hi(size_t b, size_t nchans) const { return bands ? bands[2 * b + 1] : nchans; }
+};
+
 template <class T, class Acc>
 void dedisperse_rows(const T* x, size_t nchans, const int64_t* delays, const uint8_t* mask, size_t ndm, size_t nout,
-                     float* out)
+                     float* out, const Bands& bt)
 {
     for (size_t d = 0; d < ndm; ++d) {
         const int64_t* del = delays + d * nchans;
-        float* o = out + d * nout;
-        for (size_t t = 0; t < nout; ++t) {
-            Acc acc = 0;
-            for (size_t c = 0; c < nchans; ++c)
-                if (!mask || !mask[c]) acc += (Acc)x[(t + (size_t)del[c]) * nchans + c];
-            o[t] = (float)acc;
+        for (size_t b = 0; b < bt.nbands; ++b) {
+            float* o = out + (d * bt.nbands + b) * nout;
+            const size_t lo = bt.lo(b, nchans), hi = bt.hi(b, nchans);
+            for (size_t t = 0; t < nout; ++t) {
+                Acc acc = 0;
+                for (size_t c = lo; c < hi; ++c)
+                    if (!mask || !mask[c]) acc += (Acc)x[(t + (size_t)del[c]) * nchans + c];
+                o[t] = (float)acc;
+            }
         }
     }
 }
@@ -49,24 +62,28 @@ void zero_dm_mean(const T* x, size_t nsamp, size_t nchans, const uint8_t* mask, 
     }
 }
 
+// m is the mean over the unmasked channels of the whole file, whatever the band
 template <class T>
 void dedisperse_rows_zero_dm(const T* x, size_t nsamp, size_t nchans, const int64_t* delays, const uint8_t* mask,
-                             size_t ndm, size_t nout, float* out)
+                             size_t ndm, size_t nout, float* out, const Bands& bt)
 {
     std::vector<float> m(nsamp);
     zero_dm_mean<T, typename std::conditional<std::is_integral<T>::value, int64_t, double>::type>(x, nsamp, nchans,
                                                                                                   mask, m.data());
     for (size_t d = 0; d < ndm; ++d) {
         const int64_t* del = delays + d * nchans;
-        float* o = out + d * nout;
-        for (size_t t = 0; t < nout; ++t) {
-            float acc = 0.0f;
-            for (size_t c = 0; c < nchans; ++c) {
-                if (mask && mask[c]) continue;
-                const size_t tt = t + (size_t)del[c];
-                acc += (float)x[tt * nchans + c] - m[tt];
+        for (size_t b = 0; b < bt.nbands; ++b) {
+            float* o = out + (d * bt.nbands + b) * nout;
+            const size_t lo = bt.lo(b, nchans), hi = bt.hi(b, nchans);
+            for (size_t t = 0; t < nout; ++t) {
+                float acc = 0.0f;
+                for (size_t c = lo; c < hi; ++c) {
+                    if (mask && mask[c]) continue;
+                    const size_t tt = t + (size_t)del[c];
+                    acc += (float)x[tt * nchans + c] - m[tt];
+                }
+                o[t] = acc;
             }
-            o[t] = acc;
         }
     }
 }
@@ -136,6 +153,63 @@ void check_dtype(int dtype, size_t nchans)
     if (packed_bits(dtype)) packed_row_bytes(packed_bits(dtype), nchans);
 }
 
+// The specification of the plain and the band forms: the checks every form
+// shares, then the sums by sample type.  Throws for what they refuse.
+void dedisperse_host(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
+                     const uint8_t* mask, size_t ndm, int64_t max_delay, size_t nout, float* out, uint32_t flags,
+                     const Bands& bt)
+{
+    if (flags & ~RT_DEDISP_ZERO_DM) throw std::invalid_argument("dedisperse: unknown flag bit");
+    if (!nchans || !ndm) throw std::invalid_argument("dedisperse: nchans and ndm must be at least 1");
+    if (!known_dtype(dtype)) throw std::invalid_argument("dedisperse: unknown sample type code");
+    const int nbits = packed_bits(dtype);
+    if (nbits) packed_row_bytes(nbits, nchans);
+    if (max_delay < 0 || max_delay >= 2147483648ll)
+        throw std::invalid_argument("dedisperse: max_delay is outside [0, 2^31)");
+    if (nout > nsamp || (uint64_t)max_delay > nsamp - nout)
+        throw std::invalid_argument("dedisperse: nout + max_delay exceeds the " + std::to_string(nsamp) +
+                                    " samples of the input");
+    if (integer_sum(dtype) && nchans > RT_DEDISP_MAX_CHANS_8BIT)
+        throw std::invalid_argument("dedisperse: too many channels for an exact 8-bit sum");
+    for (size_t i = 0; i < ndm * nchans; ++i)
+        if (delays[i] < 0 || delays[i] > max_delay)
+            throw std::invalid_argument("dedisperse: a delay is outside [0, max_delay]");
+    if (!nout || !bt.nbands) return;
+    if (nbits) {
+        // the values of the packed block, then the same sums: 1/2/4 bit as
+        // 8-bit data, 16 bit converted exactly and added in float32
+        if (nbits == 16) {
+            const std::vector<uint16_t> v = unpack_block<uint16_t>(x, nbits, nsamp, nchans);
+            if (flags & RT_DEDISP_ZERO_DM)
+                dedisperse_rows_zero_dm(v.data(), nsamp, nchans, delays, mask, ndm, nout, out, bt);
+            else
+                dedisperse_rows<uint16_t, float>(v.data(), nchans, delays, mask, ndm, nout, out, bt);
+        } else {
+            const std::vector<uint8_t> v = unpack_block<uint8_t>(x, nbits, nsamp, nchans);
+            if (flags & RT_DEDISP_ZERO_DM)
+                dedisperse_rows_zero_dm(v.data(), nsamp, nchans, delays, mask, ndm, nout, out, bt);
+            else
+                dedisperse_rows<uint8_t, int32_t>(v.data(), nchans, delays, mask, ndm, nout, out, bt);
+        }
+        return;
+    }
+    if (flags & RT_DEDISP_ZERO_DM) {
+        if (dtype == RT_DEDISP_U8)
+            dedisperse_rows_zero_dm((const uint8_t*)x, nsamp, nchans, delays, mask, ndm, nout, out, bt);
+        else if (dtype == RT_DEDISP_I8)
+            dedisperse_rows_zero_dm((const int8_t*)x, nsamp, nchans, delays, mask, ndm, nout, out, bt);
+        else
+            dedisperse_rows_zero_dm((const float*)x, nsamp, nchans, delays, mask, ndm, nout, out, bt);
+        return;
+    }
+    if (dtype == RT_DEDISP_U8)
+        dedisperse_rows<uint8_t, int32_t>((const uint8_t*)x, nchans, delays, mask, ndm, nout, out, bt);
+    else if (dtype == RT_DEDISP_I8)
+        dedisperse_rows<int8_t, int32_t>((const int8_t*)x, nchans, delays, mask, ndm, nout, out, bt);
+    else
+        dedisperse_rows<float, float>((const float*)x, nchans, delays, mask, ndm, nout, out, bt);
+}
+
 }  // namespace
 
 extern "C" {
@@ -202,55 +276,24 @@ int rt_dedisperse_host_opt(const void* x, int dtype, size_t nsamp, size_t nchans
                            uint32_t flags)
 {
     return guarded([&] {
-        if (flags & ~RT_DEDISP_ZERO_DM) throw std::invalid_argument("dedisperse: unknown flag bit");
+        dedisperse_host(x, dtype, nsamp, nchans, delays, mask, ndm, max_delay, nout, out, flags, Bands{});
+        return RT_OK;
+    });
+}
+
+int rt_dedisperse_bands_host(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
+                             const uint8_t* mask, size_t ndm, const uint32_t* bands, size_t nbands,
+                             int64_t max_delay, size_t nout, float* out, uint32_t flags)
+{
+    return guarded([&] {
         if (!nchans || !ndm) throw std::invalid_argument("dedisperse: nchans and ndm must be at least 1");
-        if (!known_dtype(dtype)) throw std::invalid_argument("dedisperse: unknown sample type code");
-        const int nbits = packed_bits(dtype);
-        if (nbits) packed_row_bytes(nbits, nchans);
-        if (max_delay < 0 || max_delay >= 2147483648ll)
-            throw std::invalid_argument("dedisperse: max_delay is outside [0, 2^31)");
-        if (nout > nsamp || (uint64_t)max_delay > nsamp - nout)
-            throw std::invalid_argument("dedisperse: nout + max_delay exceeds the " + std::to_string(nsamp) +
-                                        " samples of the input");
-        if (integer_sum(dtype) && nchans > RT_DEDISP_MAX_CHANS_8BIT)
-            throw std::invalid_argument("dedisperse: too many channels for an exact 8-bit sum");
-        for (size_t i = 0; i < ndm * nchans; ++i)
-            if (delays[i] < 0 || delays[i] > max_delay)
-                throw std::invalid_argument("dedisperse: a delay is outside [0, max_delay]");
-        if (!nout) return RT_OK;
-        if (nbits) {
-            // the values of the packed block, then the same sums: 1/2/4 bit as
-            // 8-bit data, 16 bit converted exactly and added in float32
-            if (nbits == 16) {
-                const std::vector<uint16_t> v = unpack_block<uint16_t>(x, nbits, nsamp, nchans);
-                if (flags & RT_DEDISP_ZERO_DM)
-                    dedisperse_rows_zero_dm(v.data(), nsamp, nchans, delays, mask, ndm, nout, out);
-                else
-                    dedisperse_rows<uint16_t, float>(v.data(), nchans, delays, mask, ndm, nout, out);
-            } else {
-                const std::vector<uint8_t> v = unpack_block<uint8_t>(x, nbits, nsamp, nchans);
-                if (flags & RT_DEDISP_ZERO_DM)
-                    dedisperse_rows_zero_dm(v.data(), nsamp, nchans, delays, mask, ndm, nout, out);
-                else
-                    dedisperse_rows<uint8_t, int32_t>(v.data(), nchans, delays, mask, ndm, nout, out);
-            }
-            return RT_OK;
-        }
-        if (flags & RT_DEDISP_ZERO_DM) {
-            if (dtype == RT_DEDISP_U8)
-                dedisperse_rows_zero_dm((const uint8_t*)x, nsamp, nchans, delays, mask, ndm, nout, out);
-            else if (dtype == RT_DEDISP_I8)
-                dedisperse_rows_zero_dm((const int8_t*)x, nsamp, nchans, delays, mask, ndm, nout, out);
-            else
-                dedisperse_rows_zero_dm((const float*)x, nsamp, nchans, delays, mask, ndm, nout, out);
-            return RT_OK;
-        }
-        if (dtype == RT_DEDISP_U8)
-            dedisperse_rows<uint8_t, int32_t>((const uint8_t*)x, nchans, delays, mask, ndm, nout, out);
-        else if (dtype == RT_DEDISP_I8)
-            dedisperse_rows<int8_t, int32_t>((const int8_t*)x, nchans, delays, mask, ndm, nout, out);
-        else
-            dedisperse_rows<float, float>((const float*)x, nchans, delays, mask, ndm, nout, out);
+        if (nbands && !bands) throw std::invalid_argument("dedisperse: bands is NULL");
+        for (size_t b = 0; b < nbands; ++b)
+            if (bands[2 * b] > bands[2 * b + 1] || bands[2 * b + 1] > nchans)
+                throw std::invalid_argument("dedisperse: band " + std::to_string(b) + " [" +
+                                            std::to_string(bands[2 * b]) + ", " + std::to_string(bands[2 * b + 1]) +
+                                            ") is not a channel range lo <= hi <= " + std::to_string(nchans));
+        dedisperse_host(x, dtype, nsamp, nchans, delays, mask, ndm, max_delay, nout, out, flags, Bands{bands, nbands});
         return RT_OK;
     });
 }

@@ -19,6 +19,10 @@
 //                             tile's DMs read is staged in LDS with aligned
 //                             dword loads, then every wave adds its four DMs
 //                             (one DM at a time, its delay wave-uniform)
+//   dedisp_sum_kernel<T, DdBandTable>  the same tile over the channels [lo, hi)
+//                             of one band of a table, a grid layer per band:
+//                             out[d, b, t], every band of a batch of DMs from
+//                             one pass over the transposed block
 //   dedisp_rowmean_kernel     zero-DM filter (RT_DEDISP_ZERO_DM): m[t], the mean
 //                             of time sample t over the unmasked channels, one
 //                             wave per sample
@@ -342,15 +346,40 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_chanstats_fold_kernel(
     acc[i] = a;
 }
 
+// Which channels a workgroup of dedisp_sum_kernel sums, its last argument.
+// DdAllChans (empty: the plain call) is every channel, grid (time tiles, DM
+// tiles), out[d * out_stride + t].  DdBandTable (rt_dedisperse_bands_device)
+// is the channels [lo, hi) of band blockIdx.z of uint32 bands[nbands][2], a
+// grid layer per band, out[(d * nbands + b) * out_stride + t]; the edges are
+// clamped as they are read, hi to nchans and lo to hi, so a band of any two
+// numbers reads rows of the workspace only.  An empty band, or one whose
+// channels are all masked, stores zeros.
+struct DdAllChans {};
+struct DdBandTable {
+    const uint32_t* bands;
+    uint32_t nbands;
+};
+
 // T = uint8_t (signed samples biased by 128: bias = 128) or float.  pitch is
 // in elements.  Lane l of a wave owns the outputs t0 + 4 l + j (8-bit) or
-// t0 + l + 64 j (float), j = 0..3, of each of the wave's four DMs.
-template <class T>
+// t0 + l + 64 j (float), j = 0..3, of each of the wave's four DMs.  nsum,
+// which the 8-bit bias correction multiplies, counts the channels summed by
+// this workgroup: those of its band, not of the file.
+template <class T, class Sel = DdAllChans>
 __global__ __launch_bounds__(kDdThreads) void dedisp_sum_kernel(
     const T* __restrict__ ws, uint64_t pitch, uint32_t nchans, const int32_t* __restrict__ delays,
     const uint8_t* __restrict__ mask, uint32_t ndm, uint32_t max_delay, uint32_t nout, float* __restrict__ out,
-    uint64_t out_stride, int32_t bias)
+    uint64_t out_stride, int32_t bias, Sel sel)
 {
+    uint32_t c_lo = 0, c_hi = nchans;
+    uint64_t row_stride = out_stride;
+    if constexpr (std::is_same<Sel, DdBandTable>::value) {
+        const uint32_t b = blockIdx.z;
+        c_hi = min(sel.bands[2 * b + 1], nchans);
+        c_lo = min(sel.bands[2 * b], c_hi);
+        out += (uint64_t)b * out_stride;
+        row_stride = (uint64_t)sel.nbands * out_stride;
+    }
     constexpr bool kBytes = sizeof(T) == 1;
     constexpr uint32_t kE = 4 / sizeof(T);   // elements per dword
     constexpr uint32_t kSpan = DdSpan<T>::dwords;
@@ -370,20 +399,20 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_sum_kernel(
         for (uint32_t j = 0; j < 4; ++j) acc[r][j] = 0;
     int32_t nsum = 0;
 
-    for (uint32_t c0 = 0; c0 < nchans; c0 += kDdChans) {
+    for (uint32_t c0 = c_lo; c0 < c_hi; c0 += kDdChans) {
         __syncthreads();   // the previous step's spans and delays are consumed
         {
             // the tile's delays: rows past ndm repeat the last DM (never stored)
             const uint32_t dd = tid >> 4, cc = tid & 15;
             const uint32_t d = min(d0 + dd, ndm - 1), c = c0 + cc;
             int32_t v = 0;
-            if (c < nchans) v = min(max(delays[(uint64_t)d * nchans + c], 0), (int32_t)max_delay);
+            if (c < c_hi) v = min(max(delays[(uint64_t)d * nchans + c], 0), (int32_t)max_delay);
             sdel[dd][cc] = v;
         }
         __syncthreads();
         for (uint32_t cc = wave; cc < kDdChans; cc += kDdWaves) {
             const uint32_t c = c0 + cc;
-            if (c >= nchans || (mask && mask[c])) {
+            if (c >= c_hi || (mask && mask[c])) {
                 if (lane == 0) sbase[cc] = kDdSkip;
                 continue;
             }
@@ -463,7 +492,7 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_sum_kernel(
     for (uint32_t r = 0; r < kDdPerWave; ++r) {
         const uint32_t d = d0 + wave * kDdPerWave + r;
         if (d >= ndm) continue;
-        float* o = out + (uint64_t)d * out_stride;
+        float* o = out + (uint64_t)d * row_stride;
 #pragma unroll
         for (uint32_t j = 0; j < 4; ++j) {
             const uint32_t t = t0 + (kBytes ? lane * 4 + j : lane + 64 * j);
@@ -471,6 +500,23 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_sum_kernel(
             if constexpr (kBytes) o[t] = (float)(acc[r][j] - bias * nsum);
             else o[t] = acc[r][j];
         }
+    }
+}
+
+// the sum over the transposed rows: the plain instantiation, or with a band
+// table the band one on a grid with a z layer per band
+template <class T>
+void launch_sum(dim3 grid, hipStream_t s, const T* ws, uint64_t pitch, uint32_t nchans, const int32_t* delays,
+                const uint8_t* mask, uint32_t ndm, uint32_t max_delay, uint32_t nout, float* out, uint64_t out_stride,
+                int32_t bias, const uint32_t* bands, uint32_t nbands)
+{
+    if (bands) {
+        grid.z = nbands;
+        hipLaunchKernelGGL((dedisp_sum_kernel<T, DdBandTable>), grid, dim3(kDdThreads), 0, s, ws, pitch, nchans, delays,
+                           mask, ndm, max_delay, nout, out, out_stride, bias, DdBandTable{bands, nbands});
+    } else {
+        hipLaunchKernelGGL((dedisp_sum_kernel<T, DdAllChans>), grid, dim3(kDdThreads), 0, s, ws, pitch, nchans, delays,
+                           mask, ndm, max_delay, nout, out, out_stride, bias, DdAllChans{});
     }
 }
 
@@ -555,7 +601,8 @@ hipError_t launch_channel_stats(const void* block, int dtype, uint32_t nsamp_blk
 
 hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
                              const int32_t* d_delays, const uint8_t* d_mask, uint32_t ndm, uint32_t max_delay,
-                             float* out, uint64_t out_stride, void* ws, uint32_t flags, hipStream_t s)
+                             float* out, uint64_t out_stride, void* ws, uint32_t flags, hipStream_t s,
+                             const uint32_t* d_bands, uint32_t nbands)
 {
     const uint32_t nout = nsamp_blk - max_delay;
     const int nbits = dedisp_packed_bits(dtype);
@@ -583,16 +630,16 @@ hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, u
         else
             hipLaunchKernelGGL(dedisp_transpose_zdm_kernel<float>, grid, dim3(kDdThreads), 0, s,
                                (const float*)block, nsamp_blk, nchans, (const float*)m, (float*)ws, pitch);
-        hipLaunchKernelGGL(dedisp_sum_kernel<float>, sum_grid, dim3(kDdThreads), 0, s, (const float*)ws, pitch,
-                           nchans, d_delays, d_mask, ndm, max_delay, nout, out, out_stride, 0);
+        launch_sum(sum_grid, s, (const float*)ws, pitch, nchans, d_delays, d_mask, ndm, max_delay, nout, out, out_stride,
+                   0, d_bands, nbands);
     } else if (nbits == 16) {
         // exact float32 rows, then the float sum
         const uint64_t pitch = pitch_bytes / 4;
         const dim3 grid((uint32_t)((pitch + 63) / 64), (nchans + 63) / 64);
         hipLaunchKernelGGL((dedisp_transpose_zdm_kernel<DdBits<16>, false>), grid, dim3(kDdThreads), 0, s,
                            (const DdBits<16>*)block, nsamp_blk, nchans, (const float*)nullptr, (float*)ws, pitch);
-        hipLaunchKernelGGL(dedisp_sum_kernel<float>, sum_grid, dim3(kDdThreads), 0, s, (const float*)ws, pitch,
-                           nchans, d_delays, d_mask, ndm, max_delay, nout, out, out_stride, 0);
+        launch_sum(sum_grid, s, (const float*)ws, pitch, nchans, d_delays, d_mask, ndm, max_delay, nout, out, out_stride,
+                   0, d_bands, nbands);
     } else if (nbits) {
         // the 8-bit rows of the values, then the 8-bit sum with no bias
         const uint32_t row_bytes = (uint32_t)((uint64_t)nchans * nbits / 8);
@@ -605,22 +652,21 @@ hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, u
                                    (const uint8_t*)block, nsamp_blk, nchans, row_bytes, (uint8_t*)ws, pitch_bytes,
                                    dwords);
         });
-        hipLaunchKernelGGL(dedisp_sum_kernel<uint8_t>, sum_grid, dim3(kDdThreads), 0, s, (const uint8_t*)ws,
-                           pitch_bytes, nchans, d_delays, d_mask, ndm, max_delay, nout, out, out_stride, 0);
+        launch_sum(sum_grid, s, (const uint8_t*)ws, pitch_bytes, nchans, d_delays, d_mask, ndm, max_delay, nout, out,
+                   out_stride, 0, d_bands, nbands);
     } else if (dtype == 2) {
         const uint64_t pitch = pitch_bytes / 4;
         const dim3 grid((uint32_t)((pitch + 63) / 64), (nchans + 63) / 64);
         hipLaunchKernelGGL(dedisp_transpose32_kernel, grid, dim3(kDdThreads), 0, s, (const float*)block, nsamp_blk,
                            nchans, (float*)ws, pitch);
-        hipLaunchKernelGGL(dedisp_sum_kernel<float>, sum_grid, dim3(kDdThreads), 0, s, (const float*)ws, pitch,
-                           nchans, d_delays, d_mask, ndm, max_delay, nout, out, out_stride, 0);
+        launch_sum(sum_grid, s, (const float*)ws, pitch, nchans, d_delays, d_mask, ndm, max_delay, nout, out, out_stride,
+                   0, d_bands, nbands);
     } else {
         const dim3 grid((uint32_t)((pitch_bytes + 255) / 256), (nchans + 63) / 64);
         hipLaunchKernelGGL(dedisp_transpose8_kernel, grid, dim3(kDdThreads), 0, s, (const uint8_t*)block, nsamp_blk,
                            nchans, (uint8_t*)ws, pitch_bytes, dtype == 1 ? 0x80u : 0u);
-        hipLaunchKernelGGL(dedisp_sum_kernel<uint8_t>, sum_grid, dim3(kDdThreads), 0, s, (const uint8_t*)ws,
-                           pitch_bytes, nchans, d_delays, d_mask, ndm, max_delay, nout, out, out_stride,
-                           dtype == 1 ? 128 : 0);
+        launch_sum(sum_grid, s, (const uint8_t*)ws, pitch_bytes, nchans, d_delays, d_mask, ndm, max_delay, nout, out,
+                   out_stride, dtype == 1 ? 128 : 0, d_bands, nbands);
     }
     return hipGetLastError();
 }

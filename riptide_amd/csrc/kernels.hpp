@@ -99,9 +99,14 @@ constexpr uint32_t kDdZeroDm = 1u;   // RT_DEDISP_ZERO_DM
 // bytes of ws for these flags: the rows, with kDdZeroDm float rows plus one
 // more pitch for m [nsamp_blk]
 uint64_t dedisp_workspace_bytes(int dtype, uint64_t nsamp_blk, uint64_t nchans, uint32_t flags);
+// d_bands: nullptr, or uint32 [nbands][2] channel ranges [lo, hi) in device
+// memory (clamped to nchans as they are read): out[(d * nbands + b) *
+// out_stride + t] is then the sum over band b alone; nbands <= 65535
+// (RT_DEDISP_MAX_BANDS), a grid layer per band.
 hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
                              const int32_t* d_delays, const uint8_t* d_mask, uint32_t ndm, uint32_t max_delay,
-                             float* out, uint64_t out_stride, void* ws, uint32_t flags, hipStream_t s);
+                             float* out, uint64_t out_stride, void* ws, uint32_t flags, hipStream_t s,
+                             const uint32_t* d_bands = nullptr, uint32_t nbands = 0);
 // m[t] = (float32)(sum over unmasked c of block[t, c] / their number), t < nsamp_blk
 hipError_t launch_zero_dm_mean(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
                                const uint8_t* d_mask, float* m, hipStream_t s);

@@ -168,6 +168,70 @@ def dedisperse(data, freqs, tsamp, dms, mask=None, kdm=KDM, zero_dm=False, nbits
     return out
 
 
+def band_edges(nchans, nsub):
+    """uint32 [nsub, 2]: the channel ranges [lo, hi) of nsub contiguous
+    sub-bands of nchans channels, lo_s = s * nchans // nsub and hi_s =
+    (s + 1) * nchans // nsub (no band empty, widths differing by at most one
+    channel).  ValueError unless 1 <= nsub <= nchans."""
+    nchans, nsub = int(nchans), int(nsub)
+    if not 1 <= nsub <= nchans:
+        raise ValueError(f"nsub must be in [1, {nchans}], the number of channels")
+    edges = np.arange(nsub + 1, dtype=np.int64) * nchans // nsub
+    return np.stack([edges[:-1], edges[1:]], axis=1).astype(np.uint32)
+
+
+def _checked_bands(bands, nchans):
+    from .engine import checked_bands
+    return checked_bands(bands, nchans)
+
+
+def dedisperse_bands_host(data, delays, max_delay, bands, mask=None, nout=None, zero_dm=False, nbits=None):
+    """The specification of the band sums on the host (rt_dedisperse_bands_host,
+    no device): float32 [ndm, nbands, nout],
+
+      out[d, b, t] = sum over unmasked c in [lo_b, hi_b) of x[t + delay[d, c], c]
+
+    for bands uint32 [nbands, 2] of channel ranges [lo, hi), which may overlap,
+    be empty or cover the whole file.  Everything else as dedisperse_host; with
+    zero_dm the mean is over the unmasked channels of the whole file."""
+    data, code, nsamp, nchans = _host_block(data, nbits)
+    delays = np.ascontiguousarray(delays, dtype=np.int64)
+    if delays.ndim != 2 or delays.shape[1] != nchans:
+        raise ValueError("delays must be [ndm, nchans]")
+    mask = _checked_mask(mask, nchans)
+    bands = np.ascontiguousarray(bands, dtype=np.uint32)
+    if bands.ndim != 2 or bands.shape[1] != 2:
+        raise ValueError("bands must be [nbands, 2]")
+    nout = nsamp - int(max_delay) if nout is None else int(nout)
+    if nout < 0:
+        raise ValueError(f"max_delay {max_delay} exceeds the {nsamp} samples of the input")
+    out = np.zeros((delays.shape[0], bands.shape[0], nout), dtype=np.float32)
+    _check(_L.rt_dedisperse_bands_host(_lib.ptr(data), code, nsamp, nchans, _lib.ptr(delays),
+                                       None if mask is None else _lib.ptr(mask), delays.shape[0], _lib.ptr(bands),
+                                       bands.shape[0], int(max_delay), nout, _lib.ptr(out), _flags(zero_dm)))
+    return out
+
+
+def dedisperse_bands(data, freqs, tsamp, dms, bands, mask=None, kdm=KDM, zero_dm=False, nbits=None):
+    """dedisperse() for every band of a table on the GPU: float32
+    [ndm, nbands, nsamp - max_delay] (rt_dedisperse_bands: upload, kernels,
+    download).  The delays are against the highest frequency of all of
+    `freqs`, whatever the bands."""
+    data, code, nsamp, nchans = _host_block(data, nbits)
+    delays, max_delay = dispersion_delays(freqs, dms, tsamp, kdm)
+    if delays.shape[1] != nchans:
+        raise ValueError("freqs must have one entry per channel of data")
+    mask = _checked_mask(mask, nchans)
+    bands = _checked_bands(bands, nchans)
+    if max_delay >= nsamp:
+        raise ValueError(f"the largest delay ({max_delay} samples) is not below the {nsamp} samples of the data")
+    out = np.empty((delays.shape[0], bands.shape[0], nsamp - max_delay), dtype=np.float32)
+    _check(_L.rt_dedisperse_bands(_lib.ptr(data), code, nsamp, nchans, _lib.ptr(delays),
+                                  None if mask is None else _lib.ptr(mask), delays.shape[0], _lib.ptr(bands),
+                                  bands.shape[0], max_delay, _lib.ptr(out), _flags(zero_dm)))
+    return out
+
+
 def _gulp_layout(fb):
     """(elements of a row of fb.data, their numpy dtype): the raw bytes of a
     PackedFilterbank, the samples of a Filterbank."""
@@ -229,7 +293,7 @@ def stream_gulps(fb, dev, gulp, nrows, overlap, process):
 
 
 def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, nout=None,
-                          budget_bytes=DEFAULT_BUDGET_BYTES, zero_dm=False):
+                          budget_bytes=DEFAULT_BUDGET_BYTES, zero_dm=False, bands=None):
     """Dedisperse a reading.Filterbank (or PackedFilterbank: the rows are
     uploaded packed) at the trial DMs into one device tensor
     float32 [ndm, nout], nout = nsamp - max_delay (or a smaller `nout`: the
@@ -245,6 +309,11 @@ def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, n
     zero_dm: the zero-DM filter in front of the sum (module docstring).  The
     mean of a time sample needs that sample's row alone, so the result still
     does not depend on gulp; the workspace of a gulp is the larger float32 one.
+
+    bands (uint32 [nbands, 2] of channel ranges [lo, hi): band_edges): the
+    result is float32 [ndm, nbands, nout] instead, every band's sum of every DM
+    from the same single pass over the file (engine.dedisperse_bands_device),
+    and the output counted against the budget is ndm * nbands * nout * 4 bytes.
 
     ValueError -- nothing is launched -- when max_delay >= nsamp, for 8-bit
     data of more than 65793 channels, and when the output (ndm * nout * 4
@@ -281,19 +350,64 @@ def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, n
     need_in = nout + max_delay          # input rows the outputs read
     gulp = min(gulp, need_in)
     ws_bytes = engine.dedisperse_workspace_bytes(dtype.name, gulp, nchans, zero_dm, nbits=nbits)
-    total = ndm * nout * 4 + 2 * gulp * row_bytes + ws_bytes
+    if bands is not None:
+        bands = _checked_bands(bands, nchans)
+    out_bytes = ndm * (1 if bands is None else bands.shape[0]) * nout * 4
+    total = out_bytes + 2 * gulp * row_bytes + ws_bytes
     if total > int(budget_bytes):
-        raise ValueError(f"dedispersing {ndm} DMs needs {total} bytes of device memory ({ndm * nout * 4} of output "
+        raise ValueError(f"dedispersing {ndm} DMs needs {total} bytes of device memory ({out_bytes} of output "
                          f"plus the gulp buffers), over the budget of {int(budget_bytes)}: pass fewer DMs per call")
     with torch.cuda.device(dev):
-        out = torch.empty((ndm, nout), dtype=torch.float32, device=dev)
         d_delays = torch.from_numpy(delays.astype(np.int32)).to(dev)
         d_mask = None if mask is None else torch.from_numpy(mask).to(dev)
         workspace = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        if bands is None:
+            out = torch.empty((ndm, nout), dtype=torch.float32, device=dev)
 
-        def process(block, start):
-            engine.dedisperse_device(block, d_delays, max_delay, mask=d_mask, out=out, out_offset=start,
-                                     workspace=workspace, zero_dm=zero_dm, nbits=nbits)
+            def process(block, start):
+                engine.dedisperse_device(block, d_delays, max_delay, mask=d_mask, out=out, out_offset=start,
+                                         workspace=workspace, zero_dm=zero_dm, nbits=nbits)
+        else:
+            out = torch.empty((ndm, bands.shape[0], nout), dtype=torch.float32, device=dev)
+            d_bands = torch.from_numpy(bands.view(np.int32)).to(dev)
+
+            def process(block, start):
+                engine.dedisperse_bands_device(block, d_delays, max_delay, d_bands, mask=d_mask, out=out,
+                                               out_offset=start, workspace=workspace, zero_dm=zero_dm, nbits=nbits)
 
         stream_gulps(fb, dev, gulp, need_in, max_delay, process)
     return out
+
+
+def band_series(fb, dms, bands, deredden_params, nout, mask=None, zero_dm=False, kdm=KDM, device=None,
+                budget_bytes=DEFAULT_BUDGET_BYTES):
+    """The series a candidate's frequency-phase diagnostic is folded from:
+    (device tensor float32 [ndm, nbands, nout], bool [nbands]).  The file is
+    dedispersed into every band at every DM by one pass
+    (dedisperse_filterbank(..., bands=bands, nout=nout)), then every row is
+    dereddened (deredden_params: rmed_width in seconds, rmed_minpts) and
+    normalised by one batched engine.deredden_normalise call, as the search
+    does with a DM trial.  The second result marks the bands with no unmasked
+    channel: their rows are left zero and are not normalised (the variance of
+    a constant row is zero)."""
+    import torch
+    from . import engine
+    bands = _checked_bands(bands, fb.nchans)
+    mask = _checked_mask(mask, fb.nchans)
+    live = np.ones(fb.nchans, dtype=bool) if mask is None else mask == 0
+    empty = np.array([not live[lo:hi].any() for lo, hi in bands], dtype=bool)
+    raw = dedisperse_filterbank(fb, dms, mask=mask, device=device, kdm=kdm, nout=nout, budget_bytes=budget_bytes,
+                                zero_dm=zero_dm, bands=bands)
+    ndm, nbands, nout = raw.shape
+    width = int(round(deredden_params["rmed_width"] / fb.tsamp))
+    minpts = int(deredden_params["rmed_minpts"])
+    rows = raw.view(ndm * nbands, nout)
+    with torch.cuda.device(raw.device):
+        if not empty.any():
+            return engine.deredden_normalise(rows, width, minpts).view(ndm, nbands, nout), empty
+        out = torch.zeros_like(rows)
+        if not empty.all():
+            keep = np.flatnonzero(np.tile(~empty, ndm))
+            idx = torch.from_numpy(keep).to(raw.device)
+            out[idx] = engine.deredden_normalise(rows[idx], width, minpts)
+    return out.view(ndm, nbands, nout), empty

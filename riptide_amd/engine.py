@@ -312,6 +312,17 @@ def _dedisp_name(dtype, nbits):
 DEDISP_ZERO_DM = 1    # RT_DEDISP_ZERO_DM
 
 
+def checked_bands(bands, nchans):
+    """bands as a contiguous uint32 [nbands, 2] array of channel ranges
+    [lo, hi) with lo <= hi <= nchans; ValueError otherwise."""
+    b = np.asarray(bands)
+    if b.ndim != 2 or b.shape[1] != 2 or b.dtype.kind not in "iu":
+        raise ValueError("bands must be an integer array [nbands, 2] of channel ranges [lo, hi)")
+    if b.size and (b.min() < 0 or np.any(b[:, 0] > b[:, 1]) or b[:, 1].max() > nchans):
+        raise ValueError(f"every band must be a channel range lo <= hi <= {nchans}")
+    return np.ascontiguousarray(b, dtype=np.uint32)
+
+
 def dedisperse_workspace_bytes(dtype, nsamp_blk, nchans, zero_dm=False, nbits=None):
     """Device workspace bytes of dedisperse_device for a block of this shape;
     dtype is 'uint8', 'int8', 'float32' or a packed type name ('u1', 'u2',
@@ -468,6 +479,66 @@ def dedisperse_device(block, delays, max_delay, mask=None, out=None, out_offset=
             _check(_L.rt_dedisperse_device_opt(*args, DEDISP_ZERO_DM))
         else:
             _check(_L.rt_dedisperse_device(*args))
+    return out
+
+
+def dedisperse_bands_device(block, delays, max_delay, bands, mask=None, out=None, out_offset=0, workspace=None,
+                            stream=None, zero_dm=False, nbits=None):
+    """dedisperse_device for every band of a table at once
+    (rt_dedisperse_bands_device): bands is uint32 [nbands, 2] of channel
+    ranges [lo, hi) -- a numpy array, or a contiguous int32 tensor on the
+    block's device holding the same bits -- and
+    out[d, b, out_offset + t] = the sum over the unmasked channels c in
+    [lo_b, hi_b) of block[t + delays[d, c], c].  Bands may overlap, be empty
+    (a row of zeros, as is a band whose channels are all masked) and come in
+    any order; the delays are the plain call's, so the bands stay aligned, and
+    the row of the band [0, nchans) equals dedisperse_device's bit for bit.
+    With zero_dm the mean is over the unmasked channels of the whole block.
+    Returns out, float32 [ndm, nbands, >= out_offset + nsamp_blk - max_delay]
+    (contiguous; allocated [ndm, nbands, nsamp_blk - max_delay] when None).
+    One pass over the block for all bands; block, delays, mask, workspace and
+    nbits as for dedisperse_device."""
+    import torch
+    name, nsamp_blk, nchans = _dedisp_block(block, nbits)
+    if (delays.dim() != 2 or delays.dtype != torch.int32 or delays.device != block.device
+            or not delays.is_contiguous() or delays.shape[1] != nchans):
+        raise ValueError("delays must be a contiguous int32 [ndm, nchans] tensor on the block's device")
+    ndm = delays.shape[0]
+    if mask is not None and (mask.dtype != torch.uint8 or mask.device != block.device or not mask.is_contiguous()
+                             or tuple(mask.shape) != (nchans,)):
+        raise ValueError("mask must be a contiguous uint8 [nchans] tensor on the block's device")
+    max_delay = int(max_delay)
+    nout = nsamp_blk - max_delay
+    s = stream if stream is not None else torch.cuda.current_stream(block.device)
+    with torch.cuda.device(block.device), torch.cuda.stream(s):
+        if not torch.is_tensor(bands):
+            bands = torch.from_numpy(checked_bands(bands, nchans).view(np.int32)).to(block.device)
+        if (bands.dim() != 2 or bands.dtype != torch.int32 or bands.device != block.device
+                or not bands.is_contiguous() or bands.shape[1] != 2):
+            raise ValueError("bands must be uint32 [nbands, 2] (as a tensor: contiguous int32 on the block's device)")
+        nbands = bands.shape[0]
+        # validates the shape before anything is allocated
+        need = dedisperse_workspace_bytes(name, nsamp_blk, nchans, zero_dm)
+        if not 0 <= max_delay < nsamp_blk:
+            raise ValueError(f"max_delay {max_delay} must be in [0, {nsamp_blk}): the block is no longer than the "
+                             "largest delay")
+        if out is None:
+            out = torch.empty((ndm, nbands, nout), dtype=torch.float32, device=block.device)
+        elif (out.dim() != 3 or out.dtype != torch.float32 or out.device != block.device
+              or tuple(out.shape[:2]) != (ndm, nbands) or not out.is_contiguous()
+              or out.shape[2] < int(out_offset) + nout):
+            raise ValueError(f"out must be a contiguous float32 [{ndm}, {nbands}, >= {int(out_offset) + nout}] "
+                             "tensor on the block's device")
+        if workspace is None:
+            workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=block.device)
+        elif (workspace.dtype != torch.uint8 or workspace.device != block.device or not workspace.is_contiguous()
+              or workspace.numel() < need):
+            raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on the block's device")
+        _check(_L.rt_dedisperse_bands_device(_lib.ptr(block), DEDISP_DTYPES[name], nsamp_blk, nchans,
+                                             _lib.ptr(delays), None if mask is None else _lib.ptr(mask), ndm,
+                                             _lib.ptr(bands) if nbands else None, nbands, max_delay, _lib.ptr(out),
+                                             out.shape[2], int(out_offset), _lib.ptr(workspace), workspace.numel(),
+                                             _stream_handle(s), DEDISP_ZERO_DM if zero_dm else 0))
     return out
 
 

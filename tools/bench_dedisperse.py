@@ -17,6 +17,11 @@ inside the transpose): 4096 rows of uniform values packed on the host with
 reading.pack_samples and repeated down the block.  --stream adds the streamed
 dedisperse_filterbank of a file of the same rows (written to --stream-dir,
 page cache warm), the upload included.
+--bands N adds engine.dedisperse_bands_device on the same block and DM list
+with the N sub-bands of dedispersion.band_edges: the same reads and additions
+as the plain call, N times its output.  Reported next to the plain call's time
+with both outputs' bytes and the time the plain call would take for the extra
+output at the bandwidth it achieved.
 A record, not a gate: prints one JSON line and writes it to --out.
 
     python tools/bench_dedisperse.py --out profiles/<tag>_dedisperse.json
@@ -44,6 +49,7 @@ def main():
     ap.add_argument("--stats", action="store_true", help="also time the channel statistics")
     ap.add_argument("--nbits", type=int, default=0, choices=[0, 1, 2, 4, 16],
                     help="time packed rows of this width instead of 8-bit samples")
+    ap.add_argument("--bands", type=int, default=0, help="also time the sub-band call with this many bands")
     ap.add_argument("--stream", action="store_true", help="also time dedisperse_filterbank on a file of the block")
     ap.add_argument("--stream-dir", default="/tmp")
     args = ap.parse_args()
@@ -52,7 +58,7 @@ def main():
     import torch
     import bench
     from riptide_amd import engine
-    from riptide_amd.dedispersion import dedisperse_filterbank, dispersion_delays
+    from riptide_amd.dedispersion import band_edges, dedisperse_filterbank, dispersion_delays
     from riptide_amd.reading import open_filterbank, pack_samples, unpack_samples, write_sigproc
 
     nchans, nsamp, ndm, tsamp = args.nchans, 1 << args.log2_nsamp, args.ndm, 256e-6
@@ -160,6 +166,26 @@ def main():
         smed = float(np.median(sms))
         extra.update({"stats_ms_median": smed, "stats_ms_min": float(np.min(sms)), "stats_ms_max": float(np.max(sms)),
                       "stats_block_gb_per_s": block_bytes / (smed * 1e-3) / 1e9})
+    if args.bands:
+        d_bands = torch.from_numpy(band_edges(nchans, args.bands).view(np.int32)).cuda()
+        bout = torch.empty((ndm, args.bands, nout), dtype=torch.float32, device="cuda")
+
+        def run_bands():
+            engine.dedisperse_bands_device(block, d_delays, max_delay, d_bands, out=bout, workspace=ws, nbits=nbits)
+
+        run_bands()
+        torch.cuda.synchronize()
+        if nbits != 16:     # integer sums: the bands of a partition add up to the plain call's row exactly
+            parts = bout[dm_rows, :, t_chk:t_chk + 64].to(torch.float64).sum(dim=1)
+            assert torch.equal(parts, got), "the sub-band sums do not add up to the plain call's"
+        bms = timed(run_bands)
+        bmed = float(np.median(bms))
+        plain_rate = (block_bytes + out.numel() * 4) / (med * 1e-3)     # bytes/s the plain call achieved
+        extra.update({"bands": args.bands, "bands_call_ms_median": bmed, "bands_call_ms_min": float(np.min(bms)),
+                      "bands_call_ms_max": float(np.max(bms)), "bands_output_bytes": bout.numel() * 4,
+                      "plain_output_bytes": out.numel() * 4, "bands_to_plain_ratio": bmed / med,
+                      "plain_plus_extra_output_ms": med + (bout.numel() - out.numel()) * 4 / plain_rate * 1e3})
+        del bout
     if args.stream:
         # the same rows as a file, streamed in the default gulps: upload + kernels
         fname = os.path.join(args.stream_dir, f"bench_dedisperse_{dname}.fil")
