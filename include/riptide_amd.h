@@ -369,6 +369,80 @@ int rt_fold_device(const float* d_data, size_t size, size_t data_stride, size_t 
 int rt_fold(const float* x, size_t size, size_t nseries, const rt_fold_spec* specs, size_t nspecs,
             float* out, size_t out_floats);
 
+/* ------------------------- candidate refinement ---------------------------- */
+/* The search over small period and DM offsets that follows a sub-band fold:
+ * the sub-bands and the sub-integrations of a folded cube are re-aligned by
+ * whole bins and the boxcar S/N of every trial's profile is taken.  For a cube
+ * x[b][s][n] (float32, B bands, S sub-integrations, N bins), shift tables
+ * dshift[k][b] (K DM trials) and pshift[j][s] (J period trials) with entries in
+ * [0, N), W widths in [1, N - 1] and stdnoise > 0:
+ *   y[k][s][n]    = sum over b = 0..B-1 of x[b][s][(n + dshift[k][b]) mod N]
+ *   prof[k][j][n] = sum over s = 0..S-1 of y[k][s][(n + pshift[j][s]) mod N]
+ *   snr[k][j][w]  = snr1 of prof[k][j][:] at width w with stdnoise
+ * The sums are float32, start from 0.0f and add in index order: host and
+ * device profiles have the same bits.  The S/N's prefix sums are taken in
+ * another order on the device: S/N agrees to rounding, not to bits. */
+
+/* Host only, the physics in double (operation order: refine_host.hpp):
+ *   pshift[j][s] = floor(N*T*(1/P - 1/P_j) * ((s + 0.5)/S - 0.5) + 0.5)          mod N
+ *   dshift[k][b] = floor(N * kdm*(DM_k - DM)*(f[b]^-2 - fmax^-2) / P + 0.5)      mod N
+ * P: the fold period; T: the fold's span in seconds (m * P, m of rt_fold_shape);
+ * f: band centre frequencies in MHz, fmax their maximum; DM: the fold's.
+ * pshift: J x S, dshift: K x B, int32 in [0, N).  RT_EINVAL for P, T, a trial
+ * period or a frequency that is not positive and finite, N < 2, S, B, J or K
+ * of 0, a shift of magnitude 2^31 or more before the reduction (a trial DM
+ * that is not finite is one). */
+int rt_refine_shifts(double period, double span, size_t bins, size_t subints, const double* band_freqs,
+                     size_t bands, double dm, double kdm, const double* periods, size_t nper, const double* dms,
+                     size_t ndm, int32_t* pshift, int32_t* dshift);
+
+/* Host only: the specification above for one candidate, sequential, with
+ * snr1's prefix sums (a double accumulator stored as float32).  snr: K x J x W;
+ * prof: K x J x N, or NULL.  RT_EINVAL for N < 2, a count of 0, a shift
+ * outside [0, N), a width outside [1, N - 1] and stdnoise <= 0 (the last two
+ * with snr1's texts). */
+int rt_refine_host(const float* cube, size_t bands, size_t subints, size_t bins, const int32_t* dshift, size_t ndm,
+                   const int32_t* pshift, size_t nper, const uint32_t* widths, size_t num_widths, float stdnoise,
+                   float* snr, float* prof);
+
+/* One candidate of a batched call: where its arrays lie in the call's packed
+ * buffers, and its shape.  Candidates of different shapes share a call. */
+typedef struct rt_refine_spec {
+    uint64_t cube_off;    /* float offset of the cube [bands][subints][bins] in cubes */
+    uint64_t dshift_off;  /* int32 offset of dshift [ndm][bands] in shifts */
+    uint64_t pshift_off;  /* int32 offset of pshift [nper][subints] in shifts */
+    uint64_t width_off;   /* uint32 offset of the nw widths in widths */
+    uint64_t snr_off;     /* float offset of the result [ndm][nper][nw] in snr */
+    uint64_t prof_off;    /* float offset of [ndm][nper][bins] in profiles (unused without profiles) */
+    uint32_t bands, subints;
+    uint32_t bins;        /* 2 .. 1024 */
+    uint32_t ndm, nper, nw;
+    float    stdnoise;
+    uint32_t reserved;
+} rt_refine_spec;
+
+/* Host only: device workspace bytes of a call with these specs (the
+ * descriptor table and y of every candidate).  Validates the shapes. */
+int rt_refine_workspace_bytes(const rt_refine_spec* specs, size_t nspecs, size_t* bytes);
+/* Refine `nspecs` candidates whose arrays are device resident.  Stream-ordered:
+ * no host synchronisation and no device allocation; `specs` is host memory,
+ * read before the call returns through a pinned staging buffer the library
+ * owns (as rt_fold_device).  d_profiles may be NULL.  The buffers carry no
+ * lengths: the caller answers for every offset of `specs` lying inside them.
+ * Device tables are not validated and cannot cause a read outside the cube:
+ * a shift v is used as (uint32_t)v mod bins, a width is clamped to
+ * [1, bins - 1].  RT_EINVAL (nothing is launched) for bins outside [2, 1024],
+ * a count of 0, stdnoise <= 0, a null pointer, a workspace below
+ * rt_refine_workspace_bytes.  nspecs == 0 is RT_OK. */
+int rt_refine_device(const float* d_cubes, const int32_t* d_shifts, const uint32_t* d_widths,
+                     const rt_refine_spec* specs, size_t nspecs, float* d_snr, float* d_profiles,
+                     void* d_workspace, size_t workspace_bytes, void* stream);
+/* Host-buffer form: validates every table as rt_refine_host does, uploads the
+ * arrays once (their lengths: the furthest end any spec names), runs every
+ * candidate, copies the S/N (and the profiles, unless NULL) back.  Synchronous. */
+int rt_refine(const float* cubes, const int32_t* shifts, const uint32_t* widths, const rt_refine_spec* specs,
+              size_t nspecs, float* snr, float* profiles);
+
 /* --------------------------- harmonic flagging ----------------------------- */
 /* riptide/pipeline/harmonic_testing.py (hdiag, htest) and the pair loop of
  * Pipeline.flag_harmonics (pipeline/pipeline.py:217-249).  A cluster is its

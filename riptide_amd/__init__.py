@@ -23,6 +23,7 @@ from .candidate import Candidate, build_candidates, build_candidates_filterbank
 from .harmonic_testing import apply_candidate_filters, flag_harmonics, hdiag, htest
 from .reading import Filterbank, PackedFilterbank, open_filterbank
 from .dispatch import search_filterbank
+from .refine import Refinement, refine_candidates, refine_cube
 from . import dedispersion, rfi
 
 __all__ = [
@@ -32,5 +33,5 @@ __all__ = [
     "generate_signal", "downsample", "boxcar_snr", "find_peaks", "running_median",
     "fast_running_median", "generate_width_trials", "cluster1d", "Peak", "Filterbank", "search_filterbank",
     "PackedFilterbank", "open_filterbank",
-    "dedispersion", "rfi",
+    "dedispersion", "rfi", "Refinement", "refine_cube", "refine_candidates",
 ]

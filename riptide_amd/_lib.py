@@ -42,6 +42,14 @@ _SIGNATURES = {
     "rt_fold_workspace_bytes": (_c_i, [_c_sz, _vp, _c_sz, _psz]),
     "rt_fold_device": (_c_i, [_vp, _c_sz, _c_sz, _c_sz, _vp, _c_sz, _vp, _c_sz, _vp, _c_sz, _vp]),
     "rt_fold": (_c_i, [_vp, _c_sz, _c_sz, _vp, _c_sz, _vp, _c_sz]),
+    # period, span, bins, subints, band freqs, bands, dm, kdm, periods, nper, dms, ndm, pshift, dshift
+    "rt_refine_shifts": (_c_i, [_c_d, _c_d, _c_sz, _c_sz, _vp, _c_sz, _c_d, _c_d, _vp, _c_sz, _vp, _c_sz, _vp, _vp]),
+    # cube, bands, subints, bins, dshift, ndm, pshift, nper, widths (uint32), nw, stdnoise, snr, prof or NULL
+    "rt_refine_host": (_c_i, [_vp, _c_sz, _c_sz, _c_sz, _vp, _c_sz, _vp, _c_sz, _vp, _c_sz, _c_f, _vp, _vp]),
+    "rt_refine_workspace_bytes": (_c_i, [_vp, _c_sz, _psz]),
+    # cubes, shifts, widths, specs, nspecs, snr, profiles or NULL, workspace, workspace bytes, stream
+    "rt_refine_device": (_c_i, [_vp, _vp, _vp, _vp, _c_sz, _vp, _vp, _vp, _c_sz, _vp]),
+    "rt_refine": (_c_i, [_vp, _vp, _vp, _vp, _c_sz, _vp, _vp]),
     "rt_periodogram_length": (_c_i, [_c_sz, _c_d, _c_d, _c_d, _c_sz, _c_sz, _psz]),
     "rt_periodogram": (_c_i, [_vp, _c_sz, _c_d, _vp, _c_sz, _c_d, _c_d, _c_sz, _c_sz, _vp, _vp, _vp]),
     "rt_running_median": (_c_i, [_vp, _c_sz, _c_sz, _vp]),

@@ -41,15 +41,18 @@ class Candidate:
         data, float32 (num_bands, num_subints, num_bins), or (num_bands,
         num_bins) for a single sub-integration (build_candidates_filterbank).
     band_freqs: None, or the mean channel frequency of each sub-band in MHz.
+    refined: None, or the refine.Refinement of `subbands` over period and DM
+        offsets (refine.refine_candidates); `params` is not altered by it.
     """
 
-    def __init__(self, params, tsmeta, peaks, subints, subbands=None, band_freqs=None):
+    def __init__(self, params, tsmeta, peaks, subints, subbands=None, band_freqs=None, refined=None):
         self.params = params
         self.tsmeta = tsmeta
         self.peaks = peaks
         self.subints = subints
         self.subbands = subbands
         self.band_freqs = band_freqs
+        self.refined = refined
 
     @property
     def profile(self):
@@ -76,12 +79,15 @@ class Candidate:
             items["subbands"] = self.subbands
         if self.band_freqs is not None:
             items["band_freqs"] = self.band_freqs
+        if self.refined is not None:
+            items["refined"] = self.refined
         return items
 
     @classmethod
     def from_dict(cls, items):
         return cls(items["params"], items["tsmeta"], items["peaks"], items["subints"],
-                   subbands=items.get("subbands"), band_freqs=items.get("band_freqs"))
+                   subbands=items.get("subbands"), band_freqs=items.get("band_freqs"),
+                   refined=items.get("refined"))
 
     @classmethod
     def from_folded(cls, ts, peak_cluster, subints_array):
@@ -187,7 +193,7 @@ class _SeriesShape(namedtuple("_SeriesShape", "nsamp tsamp")):
 
 
 def build_candidates_filterbank(clusters, fb_or_fname, range_confs, deredden_params, nsub=32, mask=None,
-                                zero_dm=False, kdm=None, nout=None, budget_bytes=None, device=None):
+                                zero_dm=False, kdm=None, nout=None, budget_bytes=None, device=None, refine=False):
     """Candidates of a list of PeakClusters, by decreasing S/N, straight from
     the channelised file (a name for reading.open_filterbank, or a Filterbank /
     PackedFilterbank): build_candidates without a load_series, and every
@@ -208,7 +214,11 @@ def build_candidates_filterbank(clusters, fb_or_fname, range_confs, deredden_par
     those DMs; pass the search's own nout to fold exactly what was searched).
     mask, zero_dm, kdm: as for search_filterbank.  tsmeta is the file's
     metadata with `dm` set, as search_filterbank's trials have it.  A cluster
-    that cannot be folded is logged and left out."""
+    that cannot be folded is logged and left out.
+
+    refine=True: every candidate is then refined in period and DM from its
+    sub-bands (refine.refine_candidates with its defaults, one device call) and
+    carries the result as `refined`."""
     import torch
     from . import engine
     from .dedispersion import DEFAULT_BUDGET_BYTES, KDM, band_edges, band_series, dispersion_delays
@@ -262,6 +272,9 @@ def build_candidates_filterbank(clusters, fb_or_fname, range_confs, deredden_par
             arrs = torch.stack(folds[k * nbands:(k + 1) * nbands]).cpu().numpy()
             candidates.append(Candidate(cl.centre.summary_dict(), fb.metadata(dm), cl.summary_dataframe(),
                                         arrs[-1].copy(), subbands=arrs[:-1].copy(), band_freqs=band_freqs))
+    if refine:
+        from .refine import refine_candidates
+        refine_candidates(candidates, kdm=kdm, nsamp=nout)
     candidates.sort(key=lambda c: c.params["snr"], reverse=True)
     log.info(f"Total candidates: {len(candidates)}")
     return candidates

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -86,6 +87,43 @@ struct DeviceGuard {
     DeviceGuard(const DeviceGuard&) = delete;
     DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
+
+// ---- pinned staging of host tables for stream-ordered entry points
+// A buffer belongs to the call that filled it until the stream has passed the
+// copy out of it (its event); later calls reuse the buffers whose event has
+// completed.  The buffers and their events live for the rest of the process.
+struct PinnedStage {
+    void* h = nullptr;
+    size_t bytes = 0;
+    hipEvent_t ev = nullptr;
+    int device = 0;
+    bool pending = false;
+};
+
+// a free buffer of `pool` of at least `bytes` on the current device, or a new
+// one; the caller holds the pool's mutex, fills the buffer, queues the copy,
+// sets `pending` and records `ev`
+inline PinnedStage* pinned_stage_acquire(std::vector<PinnedStage*>& pool, size_t bytes)
+{
+    int device = 0;
+    ck(hipGetDevice(&device), "hipGetDevice");
+    for (PinnedStage* st : pool) {
+        if (st->device != device || st->bytes < bytes) continue;
+        if (st->pending && hipEventQuery(st->ev) != hipSuccess) continue;
+        st->pending = false;
+        return st;
+    }
+    std::unique_ptr<PinnedStage> st(new PinnedStage());
+    st->device = device;
+    st->bytes = std::max<size_t>(bytes, 4096);
+    ck(hipHostMalloc(&st->h, st->bytes, hipHostMallocDefault), "hipHostMalloc");
+    if (hipEventCreateWithFlags(&st->ev, hipEventDisableTiming) != hipSuccess) {
+        (void)hipHostFree(st->h);
+        throw HipError("hipEventCreate failed");
+    }
+    pool.push_back(st.get());
+    return st.release();
+}
 
 // ---- profiling of cone / downsample launches
 struct ProfRec {

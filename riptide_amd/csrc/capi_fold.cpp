@@ -15,40 +15,9 @@ using namespace rt;
 
 namespace {
 
-// Pinned staging buffers of the descriptor tables.  A buffer belongs to the
-// call that filled it until the stream has passed the copy out of it (its
-// event); later calls reuse the buffers whose event has completed.
-struct FoldStage {
-    void* h = nullptr;
-    size_t bytes = 0;
-    hipEvent_t ev = nullptr;
-    int device = 0;
-    bool pending = false;
-};
+// pinned staging buffers of the descriptor tables (capi_device.hpp)
 std::mutex g_fold_mu;
-std::vector<FoldStage*> g_fold_stages;
-
-FoldStage* fold_stage_acquire(size_t bytes)   // g_fold_mu held
-{
-    int device = 0;
-    ck(hipGetDevice(&device), "hipGetDevice");
-    for (FoldStage* st : g_fold_stages) {
-        if (st->device != device || st->bytes < bytes) continue;
-        if (st->pending && hipEventQuery(st->ev) != hipSuccess) continue;
-        st->pending = false;
-        return st;
-    }
-    std::unique_ptr<FoldStage> st(new FoldStage());
-    st->device = device;
-    st->bytes = std::max<size_t>(bytes, 4096);
-    ck(hipHostMalloc(&st->h, st->bytes, hipHostMallocDefault), "hipHostMalloc");
-    if (hipEventCreateWithFlags(&st->ev, hipEventDisableTiming) != hipSuccess) {
-        (void)hipHostFree(st->h);
-        throw HipError("hipEventCreate failed");
-    }
-    g_fold_stages.push_back(st.get());
-    return st.release();
-}
+std::vector<PinnedStage*> g_fold_stages;
 
 void run_fold(const FoldPlan& P, const rt_fold_spec* specs, const float* d_data, size_t size, size_t data_stride,
               float* d_out, void* d_ws, hipStream_t s)
@@ -59,7 +28,7 @@ void run_fold(const FoldPlan& P, const rt_fold_spec* specs, const float* d_data,
     float* rows_ws = (float*)((char*)d_ws + P.table_bytes);
     {
         std::lock_guard<std::mutex> lk(g_fold_mu);
-        FoldStage* st = fold_stage_acquire((nr + ns) * sizeof(FoldCand));
+        PinnedStage* st = pinned_stage_acquire(g_fold_stages, (nr + ns) * sizeof(FoldCand));
         FoldCand* h = (FoldCand*)st->h;
         for (size_t i = 0; i < nr; ++i) {
             h[i] = P.rows[i];

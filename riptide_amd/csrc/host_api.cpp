@@ -2,7 +2,8 @@
 // search parameters, read back without a device.  Each is checked_params ->
 // planner (plan.hpp) -> copy out; rt_plan_create (capi_pgram.cpp) uploads the
 // same plan_periodogram result.  Likewise the fold's shape and workspace
-// (fold_host.hpp) and the dereddening workspace (dered_host.hpp).  No HIP
+// (fold_host.hpp), the dereddening workspace (dered_host.hpp) and the candidate
+// refinement's shift tables, specification and workspace (refine_host.hpp).  No HIP
 // header (`make asan` builds this file as is).
 #include "riptide_amd.h"
 
@@ -14,6 +15,7 @@
 #include "fold_host.hpp"
 #include "peaks_host.hpp"
 #include "plan.hpp"
+#include "refine_host.hpp"
 
 using namespace rt;
 
@@ -191,6 +193,35 @@ int rt_fold_workspace_bytes(size_t size, const rt_fold_spec* specs, size_t nspec
 {
     return guarded([&] {
         const size_t need = fold_plan(size, specs, nspecs).ws_bytes;
+        if (bytes) *bytes = need;
+        return RT_OK;
+    });
+}
+
+int rt_refine_shifts(double period, double span, size_t bins, size_t subints, const double* band_freqs, size_t bands,
+                     double dm, double kdm, const double* periods, size_t nper, const double* dms, size_t ndm,
+                     int32_t* pshift, int32_t* dshift)
+{
+    return guarded([&] {
+        refine_shifts(period, span, bins, subints, band_freqs, bands, dm, kdm, periods, nper, dms, ndm, pshift, dshift);
+        return RT_OK;
+    });
+}
+
+int rt_refine_host(const float* cube, size_t bands, size_t subints, size_t bins, const int32_t* dshift, size_t ndm,
+                   const int32_t* pshift, size_t nper, const uint32_t* widths, size_t num_widths, float stdnoise,
+                   float* snr, float* prof)
+{
+    return guarded([&] {
+        refine_host(cube, bands, subints, bins, dshift, ndm, pshift, nper, widths, num_widths, stdnoise, snr, prof);
+        return RT_OK;
+    });
+}
+
+int rt_refine_workspace_bytes(const rt_refine_spec* specs, size_t nspecs, size_t* bytes)
+{
+    return guarded([&] {
+        const size_t need = refine_plan(specs, nspecs).ws_bytes;
         if (bytes) *bytes = need;
         return RT_OK;
     });

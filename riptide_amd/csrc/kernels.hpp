@@ -6,6 +6,7 @@
 #include "dered_host.hpp"
 #include "fold_host.hpp"
 #include "harmonic.hpp"
+#include "refine_host.hpp"
 
 namespace rt {
 
@@ -78,6 +79,14 @@ hipError_t launch_fold_rows(const float* data, uint64_t n_in, const FoldCand* d_
                             uint32_t total_blocks, float* out, float* rows_ws, hipStream_t s);
 hipError_t launch_fold_subints(const FoldCand* d_cands, uint32_t num_cands, uint32_t total_blocks, float* out,
                                const float* rows_ws, hipStream_t s);
+
+// refine_kernels.hip
+// the candidate descriptor RefineCand and the plan's block counts and LDS
+// bytes: refine_host.hpp.  Stage A (y of every candidate into d_y), then stage
+// B (S/N, and the profiles unless d_profiles is null).
+hipError_t launch_refine(const float* d_cubes, const int32_t* d_shifts, const uint32_t* d_widths,
+                         const RefineCand* d_cands, uint32_t num_cands, uint32_t blocks_a, uint32_t blocks_b,
+                         uint32_t lds_a, uint32_t lds_b, float* d_y, float* d_snr, float* d_profiles, hipStream_t s);
 
 // dedisp_kernels.hip
 // bits of a packed sample type code (RT_DEDISP_U1, U2, U4, U16: the block is

@@ -295,6 +295,47 @@ def fold_device(data, tsamp, specs, stream=None):
     return results
 
 
+def refine_device(cubes, shifts, widths, table, profiles=False, stream=None):
+    """refine.refine_many for arrays that stay on the device
+    (rt_refine_device): cubes float32, shifts int32 and widths int32 (values
+    below 2^31, read as uint32) are flat device tensors, packed as
+    refine.pack_refine packs them; table is its host REFINE_SPEC array.
+    Returns (snr, prof): flat float32 device tensors holding each candidate's
+    [K, J, W] and [K, J, N] at its snr_off / prof_off (prof is None without
+    profiles=True).  Stream-ordered, no host synchronisation.
+
+    The device tables are not validated, and need not be: a shift v is used
+    as (v mod 2^32) mod bins and a width is clamped to [1, bins - 1].  Every
+    offset of `table` must lie inside the tensors: that is checked here."""
+    import torch
+    from .refine import REFINE_SPEC
+    table = np.ascontiguousarray(table, dtype=REFINE_SPEC)
+    for t, dt, name in ((cubes, torch.float32, "cubes"), (shifts, torch.int32, "shifts"), (widths, torch.int32, "widths")):
+        if t.dim() != 1 or t.dtype != dt or t.device.type != "cuda" or not t.is_contiguous():
+            raise ValueError(f"{name} must be a flat contiguous {dt} device tensor")
+    if not table.size:
+        return torch.empty(0, dtype=torch.float32, device=cubes.device), None
+    u = {k: table[k].astype(np.uint64) for k in table.dtype.names if k not in ("stdnoise", "reserved")}
+    if (int((u["cube_off"] + u["bands"] * u["subints"] * u["bins"]).max()) > cubes.numel()
+            or int((u["dshift_off"] + u["ndm"] * u["bands"]).max()) > shifts.numel()
+            or int((u["pshift_off"] + u["nper"] * u["subints"]).max()) > shifts.numel()
+            or int((u["width_off"] + u["nw"]).max()) > widths.numel()):
+        raise ValueError("refine: a spec's arrays exceed the device tensors")
+    nsnr = int((u["snr_off"] + u["ndm"] * u["nper"] * u["nw"]).max())
+    nprof = int((u["prof_off"] + u["ndm"] * u["nper"] * u["bins"]).max())
+    need = ctypes.c_size_t()
+    _check(_L.rt_refine_workspace_bytes(_lib.ptr(table), table.size, ctypes.byref(need)))
+    s = stream if stream is not None else torch.cuda.current_stream(cubes.device)
+    with torch.cuda.device(cubes.device), torch.cuda.stream(s):
+        snr = torch.empty(nsnr, dtype=torch.float32, device=cubes.device)
+        prof = torch.empty(nprof, dtype=torch.float32, device=cubes.device) if profiles else None
+        workspace = torch.empty(max(need.value, 1), dtype=torch.uint8, device=cubes.device)
+        _check(_L.rt_refine_device(_lib.ptr(cubes), _lib.ptr(shifts), _lib.ptr(widths), _lib.ptr(table), table.size,
+                                   _lib.ptr(snr), _lib.ptr(prof) if profiles else None, _lib.ptr(workspace),
+                                   workspace.numel(), _stream_handle(s)))
+    return snr, prof
+
+
 # RT_DEDISP_* sample type codes (include/riptide_amd.h); 'u1', 'u2', 'u4' and
 # 'u16' are the packed types: the block is then uint8 rows of nchans * nbits / 8
 # bytes (reading.unpack_samples has the format)
