@@ -124,6 +124,30 @@ int rt_schedule_final_kinds(size_t size, double tsamp, const uint64_t* widths, s
                             double period_max, size_t bins_min, size_t bins_max, uint64_t* launches,
                             uint64_t* rows_launches, uint64_t* seg_launches, uint8_t* bins_kinds, size_t bins_cap);
 
+/* Host-only, no device: the work units of the pass schedule
+ * rt_schedule_check builds for these parameters, in dispatch order (the
+ * workgroups of a launch start in this order), launch after launch.  A unit
+ * of a pass-0 launch (src_leaves = 1) reads the floats [node_start * bins,
+ * (node_start + node_size) * bins) of its rung's downsampled series.
+ * Writes min(*count, cap) records (items may be NULL when cap == 0); *count
+ * may be NULL. */
+typedef struct rt_schedule_item {
+    uint32_t launch;      /* index of the unit's launch */
+    uint32_t pass;        /* the launch's pass within its transform group */
+    uint32_t slots;       /* the launch's kernel variant (merge slot width) */
+    uint32_t snr_kind;    /* 0 merge-only, 1 / 2 final with the row-group / segmented S/N */
+    uint32_t xform;       /* transform index */
+    uint32_t rung;        /* the transform's ladder rung */
+    uint32_t bins;        /* the transform's phase bins */
+    uint32_t node_start, node_size;   /* target node, rows of the transform */
+    uint32_t s0, s1;      /* output rows [s0, s1) within the node */
+    uint32_t levels;      /* merge levels the unit evaluates */
+    uint32_t src_leaves;  /* 1: the unit fills from the rung leaf buffer */
+    uint32_t tile;        /* 0: a whole node in LDS, 1: a tile of a node's upper levels */
+} rt_schedule_item;
+int rt_schedule_items(size_t size, double tsamp, size_t num_widths, double period_min, double period_max,
+                      size_t bins_min, size_t bins_max, rt_schedule_item* items, size_t cap, uint64_t* count);
+
 /* Host-only: the downsampling-ladder kernel a periodogram plan of these
  * parameters runs (periodogram.hpp:162-168 restated per rung): *fused = 1
  * for the one-read fused ladder (32-bit sample indices: series below 2^29

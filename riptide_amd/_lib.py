@@ -59,6 +59,8 @@ _SIGNATURES = {
     "rt_ffa_schedule_check": (_c_i, [_c_sz, _c_sz, _pu64]),
     "rt_schedule_check": (_c_i, [_c_sz, _c_d, _c_sz, _c_d, _c_d, _c_sz, _c_sz, _pu64, _pu64, _pu64, _pd, _pd,
                                  _pu64]),
+    # size, tsamp, num_widths, pmin, pmax, bmin, bmax, items (rt_schedule_item[cap]), cap, count
+    "rt_schedule_items": (_c_i, [_c_sz, _c_d, _c_sz, _c_d, _c_d, _c_sz, _c_sz, _vp, _c_sz, _pu64]),
     "rt_schedule_final_kinds": (_c_i, [_c_sz, _c_d, _vp, _c_sz, _c_d, _c_d, _c_sz, _c_sz, _pu64, _pu64, _pu64, _vp,
                                        _c_sz]),
     "rt_plan_create": (_c_i, [_c_sz, _c_d, _vp, _c_sz, _c_d, _c_d, _c_sz, _c_sz, _vp]),

@@ -61,7 +61,10 @@ namespace rt {
 
 // One kernel per merge slot width SMAX (units with ceil(p/64) <= SMAX), so each
 // gets its own register allocation; one workgroup per unit u = blockIdx.x
-// (unit u = item u / batch, trial u % batch; items are sorted longest first),
+// (workgroup b runs item b / G for one of its G trial groups, ConeArgs::
+// trials_per_wg; the planner orders a launch's items for dispatch -- longest
+// first, pass 0 by rung and leaf span, plan.cpp order_launch_units -- and
+// nothing here depends on that order),
 // two workgroups per CU: a unit's DMA is waited for at its start, the CU's
 // other workgroup filling the wait.
 //   begin(u) [DMA] | wait | merge(u) | store or S/N(u)

@@ -131,6 +131,42 @@ int rt_schedule_check(size_t size, double tsamp, size_t nw, double pmin, double 
     });
 }
 
+int rt_schedule_items(size_t size, double tsamp, size_t nw, double pmin, double pmax, size_t bmin, size_t bmax,
+                      rt_schedule_item* items, size_t cap, uint64_t* count)
+{
+    return guarded([&] {
+        if (cap && !items) throw std::invalid_argument("rt_schedule_items: items is NULL");
+        const ExecPlan ex = host_plan(size, tsamp, nw, 0, pmin, pmax, bmin, bmax).ex;
+        uint64_t n = 0;
+        for (size_t l = 0; l < ex.launches.size(); ++l) {
+            const Launch& L = ex.launches[l];
+            for (uint32_t i = L.first; i < L.first + L.count; ++i, ++n) {
+                if (n >= cap) continue;
+                const ConeItem& it = ex.items[i];
+                const FfaXform& X = ex.xf[it.xform];
+                rt_schedule_item o{};
+                o.launch = (uint32_t)l;
+                o.pass = L.pass;
+                o.slots = L.smax;
+                o.snr_kind = L.snr;
+                o.xform = it.xform;
+                o.rung = X.rung;
+                o.bins = X.p;
+                o.node_start = it.node_start;
+                o.node_size = it.node_size;
+                o.s0 = it.s0;
+                o.s1 = it.s1;
+                o.levels = it.levels;
+                o.src_leaves = it.src == kSelLeaves;
+                o.tile = it.mode == kModeTile;
+                items[n] = o;
+            }
+        }
+        if (count) *count = n;
+        return RT_OK;
+    });
+}
+
 int rt_schedule_final_kinds(size_t size, double tsamp, const uint64_t* widths, size_t nw, double pmin, double pmax,
                             size_t bmin, size_t bmax, uint64_t* launches, uint64_t* rows_launches,
                             uint64_t* seg_launches, uint8_t* bins_kinds, size_t bins_cap)

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cmath>
+#include <map>
 #include <stdexcept>
 #include <string>
 
@@ -285,6 +286,65 @@ static double item_cost(const ConeItem& it, const FfaXform& X)
     return rows * (double)X.p * ((double)it.levels + 2.0);
 }
 
+// Dispatch order of one launch's units (workgroups start in item order).
+// Every launch: longest first, so the launch tail is made of the cheapest
+// units.  A pass-0 launch (every unit fills from the rung leaf buffers) in
+// which some rung feeds more than one transform: rung by rung, the rungs by
+// decreasing cost of their longest unit (unit costs span ~2x, so the tail
+// stays cheap), and inside a rung every transform's units interleaved by the
+// float offset of their first leaf (node_start * p).  The transforms of a
+// rung reshape the same series, so the units that read a stretch of it are
+// then neighbours in dispatch order and all but the first find it in the
+// Infinity Cache: with Lmin / Lmax the shortest / longest leaf span of the
+// rung's units and T its transforms in the launch, all readers of a span lie
+// within T * ceil(2 Lmax / Lmin) positions of each other (each transform's
+// units tile the series, and a span's readers start less than Lmax before
+// its start and before its end), before the XCD transposition below moves
+// each by less than 8 kPass0Run positions.  A launch with one transform per
+// rung keeps the cost order alone, as do the tile launches (pass >= 1).
+// kPass0Run: neighbours in span order that share an XCD, the transforms of a
+// rung at 240-260 bins (21); measured against the span order alone, cfg2
+// 95.71 / 95.73 -> 94.85 / 94.91 ms per step (cost order: 96.38 / 96.40).
+constexpr int kPass0Run = 21;
+static void order_launch_units(std::vector<ConeItem>& items, size_t first, const std::vector<FfaXform>& xf, bool leaves)
+{
+    std::stable_sort(items.begin() + first, items.end(), [&](const ConeItem& x, const ConeItem& y) {
+        return item_cost(x, xf[x.xform]) > item_cost(y, xf[y.xform]);
+    });
+    if (!leaves) return;
+    struct RungUnits { uint32_t xform; bool shared; double cost; };
+    std::map<uint32_t, RungUnits> rungs;
+    bool shared = false;
+    for (size_t i = first; i < items.size(); ++i) {
+        const ConeItem& it = items[i];
+        const double c = item_cost(it, xf[it.xform]);
+        auto r = rungs.emplace(xf[it.xform].rung, RungUnits{it.xform, false, c});
+        RungUnits& R = r.first->second;
+        if (R.xform != it.xform) R.shared = shared = true;
+        R.cost = std::max(R.cost, c);
+    }
+    if (!shared) return;
+    std::stable_sort(items.begin() + first, items.end(), [&](const ConeItem& x, const ConeItem& y) {
+        const FfaXform &X = xf[x.xform], &Y = xf[y.xform];
+        if (X.rung != Y.rung) {
+            const double cx = rungs.find(X.rung)->second.cost, cy = rungs.find(Y.rung)->second.cost;
+            return cx != cy ? cx > cy : X.rung < Y.rung;
+        }
+        return (uint64_t)x.node_start * X.p < (uint64_t)y.node_start * Y.p;
+    });
+    // Workgroups go round-robin to the 8 XCDs, whose L2s share nothing: each
+    // block of 8 kPass0Run units is transposed, so that a run of kPass0Run
+    // neighbours in span order sits at the positions u, u + 8, u + 16, ... of
+    // one XCD and its later readers hit that L2 (the units past the last
+    // whole block stay in span order).  A unit moves less than a block.
+    const size_t block = 8 * (size_t)kPass0Run;
+    std::vector<ConeItem> tmp(block);
+    for (size_t b = first; b + block <= items.size(); b += block) {
+        for (size_t j = 0; j < block; ++j) tmp[j] = items[b + (j % 8) * kPass0Run + j / 8];
+        std::copy(tmp.begin(), tmp.end(), items.begin() + b);
+    }
+}
+
 // Output rows per final tile that leave room for the wide S/N stride (widths
 // past the S/N register window read as plain LDS windows, common.hpp
 // snr_wide_stride), or 0 (no cap: no such widths, or the variant has no wide
@@ -415,13 +475,10 @@ void build_exec_plan(const std::vector<FfaXform>& xforms, bool snr_epilogue, uin
                     L.moved_bytes += sp[k].read + ((last && snr_epilogue) ? 4.0 * X.rows_eval * num_widths : sp[k].written);
                 }
                 L.count = (uint32_t)out.items.size() - L.first;
-                // longest first, so the launch tail is made of the cheapest units
-                std::stable_sort(out.items.begin() + L.first, out.items.end(),
-                                 [&](const ConeItem& x, const ConeItem& y) {
-                                     return item_cost(x, out.xf[x.xform]) > item_cost(y, out.xf[y.xform]);
-                                 });
+                // longest first; pass 0 by rung and leaf span (order_launch_units)
+                order_launch_units(out.items, L.first, out.xf, k == 0);
                 if (!L.count) continue;
-                // whole-node units of every size in one launch, longest first
+                // whole-node units of every size in one launch
                 // (one launch per register-row class, as before round 4, left
                 // CUs idle at each class's drain: cfg2 7.22 -> 7.10, cfg3
                 // 1.864 -> 1.809, cfg1 0.285 -> 0.263 ms per trial, same S/N)

@@ -47,6 +47,25 @@ def ladder_layout(size, tsamp, period_min, period_max, bins_min, bins_max):
     return {"rungs": rungs, "leaf_floats": leaf.value, "mode": mode.value, "margin": margin.value}
 
 
+# rt_schedule_item (include/riptide_amd.h)
+SCHEDULE_ITEM_DTYPE = np.dtype([(k, np.uint32) for k in
+                                ("launch", "pass", "slots", "snr_kind", "xform", "rung", "bins", "node_start",
+                                 "node_size", "s0", "s1", "levels", "src_leaves", "tile")])
+
+
+def schedule_items(size, tsamp, period_min, period_max, bins_min, bins_max, num_widths=0):
+    """The work units of the cone schedule of these search parameters in
+    dispatch order, launch after launch (rt_schedule_items; host only, no
+    device): one SCHEDULE_ITEM_DTYPE record per unit."""
+    args = (int(size), float(tsamp), int(num_widths), float(period_min), float(period_max), int(bins_min),
+            int(bins_max))
+    count = ctypes.c_uint64()
+    _check(_L.rt_schedule_items(*args, None, 0, ctypes.byref(count)))
+    items = np.zeros(count.value, dtype=SCHEDULE_ITEM_DTYPE)
+    _check(_L.rt_schedule_items(*args, _lib.ptr(items), items.size, ctypes.byref(count)))
+    return items
+
+
 class PeriodogramPlan:
     """Compiled periodogram plan for series of `size` samples: downsampling
     ladder, trial grid and the cone-kernel pass schedule (host-built once,
