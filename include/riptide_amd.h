@@ -467,6 +467,65 @@ int rt_refine_device(const float* d_cubes, const int32_t* d_shifts, const uint32
 int rt_refine(const float* cubes, const int32_t* shifts, const uint32_t* widths, const rt_refine_spec* specs,
               size_t nspecs, float* snr, float* profiles);
 
+/* --------------------------- single-pulse search --------------------------- */
+/* Boxcar matched filtering of B series x[b][0..N) (float32, rows ldx floats
+ * apart, assumed dereddened and normalised to unit variance) at K widths
+ * w[0..K) in samples, strictly ascending:
+ *   s[b][k][t] = float32( sum of x[b][t .. t + w_k) / sqrt((double)w_k) )   0 <= t <= N - w_k
+ * The sum is formed in float64 from partial sums in a pinned order
+ * (pulse_host.hpp: sequential runs of 16 samples, the run totals added in
+ * order, the partial sums restarting every RT_PULSE_SEGMENT samples; a window
+ * that crosses restarts is its head, the whole segments between and its tail,
+ * added in that order).  Host and device results have the same bits.
+ *   c_k = w_k / 2 (integer);  best[b][t] = max over k of s[b][k][t - c_k] over
+ *   the widths whose window [t - c_k, t - c_k + w_k) lies inside the row,
+ *   kbest[b][t] the smallest k attaining it (float compares: a NaN never
+ *   wins); no width fits: best = -inf, kbest = -1.
+ * (b, t) is an event iff best[b][t] >= threshold, best[b][t] > best[b][u] for
+ * every u in [t - R, t) and best[b][t] >= best[b][u] for every u in (t, t + R]
+ * (u clipped to the row).  Events are listed in (b, t) order.
+ * RT_EINVAL for K == 0, a width < 1, widths not strictly ascending, the
+ * largest width > N, a width or radius above RT_PULSE_MAX_WIDTH, a threshold
+ * that is not finite, ldx < N, N above RT_PULSE_MAX_SAMPLES. */
+#define RT_PULSE_MAX_WIDTH 6144
+#define RT_PULSE_SEGMENT 1024
+#define RT_PULSE_MAX_SAMPLES 1073741824
+typedef struct rt_pulse_event {
+    int32_t series;   /* b */
+    int32_t sample;   /* t */
+    int32_t iwidth;   /* kbest[b][t] */
+    float   snr;      /* best[b][t] */
+} rt_pulse_event;
+
+/* Host only: the specification, sequential.  events: room for `capacity`
+ * records (NULL when capacity == 0); the first `capacity` events are written,
+ * *count (if not NULL) is the number found, never cut.  best (float32 [B][N])
+ * and kbest (int32 [B][N]) are written unless NULL. */
+int rt_single_pulse_host(const float* x, size_t nseries, size_t size, size_t ldx, const int32_t* widths,
+                         size_t num_widths, float threshold, size_t radius, rt_pulse_event* events, size_t capacity,
+                         uint64_t* count, float* best, int32_t* kbest);
+/* Host only: the device form's tile length in samples (*tile; a launch works on
+ * tiles of this many outputs with a halo of radius + largest width on each
+ * side) and RT_PULSE_MAX_WIDTH (*max_width). */
+int rt_single_pulse_limits(size_t* tile, size_t* max_width);
+/* Host only: device workspace bytes of a call of this shape. */
+int rt_single_pulse_workspace_bytes(size_t nseries, size_t size, size_t num_widths, size_t capacity, size_t* bytes);
+/* The same search of device-resident series.  Stream-ordered: no host
+ * synchronisation and no device allocation; `widths` is host memory, read
+ * before the call returns through a pinned staging buffer the library owns.
+ * d_events: room for `capacity` records (may be NULL when capacity == 0);
+ * *d_count (uint64, device) becomes the number of events found.  When that is
+ * above capacity the records written are not specified: call again with room
+ * for *d_count.  Otherwise d_events[0 .. *d_count) is the host function's
+ * list, in the same order on every run.  d_best / d_kbest: [B][N] contiguous,
+ * or NULL.  Also RT_EINVAL (nothing is launched) for nseries > 65535, a null
+ * pointer, a workspace below rt_single_pulse_workspace_bytes.  nseries == 0
+ * is RT_OK with *d_count = 0. */
+int rt_single_pulse_device(const float* d_x, size_t nseries, size_t size, size_t ldx, const int32_t* widths,
+                           size_t num_widths, float threshold, size_t radius, rt_pulse_event* d_events,
+                           size_t capacity, uint64_t* d_count, float* d_best, int32_t* d_kbest, void* d_workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* --------------------------- harmonic flagging ----------------------------- */
 /* riptide/pipeline/harmonic_testing.py (hdiag, htest) and the pair loop of
  * Pipeline.flag_harmonics (pipeline/pipeline.py:217-249).  A cluster is its

@@ -24,7 +24,8 @@ from .harmonic_testing import apply_candidate_filters, flag_harmonics, hdiag, ht
 from .reading import Filterbank, PackedFilterbank, open_filterbank
 from .dispatch import search_filterbank
 from .refine import Refinement, refine_candidates, refine_cube
-from . import dedispersion, rfi
+from .single_pulse import SinglePulse, search_filterbank_pulses
+from . import dedispersion, rfi, single_pulse
 
 __all__ = [
     "Candidate", "PeakCluster", "build_candidates", "build_candidates_filterbank", "flag_harmonics",
@@ -34,4 +35,5 @@ __all__ = [
     "fast_running_median", "generate_width_trials", "cluster1d", "Peak", "Filterbank", "search_filterbank",
     "PackedFilterbank", "open_filterbank",
     "dedispersion", "rfi", "Refinement", "refine_cube", "refine_candidates",
+    "SinglePulse", "search_filterbank_pulses", "single_pulse",
 ]

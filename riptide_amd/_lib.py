@@ -50,7 +50,16 @@ _SIGNATURES = {
     # cubes, shifts, widths, specs, nspecs, snr, profiles or NULL, workspace, workspace bytes, stream
     "rt_refine_device": (_c_i, [_vp, _vp, _vp, _vp, _c_sz, _vp, _vp, _vp, _c_sz, _vp]),
     "rt_refine": (_c_i, [_vp, _vp, _vp, _vp, _c_sz, _vp, _vp]),
-    "rt_periodogram_length": (_c_i, [_c_sz, _c_d, _c_d, _c_d, _c_sz, _c_sz, _psz]),
+    # x, nseries, size, ldx, widths (int32, host), nw, threshold, radius, events, capacity, count (uint64), best,
+    # kbest
+    "rt_single_pulse_host": (_c_i, [_vp, _c_sz, _c_sz, _c_sz, _vp, _c_sz, _c_f, _c_sz, _vp, _c_sz, _vp, _vp, _vp]),
+    "rt_single_pulse_limits": (_c_i, [_psz, _psz]),
+    # nseries, size, nw, capacity, bytes
+    "rt_single_pulse_workspace_bytes": (_c_i, [_c_sz, _c_sz, _c_sz, _c_sz, _psz]),
+    # as the host form with device x, events, count, best, kbest; then workspace, workspace bytes, stream
+    "rt_single_pulse_device": (_c_i, [_vp, _c_sz, _c_sz, _c_sz, _vp, _c_sz, _c_f, _c_sz, _vp, _c_sz, _vp, _vp, _vp,
+                                      _vp, _c_sz, _vp]),
+    "rt_periodogram_length": (_c_i,[_c_sz, _c_d, _c_d, _c_d, _c_sz, _c_sz, _psz]),
     "rt_periodogram": (_c_i, [_vp, _c_sz, _c_d, _vp, _c_sz, _c_d, _c_d, _c_sz, _c_sz, _vp, _vp, _vp]),
     "rt_running_median": (_c_i, [_vp, _c_sz, _c_sz, _vp]),
     "rt_fast_running_median": (_c_i, [_vp, _c_sz, _c_sz, _c_sz, _vp]),

@@ -127,7 +127,7 @@ class EngineSearcher:
             ev = torch.cuda.Event()
             ev.record(main)
             runs.append((conf, plan, snr, ev))
-        return {"serial": False, "runs": runs, "n": n, "tsamp": tsamp, "dms": dms, "B": B, "device": x.device}
+        return {"serial": False, "runs": runs, "n": n, "tsamp": tsamp, "dms": dms, "B": B, "device": x.device, "x": x}
 
     def _detect(self, pend):
         """Peak detection of a pending batch, range by range, on a side
@@ -214,7 +214,7 @@ class EngineSearcher:
         (8-bit data converted on the device), results in input order."""
         return self.submit_samples(samples, tsamps, metadatas)()
 
-    def search_filterbank(self, fb, dms, mask=None, nout=None, kdm=None, zero_dm=False):
+    def search_filterbank(self, fb, dms, mask=None, nout=None, kdm=None, zero_dm=False, pulses=None):
         """Dedisperse a reading.Filterbank or PackedFilterbank at the trial DMs on the device
         (dedispersion.dedisperse_filterbank) and search every series: one peak
         list per DM, in the order given (the __call__ contract).  The series
@@ -226,11 +226,21 @@ class EngineSearcher:
         is the dispersion constant of the delay table (default:
         dedispersion.KDM); `zero_dm` puts the zero-DM filter in front of the
         sum (dedispersion.dedisperse_filterbank; rfi.channel_mask builds a
-        `mask` from the file's channel statistics)."""
+        `mask` from the file's channel statistics).
+
+        pulses: None, or a dict of single_pulse.search_pulses parameters
+        (widths, threshold, radius, time_radius, dm_gap, max_events): every
+        slice's normalised series then also goes through the single-pulse
+        search (engine.single_pulse_device), and the return is (peak lists,
+        pulses), the SinglePulse list of single_pulse.cluster_events over all
+        DMs; the events behind them (series = index into dms) are kept in
+        self.pulse_events."""
         import torch
         from .dedispersion import KDM, dedisperse_filterbank
         kdm = KDM if kdm is None else float(kdm)
         dms = [float(d) for d in dms]
+        if pulses is not None:
+            return self._search_filterbank_pulses(fb, dms, mask, nout, kdm, zero_dm, dict(pulses))
         if not dms:
             return []
         dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else
@@ -247,6 +257,41 @@ class EngineSearcher:
                 pending = pend
             per.extend(self._detect(pending))
         return per
+
+    def _search_filterbank_pulses(self, fb, dms, mask, nout, kdm, zero_dm, kw):
+        """search_filterbank with the single-pulse search beside the
+        periodicity search: the same calls in the same order, and each slice's
+        normalised series handed to engine.single_pulse_device as well."""
+        import torch
+        from . import engine, single_pulse
+        from .dedispersion import dedisperse_filterbank
+        unknown = set(kw) - {"widths", "threshold", "radius", "time_radius", "dm_gap", "max_events"}
+        if unknown:
+            raise ValueError(f"unknown single-pulse parameters: {sorted(unknown)}")
+        self.pulse_events = np.empty(0, dtype=single_pulse.EVENT_DTYPE)
+        if not dms:
+            return [], []
+        dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else
+                           (self.device.index if isinstance(self.device, torch.device) else int(self.device)))
+        with torch.cuda.device(dev):
+            series = dedisperse_filterbank(fb, dms, mask=mask, device=dev, nout=nout, kdm=kdm, zero_dm=zero_dm)
+            widths = single_pulse._default_widths(kw.get("widths"), series.shape[1])
+            metas = [fb.metadata(dm) for dm in dms]
+            slices = [(b0, min(b0 + self.batch, len(dms))) for b0 in range(0, len(dms), self.batch)]
+            per, parts, pending = [], [], None
+            for b0, b1 in slices:
+                pend = self._enqueue(series[b0:b1], fb.tsamp, metas[b0:b1])
+                ev = engine.single_pulse_device(pend["x"], widths, kw.get("threshold", 8.0), radius=kw.get("radius"),
+                                                max_events=kw.get("max_events", 1 << 20))
+                parts.append(single_pulse.events_to_host(ev, b0))
+                if pending is not None:
+                    per.extend(self._detect(pending))
+                pending = pend
+            per.extend(self._detect(pending))
+        self.pulse_events = np.concatenate(parts)
+        found = single_pulse.cluster_events(self.pulse_events, dms, fb.tsamp, time_radius=kw.get("time_radius"),
+                                            dm_gap=kw.get("dm_gap", 1), widths=widths)
+        return per, found
 
     def __call__(self, trials):
         return self.search_samples([t.data for t in trials], [t.tsamp for t in trials],
@@ -315,7 +360,7 @@ def search_files(fnames, pool, group=None, chunksize=None):
     return _gather_tagged(tagged, group, world)
 
 
-def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=None, zero_dm=False):
+def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=None, zero_dm=False, pulses=None):
     """Search a channelised SIGPROC file (a file name, opened by
     reading.open_filterbank: 1-, 2-, 4-, 8-, 16- or 32-bit samples; or a
     Filterbank / PackedFilterbank) at the trial DMs without leaving the
@@ -328,7 +373,13 @@ def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=Non
     list's largest delay, so the result does not depend on the sharding.
     `kdm` is the dispersion constant of the delay table, on every rank
     (default: dedispersion.KDM); `zero_dm` subtracts every time sample's mean
-    over the unmasked channels before the sum (the zero-DM filter)."""
+    over the unmasked channels before the sum (the zero-DM filter).
+
+    pulses: None, or a dict of single_pulse.search_pulses parameters: every
+    rank then also runs the single-pulse search on its normalised series
+    (EngineSearcher.search_filterbank), the events are gathered as the peak
+    lists are, and the return is (peak list, pulses): the SinglePulse list of
+    single_pulse.cluster_events over the events of every DM, on every rank."""
     from .dedispersion import KDM, dispersion_delays
     kdm = KDM if kdm is None else float(kdm)
     from .reading import Filterbank, open_filterbank
@@ -344,9 +395,30 @@ def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=Non
         mine = shard(len(dms), rank, world)
         # zero_dm is passed only when set: a searcher without the argument keeps working
         extra = {"zero_dm": True} if zero_dm else {}
+        if pulses is not None:
+            extra["pulses"] = pulses
         local = searcher.search_filterbank(fb, [dms[i] for i in mine], mask=mask, nout=fb.nsamp - max_delay,
                                           kdm=kdm, **extra)
+        if pulses is not None:
+            local = local[0]
         if len(local) != len(mine):
             raise RuntimeError("searcher must return one peak list per DM")
         tagged = [(i, [tuple(p) for p in plist]) for i, plist in zip(mine, local)]
-    return _gather_tagged(tagged, group, world)
+    peaks = _gather_tagged(tagged, group, world)
+    if pulses is None:
+        return peaks
+    from . import single_pulse
+    events = np.empty(0, dtype=single_pulse.EVENT_DTYPE)
+    if dms and mine:
+        events = searcher.pulse_events.copy()
+        events["series"] = np.asarray(mine, dtype=np.int32)[events["series"]]
+    if world > 1:
+        import torch.distributed as dist
+        gathered = [None] * world
+        dist.all_gather_object(gathered, events, group=group)
+        events = np.concatenate(gathered)
+    events = events[np.lexsort((events["sample"], events["series"]))]
+    nsamp = fb.nsamp - max_delay if dms else 0
+    widths = single_pulse._default_widths(pulses.get("widths"), nsamp) if dms else None
+    return peaks, single_pulse.cluster_events(events, dms, fb.tsamp, time_radius=pulses.get("time_radius"),
+                                              dm_gap=pulses.get("dm_gap", 1), widths=widths)

@@ -4,6 +4,7 @@ is the engine's HIP kernels (rt_plan_* / rt_periodogram_device /
 rt_deredden_normalise_device in include/riptide_amd.h).
 """
 import ctypes
+import typing
 
 import numpy as np
 
@@ -353,6 +354,91 @@ def refine_device(cubes, shifts, widths, table, profiles=False, stream=None):
                                    _lib.ptr(snr), _lib.ptr(prof) if profiles else None, _lib.ptr(workspace),
                                    workspace.numel(), _stream_handle(s)))
     return snr, prof
+
+
+def _pulse_limits():
+    tile, wmax = ctypes.c_size_t(), ctypes.c_size_t()
+    _check(_L.rt_single_pulse_limits(ctypes.byref(tile), ctypes.byref(wmax)))
+    return tile.value, wmax.value
+
+
+# the single-pulse kernel's tile length in samples, and RT_PULSE_MAX_WIDTH
+# (the largest width and radius; include/riptide_amd.h)
+PULSE_TILE, PULSE_MAX_WIDTH = _pulse_limits()
+# rt_pulse_event (include/riptide_amd.h)
+PULSE_EVENT_DTYPE = np.dtype([("series", np.int32), ("sample", np.int32), ("iwidth", np.int32), ("snr", np.float32)])
+
+
+class PulseEvents(typing.NamedTuple):
+    """The events of single_pulse_device as columns (device tensors of one
+    length), sorted by (series, sample)."""
+    series: typing.Any      # int32: row of the batch
+    sample: typing.Any      # int32
+    iwidth: typing.Any      # int32: index into the widths
+    snr: typing.Any         # float32
+
+
+def single_pulse_device(data, widths, threshold, radius=None, dense=False, max_events=1 << 20, stream=None,
+                        capacity=None):
+    """Single-pulse search of a batch of normalised device series
+    (rt_single_pulse_device; the specification: single_pulse.single_pulse_host,
+    bit for bit): data float32 [N] or [B, N] with unit sample stride (rows may
+    be any distance >= N apart: slices of a wider tensor are read in place),
+    widths ascending int samples, radius the local-maximum radius in samples
+    (default: the largest width).  Returns PulseEvents, and with dense=True
+    (events, best, kbest): float32 and int32 [B, N].
+
+    The events are counted on the device; `capacity` is the room of the first
+    attempt (default 4096, at most max_events).  When more are found the call
+    is repeated once with room for all of them, and ValueError is raised when
+    there are more than max_events.  The count is read back, so the call
+    waits for the stream; rt_single_pulse_device itself does not."""
+    import torch
+    if data.dim() == 1:
+        data = data.unsqueeze(0)
+    if data.dim() != 2 or data.dtype != torch.float32 or data.device.type != "cuda" or data.stride(1) != 1:
+        raise ValueError("data must be float32 [B, N] device rows with unit stride")
+    B, N = data.shape
+    if B > 1 and data.stride(0) < N:
+        raise ValueError("data rows must not overlap")
+    w = np.ascontiguousarray(widths, dtype=np.int32).ravel()
+    if not w.size:
+        raise ValueError("single pulse: no trial widths")
+    radius = int(w.max() if radius is None else radius)
+    if radius < 0:
+        raise ValueError("radius must be >= 0")
+    max_events = int(max_events)
+    if max_events < 0:
+        raise ValueError("max_events must be >= 0")
+    cap = min(max_events, 4096 if capacity is None else int(capacity))
+    if cap < 0:
+        raise ValueError("capacity must be >= 0")
+    ldx = data.stride(0) if B > 1 else max(N, 1)
+    s = stream if stream is not None else torch.cuda.current_stream(data.device)
+    dev = data.device
+    with torch.cuda.device(dev), torch.cuda.stream(s):
+        best = torch.empty((B, N), dtype=torch.float32, device=dev) if dense else None
+        kbest = torch.empty((B, N), dtype=torch.int32, device=dev) if dense else None
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        while True:
+            need = ctypes.c_size_t()
+            _check(_L.rt_single_pulse_workspace_bytes(B, N, w.size, cap, ctypes.byref(need)))
+            ev = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+            workspace = torch.empty(max(need.value, 1), dtype=torch.uint8, device=dev)
+            _check(_L.rt_single_pulse_device(_lib.ptr(data), B, N, ldx, _lib.ptr(w), w.size, float(threshold), radius,
+                                             _lib.ptr(ev) if cap else None, cap, _lib.ptr(count),
+                                             _lib.ptr(best) if dense else None, _lib.ptr(kbest) if dense else None,
+                                             _lib.ptr(workspace), workspace.numel(), _stream_handle(s)))
+            found = int(count.item())
+            if found <= cap:
+                break
+            if found > max_events:
+                raise ValueError(f"single pulse: {found} events at threshold {float(threshold):g} exceed max_events = "
+                                 f"{max_events}; raise the threshold")
+            cap = found
+        ev = ev[:found]
+        events = PulseEvents(ev[:, 0], ev[:, 1], ev[:, 2], ev[:, 3].view(torch.float32))
+    return (events, best, kbest) if dense else events
 
 
 # RT_DEDISP_* sample type codes (include/riptide_amd.h); 'u1', 'u2', 'u4' and
