@@ -18,9 +18,12 @@
 #include <cstring>
 #include <vector>
 
+#include "dedisp_types.hpp"
 #include "riptide_amd.h"
 
 namespace {
+
+using rt::dedisp_packed_bits;
 
 uint64_t g_state = 4321;
 uint32_t draw()
@@ -38,12 +41,6 @@ void expect(bool ok, const char* what)
     }
 }
 
-int packed_bits(int dtype)
-{
-    return dtype == RT_DEDISP_U1 ? 1 : dtype == RT_DEDISP_U2 ? 2 : dtype == RT_DEDISP_U4 ? 4
-           : dtype == RT_DEDISP_U16 ? 16 : 0;
-}
-
 // the value of sample (t, c), by the definitions of riptide_amd.h
 double value(const std::vector<unsigned char>& x, int dtype, size_t row_bytes, size_t t, size_t c)
 {
@@ -55,7 +52,7 @@ double value(const std::vector<unsigned char>& x, int dtype, size_t row_bytes, s
         std::memcpy(&v, row + 4 * c, 4);
         return (double)v;
     }
-    const int nbits = packed_bits(dtype);
+    const int nbits = dedisp_packed_bits(dtype);
     if (nbits == 16) return (double)((unsigned)row[2 * c] | (unsigned)row[2 * c + 1] << 8);
     const size_t bit = c * (size_t)nbits;
     return (double)((row[bit >> 3] >> (bit & 7)) & ((1u << nbits) - 1u));
@@ -76,7 +73,7 @@ std::vector<uint32_t> band_table(size_t nchans)
 
 void run_shape(size_t nchans, int dtype, bool masked, bool zero_dm, bool single_out)
 {
-    const int nbits = packed_bits(dtype);
+    const int nbits = dedisp_packed_bits(dtype);
     if (nbits && nchans * (size_t)nbits % 8) return;   // rows are not whole bytes: the error cases have it
     const double tsamp = 1e-3, kdm = 1.0 / 2.41e-4;
     const double dms_[] = {0.0, 50.0, 12.5};

@@ -1,6 +1,7 @@
 // C ABI, filterbank side: incoherent dedispersion, the zero-DM filter and the
 // channel statistics, with the shape limits of their kernels' 32-bit indices
-// and grids.
+// and grids.  The six dedispersion calls are two cores, the resident-block one
+// and the host-buffer one, each with an optional band table.
 #include "riptide_amd.h"
 
 #include <mutex>
@@ -9,52 +10,37 @@
 #include <vector>
 
 #include "capi_device.hpp"
+#include "dedisp_types.hpp"
 #include "kernels.hpp"
 
 using namespace rt;
 
 namespace {
 
-bool known_dtype(int dtype)
-{
-    return dtype == RT_DEDISP_U8 || dtype == RT_DEDISP_I8 || dtype == RT_DEDISP_F32 || dedisp_packed_bits(dtype);
-}
-
-// float and 16-bit data are summed in float32; everything else as integers
-bool integer_sum(int dtype) { return dtype != RT_DEDISP_F32 && dtype != RT_DEDISP_U16; }
-
-// bytes of a row of the block (rt_dedisp_row_bytes: throws for packed rows
-// that are not whole bytes)
-size_t row_bytes_of(int dtype, size_t nchans)
-{
-    size_t rb = 0;
-    if (rt_dedisp_row_bytes(dtype, nchans, &rb) != RT_OK) throw std::invalid_argument(rt_last_error());
-    return rb;
-}
-
 void dedisp_check_shape(int dtype, size_t nsamp_blk, size_t nchans, size_t ndm, int64_t max_delay)
 {
-    if (!known_dtype(dtype)) throw std::invalid_argument("dedisperse: unknown sample type code");
+    if (!dedisp_known_dtype(dtype)) throw std::invalid_argument("dedisperse: unknown sample type code");
     if (!nchans || !ndm) throw std::invalid_argument("dedisperse: nchans and ndm must be at least 1");
-    if (integer_sum(dtype) && nchans > RT_DEDISP_MAX_CHANS_8BIT)
-        throw std::invalid_argument("dedisperse: too many channels for an exact 8-bit sum (255 * nchans must be "
-                                    "below 2^24)");
+    dedisp_check_chan_cap(dtype, nchans);
     if (nchans > 65535ull * 64) throw std::invalid_argument("dedisperse: too many channels");
     if (ndm > 65535ull * 16) throw std::invalid_argument("dedisperse: too many DMs for one call");
     if (nsamp_blk >= (1ull << 31)) throw std::invalid_argument("dedisperse: a block must be below 2^31 samples");
     // packed rows: whole bytes, and nsamp_blk * row_bytes inside the kernels' 64-bit byte offsets
     // (row_bytes < 2^23 by the channel limit above)
-    if (dedisp_packed_bits(dtype) && row_bytes_of(dtype, nchans) > (~0ull >> 1) / (nsamp_blk ? nsamp_blk : 1))
+    if (dedisp_packed_bits(dtype) && dedisp_row_bytes(dtype, nchans) > (~0ull >> 1) / (nsamp_blk ? nsamp_blk : 1))
         throw std::invalid_argument("dedisperse: the block's bytes overflow a 64-bit offset");
     if (max_delay < 0 || (uint64_t)max_delay >= nsamp_blk)
         throw std::invalid_argument("dedisperse: max_delay must be in [0, nsamp): the block is no longer than the "
                                     "largest delay");
 }
 
-void dedisp_check_flags(uint32_t flags)
-{
-    if (flags & ~RT_DEDISP_ZERO_DM) throw std::invalid_argument("dedisperse: unknown flag bit");
-}
+// The band table of the band forms, in device memory for the resident-block
+// call and in host memory for the host-buffer one; no BandTable (a null
+// pointer to one) is the plain form.
+struct BandTable {
+    const uint32_t* table;
+    size_t nbands;
+};
 
 // the band forms: every band a grid layer, every (DM, band) a row of out
 void dedisp_check_bands(size_t ndm, size_t nbands)
@@ -67,12 +53,83 @@ void dedisp_check_bands(size_t ndm, size_t nbands)
         throw std::invalid_argument("dedisperse: ndm * nbands rows overflow 32 bits");
 }
 
+// rt_dedisperse_device, _device_opt and rt_dedisperse_bands_device (bt->table in device memory)
+int dedisperse_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans, const int32_t* d_delays,
+                      const uint8_t* d_mask, size_t ndm, const BandTable* bt, int64_t max_delay, float* d_out,
+                      size_t out_stride, size_t out_offset, void* d_ws, size_t ws_bytes, void* stream, uint32_t flags)
+{
+    return guarded([&] {
+        dedisp_check_flags(flags);
+        dedisp_check_shape(dtype, nsamp_blk, nchans, ndm, max_delay);
+        if (bt) dedisp_check_bands(ndm, bt->nbands);
+        const size_t nout = nsamp_blk - (size_t)max_delay;
+        if (out_offset > out_stride || nout > out_stride - out_offset)
+            throw std::invalid_argument("dedisperse: out_stride is shorter than out_offset plus the block's outputs");
+        if (!d_block || !d_delays || !d_out || !d_ws) throw std::invalid_argument("dedisperse: null device pointer");
+        if (bt && !bt->table) throw std::invalid_argument("dedisperse: d_bands is NULL");
+        if ((uintptr_t)d_ws % 16 || (bt && (uintptr_t)bt->table % 4) ||
+            (dtype == RT_DEDISP_F32 && (uintptr_t)d_block % 4))
+            throw std::invalid_argument("dedisperse: misaligned device pointer");
+        if (ws_bytes < dedisp_workspace_bytes(dtype, nsamp_blk, nchans, flags))
+            throw std::invalid_argument("workspace too small");
+        ck(launch_dedisperse(d_block, dtype, (uint32_t)nsamp_blk, (uint32_t)nchans, d_delays, d_mask, (uint32_t)ndm,
+                             (uint32_t)max_delay, d_out + out_offset, out_stride, d_ws, flags, (hipStream_t)stream,
+                             bt ? bt->table : nullptr, bt ? (uint32_t)bt->nbands : 0u),
+           "dedisperse");
+        return RT_OK;
+    });
+}
+
+// rt_dedisperse, _opt and rt_dedisperse_bands (bt->table in host memory): the
+// delays narrowed to int32, everything uploaded into the context's buffers
+// (slot 5: the band table), the kernels, the rows copied out
+int dedisperse_buffers(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
+                       const uint8_t* mask, size_t ndm, const BandTable* bt, int64_t max_delay, float* out,
+                       uint32_t flags)
+{
+    return guarded([&] {
+        dedisp_check_flags(flags);
+        dedisp_check_shape(dtype, nsamp, nchans, ndm, max_delay);
+        if (bt) dedisp_check_bands(ndm, bt->nbands);
+        if (!x || !delays || !out || (bt && !bt->table)) throw std::invalid_argument("dedisperse: null buffer");
+        if (bt) dedisp_check_band_table(bt->table, bt->nbands, nchans);
+        std::vector<int32_t> del(ndm * nchans);
+        for (size_t i = 0; i < del.size(); ++i) {
+            if (delays[i] < 0 || delays[i] > max_delay)
+                throw std::invalid_argument("dedisperse: a delay is outside [0, max_delay]");
+            del[i] = (int32_t)delays[i];
+        }
+        const size_t nout = nsamp - (size_t)max_delay;
+        const size_t nrows = ndm * (bt ? bt->nbands : 1);
+        const size_t in_bytes = nsamp * dedisp_row_bytes(dtype, nchans);
+        const size_t ws_bytes = (size_t)dedisp_workspace_bytes(dtype, nsamp, nchans, flags);
+        std::lock_guard<std::mutex> lk(g_mu);
+        Context& c = context();
+        void* dx = c.buf[0].get(in_bytes);
+        float* dz = dev<float>(c, 1, nrows * nout);
+        void* dw = c.buf[2].get(ws_bytes);
+        int32_t* dd = dev<int32_t>(c, 3, del.size());
+        uint8_t* dm = mask ? dev<uint8_t>(c, 4, nchans) : nullptr;
+        uint32_t* db = bt ? dev<uint32_t>(c, 5, 2 * bt->nbands) : nullptr;
+        h2d(dx, x, in_bytes, c.stream);
+        h2d(dd, del.data(), del.size() * 4, c.stream);
+        if (mask) h2d(dm, mask, nchans, c.stream);
+        if (bt) h2d(db, bt->table, 2 * bt->nbands * 4, c.stream);
+        ck(launch_dedisperse(dx, dtype, (uint32_t)nsamp, (uint32_t)nchans, dd, dm, (uint32_t)ndm,
+                             (uint32_t)max_delay, dz, nout, dw, flags, c.stream, db, bt ? (uint32_t)bt->nbands : 0u),
+           "dedisperse");
+        d2h(out, dz, nrows * nout * 4, c.stream);
+        sync(c.stream);
+        return RT_OK;
+    });
+}
+
 // the statistics have no exactness limit on the channel count of 8-bit data
 void chanstats_check_shape(int dtype, size_t nsamp_blk, size_t nchans)
 {
     dedisp_check_shape(RT_DEDISP_F32, nsamp_blk, nchans, 1, 0);
-    if (!known_dtype(dtype)) throw std::invalid_argument("channel_stats: unknown sample type code");
-    if (dedisp_packed_bits(dtype)) row_bytes_of(dtype, nchans);
+    if (!dedisp_known_dtype(dtype)) throw std::invalid_argument("channel_stats: unknown sample type code");
+    if (dedisp_packed_bits(dtype)) dedisp_row_bytes(dtype, nchans);
 }
 
 }  // namespace
@@ -99,8 +156,8 @@ int rt_dedisperse_device(const void* d_block, int dtype, size_t nsamp_blk, size_
                          const uint8_t* d_mask, size_t ndm, int64_t max_delay, float* d_out, size_t out_stride,
                          size_t out_offset, void* d_ws, size_t ws_bytes, void* stream)
 {
-    return rt_dedisperse_device_opt(d_block, dtype, nsamp_blk, nchans, d_delays, d_mask, ndm, max_delay, d_out,
-                                    out_stride, out_offset, d_ws, ws_bytes, stream, 0u);
+    return dedisperse_device(d_block, dtype, nsamp_blk, nchans, d_delays, d_mask, ndm, nullptr, max_delay, d_out,
+                             out_stride, out_offset, d_ws, ws_bytes, stream, 0u);
 }
 
 int rt_dedisperse_device_opt(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans,
@@ -108,63 +165,8 @@ int rt_dedisperse_device_opt(const void* d_block, int dtype, size_t nsamp_blk, s
                              float* d_out, size_t out_stride, size_t out_offset, void* d_ws, size_t ws_bytes,
                              void* stream, uint32_t flags)
 {
-    return guarded([&] {
-        dedisp_check_flags(flags);
-        dedisp_check_shape(dtype, nsamp_blk, nchans, ndm, max_delay);
-        const size_t nout = nsamp_blk - (size_t)max_delay;
-        if (out_offset > out_stride || nout > out_stride - out_offset)
-            throw std::invalid_argument("dedisperse: out_stride is shorter than out_offset plus the block's outputs");
-        if (!d_block || !d_delays || !d_out || !d_ws) throw std::invalid_argument("dedisperse: null device pointer");
-        if ((uintptr_t)d_ws % 16 || (dtype == RT_DEDISP_F32 && (uintptr_t)d_block % 4))
-            throw std::invalid_argument("dedisperse: misaligned device pointer");
-        if (ws_bytes < dedisp_workspace_bytes(dtype, nsamp_blk, nchans, flags))
-            throw std::invalid_argument("workspace too small");
-        ck(launch_dedisperse(d_block, dtype, (uint32_t)nsamp_blk, (uint32_t)nchans, d_delays, d_mask, (uint32_t)ndm,
-                             (uint32_t)max_delay, d_out + out_offset, out_stride, d_ws, flags, (hipStream_t)stream),
-           "dedisperse");
-        return RT_OK;
-    });
-}
-
-int rt_dedisperse(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays, const uint8_t* mask,
-                  size_t ndm, int64_t max_delay, float* out)
-{
-    return rt_dedisperse_opt(x, dtype, nsamp, nchans, delays, mask, ndm, max_delay, out, 0u);
-}
-
-int rt_dedisperse_opt(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
-                      const uint8_t* mask, size_t ndm, int64_t max_delay, float* out, uint32_t flags)
-{
-    return guarded([&] {
-        dedisp_check_flags(flags);
-        dedisp_check_shape(dtype, nsamp, nchans, ndm, max_delay);
-        if (!x || !delays || !out) throw std::invalid_argument("dedisperse: null buffer");
-        std::vector<int32_t> del(ndm * nchans);
-        for (size_t i = 0; i < del.size(); ++i) {
-            if (delays[i] < 0 || delays[i] > max_delay)
-                throw std::invalid_argument("dedisperse: a delay is outside [0, max_delay]");
-            del[i] = (int32_t)delays[i];
-        }
-        const size_t nout = nsamp - (size_t)max_delay;
-        const size_t in_bytes = nsamp * row_bytes_of(dtype, nchans);
-        const size_t ws_bytes = (size_t)dedisp_workspace_bytes(dtype, nsamp, nchans, flags);
-        std::lock_guard<std::mutex> lk(g_mu);
-        Context& c = context();
-        void* dx = c.buf[0].get(in_bytes);
-        float* dz = dev<float>(c, 1, ndm * nout);
-        void* dw = c.buf[2].get(ws_bytes);
-        int32_t* dd = dev<int32_t>(c, 3, del.size());
-        uint8_t* dm = mask ? dev<uint8_t>(c, 4, nchans) : nullptr;
-        h2d(dx, x, in_bytes, c.stream);
-        h2d(dd, del.data(), del.size() * 4, c.stream);
-        if (mask) h2d(dm, mask, nchans, c.stream);
-        ck(launch_dedisperse(dx, dtype, (uint32_t)nsamp, (uint32_t)nchans, dd, dm, (uint32_t)ndm,
-                             (uint32_t)max_delay, dz, nout, dw, flags, c.stream),
-           "dedisperse");
-        d2h(out, dz, ndm * nout * 4, c.stream);
-        sync(c.stream);
-        return RT_OK;
-    });
+    return dedisperse_device(d_block, dtype, nsamp_blk, nchans, d_delays, d_mask, ndm, nullptr, max_delay, d_out,
+                             out_stride, out_offset, d_ws, ws_bytes, stream, flags);
 }
 
 int rt_dedisperse_bands_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans,
@@ -172,69 +174,29 @@ int rt_dedisperse_bands_device(const void* d_block, int dtype, size_t nsamp_blk,
                                size_t nbands, int64_t max_delay, float* d_out, size_t out_stride, size_t out_offset,
                                void* d_ws, size_t ws_bytes, void* stream, uint32_t flags)
 {
-    return guarded([&] {
-        dedisp_check_flags(flags);
-        dedisp_check_shape(dtype, nsamp_blk, nchans, ndm, max_delay);
-        dedisp_check_bands(ndm, nbands);
-        const size_t nout = nsamp_blk - (size_t)max_delay;
-        if (out_offset > out_stride || nout > out_stride - out_offset)
-            throw std::invalid_argument("dedisperse: out_stride is shorter than out_offset plus the block's outputs");
-        if (!d_block || !d_delays || !d_out || !d_ws) throw std::invalid_argument("dedisperse: null device pointer");
-        if (!d_bands) throw std::invalid_argument("dedisperse: d_bands is NULL");
-        if ((uintptr_t)d_ws % 16 || (uintptr_t)d_bands % 4 || (dtype == RT_DEDISP_F32 && (uintptr_t)d_block % 4))
-            throw std::invalid_argument("dedisperse: misaligned device pointer");
-        if (ws_bytes < dedisp_workspace_bytes(dtype, nsamp_blk, nchans, flags))
-            throw std::invalid_argument("workspace too small");
-        ck(launch_dedisperse(d_block, dtype, (uint32_t)nsamp_blk, (uint32_t)nchans, d_delays, d_mask, (uint32_t)ndm,
-                             (uint32_t)max_delay, d_out + out_offset, out_stride, d_ws, flags, (hipStream_t)stream,
-                             d_bands, (uint32_t)nbands),
-           "dedisperse");
-        return RT_OK;
-    });
+    const BandTable bt{d_bands, nbands};
+    return dedisperse_device(d_block, dtype, nsamp_blk, nchans, d_delays, d_mask, ndm, &bt, max_delay, d_out,
+                             out_stride, out_offset, d_ws, ws_bytes, stream, flags);
+}
+
+int rt_dedisperse(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays, const uint8_t* mask,
+                  size_t ndm, int64_t max_delay, float* out)
+{
+    return dedisperse_buffers(x, dtype, nsamp, nchans, delays, mask, ndm, nullptr, max_delay, out, 0u);
+}
+
+int rt_dedisperse_opt(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
+                      const uint8_t* mask, size_t ndm, int64_t max_delay, float* out, uint32_t flags)
+{
+    return dedisperse_buffers(x, dtype, nsamp, nchans, delays, mask, ndm, nullptr, max_delay, out, flags);
 }
 
 int rt_dedisperse_bands(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
                         const uint8_t* mask, size_t ndm, const uint32_t* bands, size_t nbands, int64_t max_delay,
                         float* out, uint32_t flags)
 {
-    return guarded([&] {
-        dedisp_check_flags(flags);
-        dedisp_check_shape(dtype, nsamp, nchans, ndm, max_delay);
-        dedisp_check_bands(ndm, nbands);
-        if (!x || !delays || !out || !bands) throw std::invalid_argument("dedisperse: null buffer");
-        for (size_t b = 0; b < nbands; ++b)
-            if (bands[2 * b] > bands[2 * b + 1] || bands[2 * b + 1] > nchans)
-                throw std::invalid_argument("dedisperse: band " + std::to_string(b) + " [" +
-                                            std::to_string(bands[2 * b]) + ", " + std::to_string(bands[2 * b + 1]) +
-                                            ") is not a channel range lo <= hi <= " + std::to_string(nchans));
-        std::vector<int32_t> del(ndm * nchans);
-        for (size_t i = 0; i < del.size(); ++i) {
-            if (delays[i] < 0 || delays[i] > max_delay)
-                throw std::invalid_argument("dedisperse: a delay is outside [0, max_delay]");
-            del[i] = (int32_t)delays[i];
-        }
-        const size_t nout = nsamp - (size_t)max_delay;
-        const size_t in_bytes = nsamp * row_bytes_of(dtype, nchans);
-        const size_t ws_bytes = (size_t)dedisp_workspace_bytes(dtype, nsamp, nchans, flags);
-        std::lock_guard<std::mutex> lk(g_mu);
-        Context& c = context();
-        void* dx = c.buf[0].get(in_bytes);
-        float* dz = dev<float>(c, 1, ndm * nbands * nout);
-        void* dw = c.buf[2].get(ws_bytes);
-        int32_t* dd = dev<int32_t>(c, 3, del.size());
-        uint8_t* dm = mask ? dev<uint8_t>(c, 4, nchans) : nullptr;
-        uint32_t* db = dev<uint32_t>(c, 5, 2 * nbands);
-        h2d(dx, x, in_bytes, c.stream);
-        h2d(dd, del.data(), del.size() * 4, c.stream);
-        if (mask) h2d(dm, mask, nchans, c.stream);
-        h2d(db, bands, 2 * nbands * 4, c.stream);
-        ck(launch_dedisperse(dx, dtype, (uint32_t)nsamp, (uint32_t)nchans, dd, dm, (uint32_t)ndm,
-                             (uint32_t)max_delay, dz, nout, dw, flags, c.stream, db, (uint32_t)nbands),
-           "dedisperse");
-        d2h(out, dz, ndm * nbands * nout * 4, c.stream);
-        sync(c.stream);
-        return RT_OK;
-    });
+    const BandTable bt{bands, nbands};
+    return dedisperse_buffers(x, dtype, nsamp, nchans, delays, mask, ndm, &bt, max_delay, out, flags);
 }
 
 int rt_zero_dm_mean_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans, const uint8_t* d_mask,

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "capi_common.hpp"
+#include "dedisp_types.hpp"
 
 using namespace rt;
 
@@ -27,10 +28,12 @@ struct Bands {
     size_t hi(size_t b, size_t nchans) const { return bands ? bands[2 * b + 1] : nchans; }
 };
 
-template <class T, class Acc>
+// Acc: int32_t for 8-bit samples (an exact sum), float for float and 16-bit ones
+template <class T>
 void dedisperse_rows(const T* x, size_t nchans, const int64_t* delays, const uint8_t* mask, size_t ndm, size_t nout,
                      float* out, const Bands& bt)
 {
+    using Acc = typename std::conditional<sizeof(T) == 1, int32_t, float>::type;
     for (size_t d = 0; d < ndm; ++d) {
         const int64_t* del = delays + d * nchans;
         for (size_t b = 0; b < bt.nbands; ++b) {
@@ -47,10 +50,11 @@ void dedisperse_rows(const T* x, size_t nchans, const int64_t* delays, const uin
 }
 
 // The zero-DM mean series (riptide_amd.h, RT_DEDISP_ZERO_DM): Acc = int64_t
-// for 8-bit samples (an exact sum), double for float samples.
-template <class T, class Acc>
+// for integer samples (an exact sum), double for float samples.
+template <class T>
 void zero_dm_mean(const T* x, size_t nsamp, size_t nchans, const uint8_t* mask, float* m)
 {
+    using Acc = typename std::conditional<std::is_integral<T>::value, int64_t, double>::type;
     size_t nu = 0;
     for (size_t c = 0; c < nchans; ++c) nu += !mask || !mask[c];
     for (size_t t = 0; t < nsamp; ++t) {
@@ -68,8 +72,7 @@ void dedisperse_rows_zero_dm(const T* x, size_t nsamp, size_t nchans, const int6
                              size_t ndm, size_t nout, float* out, const Bands& bt)
 {
     std::vector<float> m(nsamp);
-    zero_dm_mean<T, typename std::conditional<std::is_integral<T>::value, int64_t, double>::type>(x, nsamp, nchans,
-                                                                                                  mask, m.data());
+    zero_dm_mean(x, nsamp, nchans, mask, m.data());
     for (size_t d = 0; d < ndm; ++d) {
         const int64_t* del = delays + d * nchans;
         for (size_t b = 0; b < bt.nbands; ++b) {
@@ -99,22 +102,7 @@ void channel_stats(const T* x, size_t nsamp, size_t nchans, double* acc)
         }
 }
 
-// ---- packed sample types (riptide_amd.h, RT_DEDISP_U1 .. RT_DEDISP_U16)
-// bits of a packed code, 0 for any other
-int packed_bits(int dtype)
-{
-    return dtype == RT_DEDISP_U1 ? 1 : dtype == RT_DEDISP_U2 ? 2 : dtype == RT_DEDISP_U4 ? 4
-           : dtype == RT_DEDISP_U16 ? 16 : 0;
-}
-
-bool known_dtype(int dtype)
-{
-    return dtype == RT_DEDISP_U8 || dtype == RT_DEDISP_I8 || dtype == RT_DEDISP_F32 || packed_bits(dtype);
-}
-
-// summed as integers, exact in float32 up to RT_DEDISP_MAX_CHANS_8BIT channels
-bool integer_sum(int dtype) { return dtype != RT_DEDISP_F32 && dtype != RT_DEDISP_U16; }
-
+// ---- the sample types (dedisp_types.hpp; riptide_amd.h, RT_DEDISP_U8 .. RT_DEDISP_U16)
 // The one unpack helper: channel c of a packed row, as riptide_amd.h defines it.
 inline uint32_t unpack_sample(const uint8_t* row, int nbits, size_t c)
 {
@@ -123,19 +111,12 @@ inline uint32_t unpack_sample(const uint8_t* row, int nbits, size_t c)
     return (uint32_t)(row[bit >> 3] >> (bit & 7)) & ((1u << nbits) - 1u);
 }
 
-size_t packed_row_bytes(int nbits, size_t nchans)
-{
-    if (nchans > SIZE_MAX / 16 || nchans * (size_t)nbits % 8)
-        throw std::invalid_argument("dedisperse: " + std::to_string(nchans) + " channels of " + std::to_string(nbits) +
-                                    "-bit data: rows are not a whole number of bytes");
-    return nchans * (size_t)nbits / 8;
-}
-
 // the block as [nsamp, nchans] values: U = uint8_t for 1/2/4 bit, uint16_t for 16 bit
 template <class U>
-std::vector<U> unpack_block(const void* x, int nbits, size_t nsamp, size_t nchans)
+std::vector<U> unpack_block(const void* x, int dtype, size_t nsamp, size_t nchans)
 {
-    const size_t rb = packed_row_bytes(nbits, nchans);
+    const int nbits = dedisp_packed_bits(dtype);
+    const size_t rb = dedisp_row_bytes(dtype, nchans);
     std::vector<U> v(nsamp * nchans);
     for (size_t t = 0; t < nsamp; ++t) {
         const uint8_t* row = (const uint8_t*)x + t * rb;
@@ -144,13 +125,17 @@ std::vector<U> unpack_block(const void* x, int nbits, size_t nsamp, size_t nchan
     return v;
 }
 
-void check_dtype(int dtype, size_t nchans)
+// f(the block as a typed [nsamp, nchans] pointer), the one dispatch on the
+// sample type: a packed block is unpacked once, 1/2/4 bit to the uint8_t and
+// 16 bit to the uint16_t values, and then summed as those
+template <class F>
+void with_samples(const void* x, int dtype, size_t nsamp, size_t nchans, F f)
 {
-    if (!known_dtype(dtype)) throw std::invalid_argument("dedisperse: unknown sample type code");
-    if (!nchans) throw std::invalid_argument("dedisperse: nchans and ndm must be at least 1");
-    if (integer_sum(dtype) && nchans > RT_DEDISP_MAX_CHANS_8BIT)
-        throw std::invalid_argument("dedisperse: too many channels for an exact 8-bit sum");
-    if (packed_bits(dtype)) packed_row_bytes(packed_bits(dtype), nchans);
+    if (dedisp_packed_bits(dtype) == 16) f(unpack_block<uint16_t>(x, dtype, nsamp, nchans).data());
+    else if (dedisp_packed_bits(dtype)) f(unpack_block<uint8_t>(x, dtype, nsamp, nchans).data());
+    else if (dtype == RT_DEDISP_U8) f((const uint8_t*)x);
+    else if (dtype == RT_DEDISP_I8) f((const int8_t*)x);
+    else f((const float*)x);
 }
 
 // The specification of the plain and the band forms: the checks every form
@@ -159,55 +144,23 @@ void dedisperse_host(const void* x, int dtype, size_t nsamp, size_t nchans, cons
                      const uint8_t* mask, size_t ndm, int64_t max_delay, size_t nout, float* out, uint32_t flags,
                      const Bands& bt)
 {
-    if (flags & ~RT_DEDISP_ZERO_DM) throw std::invalid_argument("dedisperse: unknown flag bit");
+    dedisp_check_flags(flags);
     if (!nchans || !ndm) throw std::invalid_argument("dedisperse: nchans and ndm must be at least 1");
-    if (!known_dtype(dtype)) throw std::invalid_argument("dedisperse: unknown sample type code");
-    const int nbits = packed_bits(dtype);
-    if (nbits) packed_row_bytes(nbits, nchans);
+    dedisp_check_dtype(dtype, nchans, false);   // the channel cap comes after the lengths, as it always has
     if (max_delay < 0 || max_delay >= 2147483648ll)
         throw std::invalid_argument("dedisperse: max_delay is outside [0, 2^31)");
     if (nout > nsamp || (uint64_t)max_delay > nsamp - nout)
         throw std::invalid_argument("dedisperse: nout + max_delay exceeds the " + std::to_string(nsamp) +
                                     " samples of the input");
-    if (integer_sum(dtype) && nchans > RT_DEDISP_MAX_CHANS_8BIT)
-        throw std::invalid_argument("dedisperse: too many channels for an exact 8-bit sum");
+    dedisp_check_chan_cap(dtype, nchans);
     for (size_t i = 0; i < ndm * nchans; ++i)
         if (delays[i] < 0 || delays[i] > max_delay)
             throw std::invalid_argument("dedisperse: a delay is outside [0, max_delay]");
     if (!nout || !bt.nbands) return;
-    if (nbits) {
-        // the values of the packed block, then the same sums: 1/2/4 bit as
-        // 8-bit data, 16 bit converted exactly and added in float32
-        if (nbits == 16) {
-            const std::vector<uint16_t> v = unpack_block<uint16_t>(x, nbits, nsamp, nchans);
-            if (flags & RT_DEDISP_ZERO_DM)
-                dedisperse_rows_zero_dm(v.data(), nsamp, nchans, delays, mask, ndm, nout, out, bt);
-            else
-                dedisperse_rows<uint16_t, float>(v.data(), nchans, delays, mask, ndm, nout, out, bt);
-        } else {
-            const std::vector<uint8_t> v = unpack_block<uint8_t>(x, nbits, nsamp, nchans);
-            if (flags & RT_DEDISP_ZERO_DM)
-                dedisperse_rows_zero_dm(v.data(), nsamp, nchans, delays, mask, ndm, nout, out, bt);
-            else
-                dedisperse_rows<uint8_t, int32_t>(v.data(), nchans, delays, mask, ndm, nout, out, bt);
-        }
-        return;
-    }
-    if (flags & RT_DEDISP_ZERO_DM) {
-        if (dtype == RT_DEDISP_U8)
-            dedisperse_rows_zero_dm((const uint8_t*)x, nsamp, nchans, delays, mask, ndm, nout, out, bt);
-        else if (dtype == RT_DEDISP_I8)
-            dedisperse_rows_zero_dm((const int8_t*)x, nsamp, nchans, delays, mask, ndm, nout, out, bt);
-        else
-            dedisperse_rows_zero_dm((const float*)x, nsamp, nchans, delays, mask, ndm, nout, out, bt);
-        return;
-    }
-    if (dtype == RT_DEDISP_U8)
-        dedisperse_rows<uint8_t, int32_t>((const uint8_t*)x, nchans, delays, mask, ndm, nout, out, bt);
-    else if (dtype == RT_DEDISP_I8)
-        dedisperse_rows<int8_t, int32_t>((const int8_t*)x, nchans, delays, mask, ndm, nout, out, bt);
-    else
-        dedisperse_rows<float, float>((const float*)x, nchans, delays, mask, ndm, nout, out, bt);
+    with_samples(x, dtype, nsamp, nchans, [&](const auto* v) {
+        if (flags & RT_DEDISP_ZERO_DM) dedisperse_rows_zero_dm(v, nsamp, nchans, delays, mask, ndm, nout, out, bt);
+        else dedisperse_rows(v, nchans, delays, mask, ndm, nout, out, bt);
+    });
 }
 
 }  // namespace
@@ -218,15 +171,8 @@ int rt_dedisp_row_bytes(int dtype, size_t nchans, size_t* bytes)
 {
     return guarded([&] {
         if (!bytes) throw std::invalid_argument("dedisperse: bytes is NULL");
-        if (!known_dtype(dtype)) throw std::invalid_argument("dedisperse: unknown sample type code");
-        if (!nchans) throw std::invalid_argument("dedisperse: nchans and ndm must be at least 1");
-        if (packed_bits(dtype)) {
-            *bytes = packed_row_bytes(packed_bits(dtype), nchans);
-        } else {
-            const size_t esize = dtype == RT_DEDISP_F32 ? 4 : 1;
-            if (nchans > SIZE_MAX / esize) throw std::invalid_argument("dedisperse: too many channels");
-            *bytes = nchans * esize;
-        }
+        dedisp_check_dtype(dtype, nchans, false);
+        *bytes = dedisp_row_bytes(dtype, nchans);
         return RT_OK;
     });
 }
@@ -288,11 +234,7 @@ int rt_dedisperse_bands_host(const void* x, int dtype, size_t nsamp, size_t ncha
     return guarded([&] {
         if (!nchans || !ndm) throw std::invalid_argument("dedisperse: nchans and ndm must be at least 1");
         if (nbands && !bands) throw std::invalid_argument("dedisperse: bands is NULL");
-        for (size_t b = 0; b < nbands; ++b)
-            if (bands[2 * b] > bands[2 * b + 1] || bands[2 * b + 1] > nchans)
-                throw std::invalid_argument("dedisperse: band " + std::to_string(b) + " [" +
-                                            std::to_string(bands[2 * b]) + ", " + std::to_string(bands[2 * b + 1]) +
-                                            ") is not a channel range lo <= hi <= " + std::to_string(nchans));
+        dedisp_check_band_table(bands, nbands, nchans);
         dedisperse_host(x, dtype, nsamp, nchans, delays, mask, ndm, max_delay, nout, out, flags, Bands{bands, nbands});
         return RT_OK;
     });
@@ -301,20 +243,10 @@ int rt_dedisperse_bands_host(const void* x, int dtype, size_t nsamp, size_t ncha
 int rt_zero_dm_mean_host(const void* x, int dtype, size_t nsamp, size_t nchans, const uint8_t* mask, float* m)
 {
     return guarded([&] {
-        check_dtype(dtype, nchans);
+        dedisp_check_dtype(dtype, nchans, true);
         if (!nsamp) return RT_OK;
         if (!x || !m) throw std::invalid_argument("zero_dm_mean: null buffer");
-        if (packed_bits(dtype) == 16)
-            zero_dm_mean<uint16_t, int64_t>(unpack_block<uint16_t>(x, 16, nsamp, nchans).data(), nsamp, nchans, mask, m);
-        else if (packed_bits(dtype))
-            zero_dm_mean<uint8_t, int64_t>(unpack_block<uint8_t>(x, packed_bits(dtype), nsamp, nchans).data(), nsamp,
-                                           nchans, mask, m);
-        else if (dtype == RT_DEDISP_U8)
-            zero_dm_mean<uint8_t, int64_t>((const uint8_t*)x, nsamp, nchans, mask, m);
-        else if (dtype == RT_DEDISP_I8)
-            zero_dm_mean<int8_t, int64_t>((const int8_t*)x, nsamp, nchans, mask, m);
-        else
-            zero_dm_mean<float, double>((const float*)x, nsamp, nchans, mask, m);
+        with_samples(x, dtype, nsamp, nchans, [&](const auto* v) { zero_dm_mean(v, nsamp, nchans, mask, m); });
         return RT_OK;
     });
 }
@@ -322,22 +254,11 @@ int rt_zero_dm_mean_host(const void* x, int dtype, size_t nsamp, size_t nchans, 
 int rt_channel_stats_host(const void* x, int dtype, size_t nsamp, size_t nchans, double* acc)
 {
     return guarded([&] {
-        if (!known_dtype(dtype)) throw std::invalid_argument("channel_stats: unknown sample type code");
-        if (!nchans) throw std::invalid_argument("channel_stats: nchans must be at least 1");
-        if (packed_bits(dtype)) packed_row_bytes(packed_bits(dtype), nchans);
+        dedisp_check_dtype(dtype, nchans, false, "channel_stats");   // the statistics have no channel cap
         if (!acc) throw std::invalid_argument("channel_stats: null buffer");
         if (!nsamp) return RT_OK;
         if (!x) throw std::invalid_argument("channel_stats: null buffer");
-        if (packed_bits(dtype) == 16)
-            channel_stats(unpack_block<uint16_t>(x, 16, nsamp, nchans).data(), nsamp, nchans, acc);
-        else if (packed_bits(dtype))
-            channel_stats(unpack_block<uint8_t>(x, packed_bits(dtype), nsamp, nchans).data(), nsamp, nchans, acc);
-        else if (dtype == RT_DEDISP_U8)
-            channel_stats((const uint8_t*)x, nsamp, nchans, acc);
-        else if (dtype == RT_DEDISP_I8)
-            channel_stats((const int8_t*)x, nsamp, nchans, acc);
-        else
-            channel_stats((const float*)x, nsamp, nchans, acc);
+        with_samples(x, dtype, nsamp, nchans, [&](const auto* v) { channel_stats(v, nsamp, nchans, acc); });
         return RT_OK;
     });
 }

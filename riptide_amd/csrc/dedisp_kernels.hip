@@ -39,9 +39,15 @@
 // Exactness: 8-bit sums are integers (16-bit packed partial sums of at most
 // 16 channels, then int32), converted once; float sums are float32 additions
 // in channel order.
+//
+// The launchers at the end choose by sample type in one place, dd_dispatch:
+// launch_zero_dm_mean, launch_channel_stats and the zero-DM transpose are one
+// call of it each.  launch_dedisperse fills the workspace with 8-bit or
+// float32 rows, then makes the one launch_sum call of those rows.
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
+#include "dedisp_types.hpp"
 #include "kernels.hpp"
 
 namespace rt {
@@ -520,29 +526,34 @@ void launch_sum(dim3 grid, hipStream_t s, const T* ws, uint64_t pitch, uint32_t 
     }
 }
 
-}  // namespace
-
-// f(tag) with the DdBits tag of a packed sample type code
+// f(tag), tag a value of the T that kernels reading rows of this sample type
+// code are instantiated for: the one dispatch on the sample type
 template <class F>
-void dd_packed(int dtype, F f)
+void dd_dispatch(int dtype, F f)
 {
-    switch (dedisp_packed_bits(dtype)) {
-    case 1: f(DdBits<1>{}); break;
-    case 2: f(DdBits<2>{}); break;
-    case 4: f(DdBits<4>{}); break;
-    default: f(DdBits<16>{}); break;
+    switch (dtype) {
+    case RT_DEDISP_U1: f(DdBits<1>{}); break;
+    case RT_DEDISP_U2: f(DdBits<2>{}); break;
+    case RT_DEDISP_U4: f(DdBits<4>{}); break;
+    case RT_DEDISP_U16: f(DdBits<16>{}); break;
+    case RT_DEDISP_U8: f(uint8_t{}); break;
+    case RT_DEDISP_I8: f(int8_t{}); break;
+    default: f(float{}); break;
     }
 }
 
+}  // namespace
+
 uint64_t dedisp_pitch_bytes(int dtype, uint64_t nsamp_blk)
 {
-    const uint64_t esize = dtype == 2 || dedisp_packed_bits(dtype) == 16 ? 4 : 1;
+    const uint64_t esize = dtype == RT_DEDISP_F32 || dtype == RT_DEDISP_U16 ? 4 : 1;
     return (nsamp_blk * esize + 15) / 16 * 16;
 }
 
 uint64_t dedisp_workspace_bytes(int dtype, uint64_t nsamp_blk, uint64_t nchans, uint32_t flags)
 {
-    if (flags & kDdZeroDm) return dedisp_pitch_bytes(2, nsamp_blk) * (nchans + 1);   // float rows, then m
+    if (flags & RT_DEDISP_ZERO_DM)   // float rows, then m
+        return dedisp_pitch_bytes(RT_DEDISP_F32, nsamp_blk) * (nchans + 1);
     return dedisp_pitch_bytes(dtype, nsamp_blk) * nchans;
 }
 
@@ -550,21 +561,11 @@ hipError_t launch_zero_dm_mean(const void* block, int dtype, uint32_t nsamp_blk,
                                const uint8_t* d_mask, float* m, hipStream_t s)
 {
     const dim3 grid((nsamp_blk + kRmRowsPerWg - 1) / kRmRowsPerWg);
-    if (dedisp_packed_bits(dtype))
-        dd_packed(dtype, [&](auto tag) {
-            using T = decltype(tag);
-            hipLaunchKernelGGL(dedisp_rowmean_kernel<T>, grid, dim3(kDdThreads), 0, s, (const T*)block, nsamp_blk,
-                               nchans, d_mask, m);
-        });
-    else if (dtype == 0)
-        hipLaunchKernelGGL(dedisp_rowmean_kernel<uint8_t>, grid, dim3(kDdThreads), 0, s, (const uint8_t*)block,
-                           nsamp_blk, nchans, d_mask, m);
-    else if (dtype == 1)
-        hipLaunchKernelGGL(dedisp_rowmean_kernel<int8_t>, grid, dim3(kDdThreads), 0, s, (const int8_t*)block,
-                           nsamp_blk, nchans, d_mask, m);
-    else
-        hipLaunchKernelGGL(dedisp_rowmean_kernel<float>, grid, dim3(kDdThreads), 0, s, (const float*)block,
-                           nsamp_blk, nchans, d_mask, m);
+    dd_dispatch(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(dedisp_rowmean_kernel<T>, grid, dim3(kDdThreads), 0, s, (const T*)block, nsamp_blk, nchans,
+                           d_mask, m);
+    });
     return hipGetLastError();
 }
 
@@ -579,26 +580,20 @@ hipError_t launch_channel_stats(const void* block, int dtype, uint32_t nsamp_blk
     const uint32_t nchunks = (nsamp_blk + kCsChunk - 1) / kCsChunk;
     const dim3 grid(nchunks, (nchans + 63) / 64);
     double* part = (double*)ws;
-    if (dedisp_packed_bits(dtype))
-        dd_packed(dtype, [&](auto tag) {
-            using T = decltype(tag);
-            hipLaunchKernelGGL(dedisp_chanstats_kernel<T>, grid, dim3(kDdThreads), 0, s, (const T*)block, nsamp_blk,
-                               nchans, part);
-        });
-    else if (dtype == 0)
-        hipLaunchKernelGGL(dedisp_chanstats_kernel<uint8_t>, grid, dim3(kDdThreads), 0, s, (const uint8_t*)block,
-                           nsamp_blk, nchans, part);
-    else if (dtype == 1)
-        hipLaunchKernelGGL(dedisp_chanstats_kernel<int8_t>, grid, dim3(kDdThreads), 0, s, (const int8_t*)block,
-                           nsamp_blk, nchans, part);
-    else
-        hipLaunchKernelGGL(dedisp_chanstats_kernel<float>, grid, dim3(kDdThreads), 0, s, (const float*)block,
-                           nsamp_blk, nchans, part);
+    dd_dispatch(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(dedisp_chanstats_kernel<T>, grid, dim3(kDdThreads), 0, s, (const T*)block, nsamp_blk,
+                           nchans, part);
+    });
     hipLaunchKernelGGL(dedisp_chanstats_fold_kernel, dim3((2 * nchans + kDdThreads - 1) / kDdThreads),
                        dim3(kDdThreads), 0, s, (const double*)part, nchunks, nchans, acc);
     return hipGetLastError();
 }
 
+// Two steps.  The block goes to channel-major rows in the workspace: float32
+// rows for float and 16-bit data and for every type under the zero-DM filter
+// (x - m, m behind the rows), 8-bit rows otherwise (signed samples biased by
+// 128, 1/2/4-bit samples unpacked).  Then one sum over whichever rows they are.
 hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
                              const int32_t* d_delays, const uint8_t* d_mask, uint32_t ndm, uint32_t max_delay,
                              float* out, uint64_t out_stride, void* ws, uint32_t flags, hipStream_t s,
@@ -606,67 +601,51 @@ hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, u
 {
     const uint32_t nout = nsamp_blk - max_delay;
     const int nbits = dedisp_packed_bits(dtype);
-    const uint64_t pitch_bytes = dedisp_pitch_bytes(flags & kDdZeroDm ? 2 : dtype, nsamp_blk);
+    const bool zero_dm = flags & RT_DEDISP_ZERO_DM;
+    const bool float_rows = zero_dm || nbits == 16 || dtype == RT_DEDISP_F32;
+    const uint64_t pitch_bytes = dedisp_pitch_bytes(float_rows ? RT_DEDISP_F32 : dtype, nsamp_blk);
     const dim3 sum_grid((nout + kDdTile - 1) / kDdTile, (ndm + kDdDms - 1) / kDdDms);
-    if (flags & kDdZeroDm) {
-        // m behind the float rows; every sample type then takes the float sum
+    if (float_rows) {
         const uint64_t pitch = pitch_bytes / 4;
-        float* m = (float*)ws + pitch * nchans;
-        const hipError_t e = launch_zero_dm_mean(block, dtype, nsamp_blk, nchans, d_mask, m, s);
-        if (e != hipSuccess) return e;
         const dim3 grid((uint32_t)((pitch + 63) / 64), (nchans + 63) / 64);
-        if (nbits)
-            dd_packed(dtype, [&](auto tag) {
+        if (zero_dm) {
+            float* m = (float*)ws + pitch * nchans;
+            const hipError_t e = launch_zero_dm_mean(block, dtype, nsamp_blk, nchans, d_mask, m, s);
+            if (e != hipSuccess) return e;
+            dd_dispatch(dtype, [&](auto tag) {
                 using T = decltype(tag);
                 hipLaunchKernelGGL(dedisp_transpose_zdm_kernel<T>, grid, dim3(kDdThreads), 0, s, (const T*)block,
                                    nsamp_blk, nchans, (const float*)m, (float*)ws, pitch);
             });
-        else if (dtype == 0)
-            hipLaunchKernelGGL(dedisp_transpose_zdm_kernel<uint8_t>, grid, dim3(kDdThreads), 0, s,
-                               (const uint8_t*)block, nsamp_blk, nchans, (const float*)m, (float*)ws, pitch);
-        else if (dtype == 1)
-            hipLaunchKernelGGL(dedisp_transpose_zdm_kernel<int8_t>, grid, dim3(kDdThreads), 0, s,
-                               (const int8_t*)block, nsamp_blk, nchans, (const float*)m, (float*)ws, pitch);
-        else
-            hipLaunchKernelGGL(dedisp_transpose_zdm_kernel<float>, grid, dim3(kDdThreads), 0, s,
-                               (const float*)block, nsamp_blk, nchans, (const float*)m, (float*)ws, pitch);
-        launch_sum(sum_grid, s, (const float*)ws, pitch, nchans, d_delays, d_mask, ndm, max_delay, nout, out, out_stride,
-                   0, d_bands, nbands);
-    } else if (nbits == 16) {
-        // exact float32 rows, then the float sum
-        const uint64_t pitch = pitch_bytes / 4;
-        const dim3 grid((uint32_t)((pitch + 63) / 64), (nchans + 63) / 64);
-        hipLaunchKernelGGL((dedisp_transpose_zdm_kernel<DdBits<16>, false>), grid, dim3(kDdThreads), 0, s,
-                           (const DdBits<16>*)block, nsamp_blk, nchans, (const float*)nullptr, (float*)ws, pitch);
-        launch_sum(sum_grid, s, (const float*)ws, pitch, nchans, d_delays, d_mask, ndm, max_delay, nout, out, out_stride,
-                   0, d_bands, nbands);
-    } else if (nbits) {
-        // the 8-bit rows of the values, then the 8-bit sum with no bias
-        const uint32_t row_bytes = (uint32_t)((uint64_t)nchans * nbits / 8);
-        const uint32_t dwords = row_bytes % 4 == 0 && (uintptr_t)block % 4 == 0;
-        const dim3 grid((uint32_t)((pitch_bytes + 255) / 256), (row_bytes + 63) / 64);
-        dd_packed(dtype, [&](auto tag) {
-            constexpr int kBits = decltype(tag)::kBits;
-            if constexpr (kBits < 16)
-                hipLaunchKernelGGL(dedisp_unpack_transpose_kernel<kBits>, grid, dim3(kDdThreads), 0, s,
-                                   (const uint8_t*)block, nsamp_blk, nchans, row_bytes, (uint8_t*)ws, pitch_bytes,
-                                   dwords);
-        });
-        launch_sum(sum_grid, s, (const uint8_t*)ws, pitch_bytes, nchans, d_delays, d_mask, ndm, max_delay, nout, out,
-                   out_stride, 0, d_bands, nbands);
-    } else if (dtype == 2) {
-        const uint64_t pitch = pitch_bytes / 4;
-        const dim3 grid((uint32_t)((pitch + 63) / 64), (nchans + 63) / 64);
-        hipLaunchKernelGGL(dedisp_transpose32_kernel, grid, dim3(kDdThreads), 0, s, (const float*)block, nsamp_blk,
-                           nchans, (float*)ws, pitch);
+        } else if (nbits == 16) {   // exact float32 values
+            hipLaunchKernelGGL((dedisp_transpose_zdm_kernel<DdBits<16>, false>), grid, dim3(kDdThreads), 0, s,
+                               (const DdBits<16>*)block, nsamp_blk, nchans, (const float*)nullptr, (float*)ws, pitch);
+        } else {
+            hipLaunchKernelGGL(dedisp_transpose32_kernel, grid, dim3(kDdThreads), 0, s, (const float*)block, nsamp_blk,
+                               nchans, (float*)ws, pitch);
+        }
         launch_sum(sum_grid, s, (const float*)ws, pitch, nchans, d_delays, d_mask, ndm, max_delay, nout, out, out_stride,
                    0, d_bands, nbands);
     } else {
-        const dim3 grid((uint32_t)((pitch_bytes + 255) / 256), (nchans + 63) / 64);
-        hipLaunchKernelGGL(dedisp_transpose8_kernel, grid, dim3(kDdThreads), 0, s, (const uint8_t*)block, nsamp_blk,
-                           nchans, (uint8_t*)ws, pitch_bytes, dtype == 1 ? 0x80u : 0u);
+        if (nbits) {   // the values themselves: no bias
+            const uint32_t row_bytes = (uint32_t)((uint64_t)nchans * nbits / 8);
+            const uint32_t dwords = row_bytes % 4 == 0 && (uintptr_t)block % 4 == 0;
+            const dim3 grid((uint32_t)((pitch_bytes + 255) / 256), (row_bytes + 63) / 64);
+            const auto unpack = [&](auto tag) {
+                hipLaunchKernelGGL(dedisp_unpack_transpose_kernel<decltype(tag)::kBits>, grid, dim3(kDdThreads), 0, s,
+                                   (const uint8_t*)block, nsamp_blk, nchans, row_bytes, (uint8_t*)ws, pitch_bytes,
+                                   dwords);
+            };
+            if (nbits == 1) unpack(DdBits<1>{});
+            else if (nbits == 2) unpack(DdBits<2>{});
+            else unpack(DdBits<4>{});
+        } else {
+            const dim3 grid((uint32_t)((pitch_bytes + 255) / 256), (nchans + 63) / 64);
+            hipLaunchKernelGGL(dedisp_transpose8_kernel, grid, dim3(kDdThreads), 0, s, (const uint8_t*)block, nsamp_blk,
+                               nchans, (uint8_t*)ws, pitch_bytes, dtype == RT_DEDISP_I8 ? 0x80u : 0u);
+        }
         launch_sum(sum_grid, s, (const uint8_t*)ws, pitch_bytes, nchans, d_delays, d_mask, ndm, max_delay, nout, out,
-                   out_stride, dtype == 1 ? 128 : 0, d_bands, nbands);
+                   out_stride, dtype == RT_DEDISP_I8 ? 128 : 0, d_bands, nbands);
     }
     return hipGetLastError();
 }

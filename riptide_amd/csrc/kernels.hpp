@@ -88,13 +88,7 @@ hipError_t launch_refine(const float* d_cubes, const int32_t* d_shifts, const ui
                          const RefineCand* d_cands, uint32_t num_cands, uint32_t blocks_a, uint32_t blocks_b,
                          uint32_t lds_a, uint32_t lds_b, float* d_y, float* d_snr, float* d_profiles, hipStream_t s);
 
-// dedisp_kernels.hip
-// bits of a packed sample type code (RT_DEDISP_U1, U2, U4, U16: the block is
-// then bytes, [nsamp_blk, nchans * bits / 8], byte-aligned), 0 for a plain one
-constexpr int dedisp_packed_bits(int dtype)
-{
-    return dtype == 0x101 ? 1 : dtype == 0x102 ? 2 : dtype == 0x104 ? 4 : dtype == 0x110 ? 16 : 0;
-}
+// dedisp_kernels.hip (the sample type codes and the shared checks: dedisp_types.hpp)
 // bytes of one channel-major row of the transposed block (dtype: the
 // RT_DEDISP_* code of riptide_amd.h), a multiple of 16: bytes for 8-bit and
 // 1/2/4-bit data, floats for float and 16-bit data
@@ -102,11 +96,10 @@ uint64_t dedisp_pitch_bytes(int dtype, uint64_t nsamp_blk);
 // out[d * out_stride + t] for t < nsamp_blk - max_delay; ws: nchans rows of
 // dedisp_pitch_bytes, 16-byte aligned.  The caller has checked the shape
 // (rt_dedisperse_device).
-// flags: 0 or kDdZeroDm (the zero-DM filter: m = the rows' means over the
-// unmasked channels, float rows of x - m, the float sum for every dtype).
-constexpr uint32_t kDdZeroDm = 1u;   // RT_DEDISP_ZERO_DM
-// bytes of ws for these flags: the rows, with kDdZeroDm float rows plus one
-// more pitch for m [nsamp_blk]
+// flags: 0 or RT_DEDISP_ZERO_DM (the zero-DM filter: m = the rows' means over
+// the unmasked channels, float rows of x - m, the float sum for every dtype).
+// bytes of ws for these flags: the rows, with RT_DEDISP_ZERO_DM float rows plus
+// one more pitch for m [nsamp_blk]
 uint64_t dedisp_workspace_bytes(int dtype, uint64_t nsamp_blk, uint64_t nchans, uint32_t flags);
 // d_bands: nullptr, or uint32 [nbands][2] channel ranges [lo, hi) in device
 // memory (clamped to nchans as they are read): out[(d * nbands + b) *

@@ -28,6 +28,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from .engine import DEDISP_DTYPES, DEDISP_PACKED_NBITS, DEDISP_ZERO_DM, checked_bands as _checked_bands
 
 _L = _lib.load()
 _check = _lib.check
@@ -42,8 +43,6 @@ DEFAULT_BUDGET_BYTES = 32 << 30
 # default bytes of one gulp of input
 DEFAULT_GULP_BYTES = 256 << 20
 
-_DTYPE_CODES = {np.dtype(np.uint8): 0, np.dtype(np.int8): 1, np.dtype(np.float32): 2}
-_NBITS_CODES = {1: 0x101, 2: 0x102, 4: 0x104, 16: 0x110}    # RT_DEDISP_U1 .. RT_DEDISP_U16
 MAX_CHANS_8BIT = 65793    # RT_DEDISP_MAX_CHANS_8BIT: 255 * nchans < 2^24
 
 
@@ -79,7 +78,7 @@ def _checked_packed(data, nbits):
     given with nbits."""
     nbits = int(nbits)
     data = np.asarray(data)
-    if nbits not in _NBITS_CODES:
+    if nbits not in DEDISP_PACKED_NBITS:
         raise ValueError("nbits must be 1, 2, 4 or 16")
     if data.ndim != 2 or data.dtype != np.uint8:
         raise ValueError("packed data must be a uint8 array [nsamp, row_bytes]")
@@ -89,7 +88,7 @@ def _checked_packed(data, nbits):
     if nbits != 16 and nchans > MAX_CHANS_8BIT:
         raise ValueError(f"{nbits}-bit data with {nchans} channels: sums are exact only up to {MAX_CHANS_8BIT} "
                          "channels (255 * nchans must be below 2^24)")
-    return np.ascontiguousarray(data), _NBITS_CODES[nbits], nchans
+    return np.ascontiguousarray(data), DEDISP_DTYPES[f"u{nbits}"], nchans
 
 
 def _host_block(data, nbits):
@@ -98,21 +97,17 @@ def _host_block(data, nbits):
         data, code, nchans = _checked_packed(data, nbits)
         return data, code, data.shape[0], nchans
     data = np.ascontiguousarray(_checked_data(data))
-    return data, _DTYPE_CODES[data.dtype], data.shape[0], data.shape[1]
+    return data, DEDISP_DTYPES[data.dtype.name], data.shape[0], data.shape[1]
 
 
 def _checked_data(data):
     data = np.asarray(data)
-    if data.ndim != 2 or data.dtype not in _DTYPE_CODES:
+    if data.ndim != 2 or data.dtype.name not in DEDISP_DTYPES:
         raise ValueError("data must be a uint8, int8 or float32 array [nsamp, nchans]")
     if data.dtype != np.float32 and data.shape[1] > MAX_CHANS_8BIT:
         raise ValueError(f"8-bit data with {data.shape[1]} channels: sums are exact only up to {MAX_CHANS_8BIT} "
                          "channels (255 * nchans must be below 2^24)")
     return data
-
-
-def _flags(zero_dm):
-    return 1 if zero_dm else 0     # RT_DEDISP_ZERO_DM
 
 
 def zero_dm_mean_host(data, mask=None, nbits=None):
@@ -127,23 +122,58 @@ def zero_dm_mean_host(data, mask=None, nbits=None):
     return m
 
 
-def dedisperse_host(data, delays, max_delay, mask=None, nout=None, zero_dm=False, nbits=None):
-    """The specification on the host (rt_dedisperse_host_opt, no device):
-    float32 [ndm, nout] from data [nsamp, nchans] and a delay table; nout
-    defaults to nsamp - max_delay.  nbits: data is packed rows, as for
-    dedisperse."""
+def _dedisperse_host(data, delays, max_delay, bands, mask, nout, zero_dm, nbits):
+    """dedisperse_host (bands None) and dedisperse_bands_host."""
     data, code, nsamp, nchans = _host_block(data, nbits)
     delays = np.ascontiguousarray(delays, dtype=np.int64)
     if delays.ndim != 2 or delays.shape[1] != nchans:
         raise ValueError("delays must be [ndm, nchans]")
     mask = _checked_mask(mask, nchans)
+    if bands is not None:
+        bands = np.ascontiguousarray(bands, dtype=np.uint32)
+        if bands.ndim != 2 or bands.shape[1] != 2:
+            raise ValueError("bands must be [nbands, 2]")
     nout = nsamp - int(max_delay) if nout is None else int(nout)
     if nout < 0:
         raise ValueError(f"max_delay {max_delay} exceeds the {nsamp} samples of the input")
-    out = np.zeros((delays.shape[0], nout), dtype=np.float32)
-    _check(_L.rt_dedisperse_host_opt(_lib.ptr(data), code, nsamp, nchans, _lib.ptr(delays),
-                                     None if mask is None else _lib.ptr(mask), delays.shape[0], int(max_delay),
-                                     nout, _lib.ptr(out), _flags(zero_dm)))
+    ndm = delays.shape[0]
+    out = np.zeros((ndm, nout) if bands is None else (ndm, bands.shape[0], nout), dtype=np.float32)
+    head = (_lib.ptr(data), code, nsamp, nchans, _lib.ptr(delays), None if mask is None else _lib.ptr(mask), ndm)
+    tail = (int(max_delay), nout, _lib.ptr(out), DEDISP_ZERO_DM if zero_dm else 0)
+    if bands is None:
+        _check(_L.rt_dedisperse_host_opt(*head, *tail))
+    else:
+        _check(_L.rt_dedisperse_bands_host(*head, _lib.ptr(bands), bands.shape[0], *tail))
+    return out
+
+
+def dedisperse_host(data, delays, max_delay, mask=None, nout=None, zero_dm=False, nbits=None):
+    """The specification on the host (rt_dedisperse_host_opt, no device):
+    float32 [ndm, nout] from data [nsamp, nchans] and a delay table; nout
+    defaults to nsamp - max_delay.  nbits: data is packed rows, as for
+    dedisperse."""
+    return _dedisperse_host(data, delays, max_delay, None, mask, nout, zero_dm, nbits)
+
+
+def _dedisperse(data, freqs, tsamp, dms, bands, mask, kdm, zero_dm, nbits):
+    """dedisperse (bands None) and dedisperse_bands."""
+    data, code, nsamp, nchans = _host_block(data, nbits)
+    delays, max_delay = dispersion_delays(freqs, dms, tsamp, kdm)
+    if delays.shape[1] != nchans:
+        raise ValueError("freqs must have one entry per channel of data")
+    mask = _checked_mask(mask, nchans)
+    if bands is not None:
+        bands = _checked_bands(bands, nchans)
+    if max_delay >= nsamp:
+        raise ValueError(f"the largest delay ({max_delay} samples) is not below the {nsamp} samples of the data")
+    ndm, nout = delays.shape[0], nsamp - max_delay
+    out = np.empty((ndm, nout) if bands is None else (ndm, bands.shape[0], nout), dtype=np.float32)
+    head = (_lib.ptr(data), code, nsamp, nchans, _lib.ptr(delays), None if mask is None else _lib.ptr(mask), ndm)
+    tail = (max_delay, _lib.ptr(out), DEDISP_ZERO_DM if zero_dm else 0)
+    if bands is None:
+        _check(_L.rt_dedisperse_opt(*head, *tail))
+    else:
+        _check(_L.rt_dedisperse_bands(*head, _lib.ptr(bands), bands.shape[0], *tail))
     return out
 
 
@@ -154,18 +184,7 @@ def dedisperse(data, freqs, tsamp, dms, mask=None, kdm=KDM, zero_dm=False, nbits
     channel still counts towards the reference frequency and max_delay.
     nbits (1, 2, 4 or 16): data is packed rows instead, uint8 [nsamp,
     nchans * nbits / 8] (reading.pack_samples / unpack_samples)."""
-    data, code, nsamp, nchans = _host_block(data, nbits)
-    delays, max_delay = dispersion_delays(freqs, dms, tsamp, kdm)
-    if delays.shape[1] != nchans:
-        raise ValueError("freqs must have one entry per channel of data")
-    mask = _checked_mask(mask, nchans)
-    if max_delay >= nsamp:
-        raise ValueError(f"the largest delay ({max_delay} samples) is not below the {nsamp} samples of the data")
-    out = np.empty((delays.shape[0], nsamp - max_delay), dtype=np.float32)
-    _check(_L.rt_dedisperse_opt(_lib.ptr(data), code, nsamp, nchans, _lib.ptr(delays),
-                                None if mask is None else _lib.ptr(mask), delays.shape[0], max_delay, _lib.ptr(out),
-                                _flags(zero_dm)))
-    return out
+    return _dedisperse(data, freqs, tsamp, dms, None, mask, kdm, zero_dm, nbits)
 
 
 def band_edges(nchans, nsub):
@@ -180,11 +199,6 @@ def band_edges(nchans, nsub):
     return np.stack([edges[:-1], edges[1:]], axis=1).astype(np.uint32)
 
 
-def _checked_bands(bands, nchans):
-    from .engine import checked_bands
-    return checked_bands(bands, nchans)
-
-
 def dedisperse_bands_host(data, delays, max_delay, bands, mask=None, nout=None, zero_dm=False, nbits=None):
     """The specification of the band sums on the host (rt_dedisperse_bands_host,
     no device): float32 [ndm, nbands, nout],
@@ -194,22 +208,7 @@ def dedisperse_bands_host(data, delays, max_delay, bands, mask=None, nout=None, 
     for bands uint32 [nbands, 2] of channel ranges [lo, hi), which may overlap,
     be empty or cover the whole file.  Everything else as dedisperse_host; with
     zero_dm the mean is over the unmasked channels of the whole file."""
-    data, code, nsamp, nchans = _host_block(data, nbits)
-    delays = np.ascontiguousarray(delays, dtype=np.int64)
-    if delays.ndim != 2 or delays.shape[1] != nchans:
-        raise ValueError("delays must be [ndm, nchans]")
-    mask = _checked_mask(mask, nchans)
-    bands = np.ascontiguousarray(bands, dtype=np.uint32)
-    if bands.ndim != 2 or bands.shape[1] != 2:
-        raise ValueError("bands must be [nbands, 2]")
-    nout = nsamp - int(max_delay) if nout is None else int(nout)
-    if nout < 0:
-        raise ValueError(f"max_delay {max_delay} exceeds the {nsamp} samples of the input")
-    out = np.zeros((delays.shape[0], bands.shape[0], nout), dtype=np.float32)
-    _check(_L.rt_dedisperse_bands_host(_lib.ptr(data), code, nsamp, nchans, _lib.ptr(delays),
-                                       None if mask is None else _lib.ptr(mask), delays.shape[0], _lib.ptr(bands),
-                                       bands.shape[0], int(max_delay), nout, _lib.ptr(out), _flags(zero_dm)))
-    return out
+    return _dedisperse_host(data, delays, max_delay, bands, mask, nout, zero_dm, nbits)
 
 
 def dedisperse_bands(data, freqs, tsamp, dms, bands, mask=None, kdm=KDM, zero_dm=False, nbits=None):
@@ -217,19 +216,18 @@ def dedisperse_bands(data, freqs, tsamp, dms, bands, mask=None, kdm=KDM, zero_dm
     [ndm, nbands, nsamp - max_delay] (rt_dedisperse_bands: upload, kernels,
     download).  The delays are against the highest frequency of all of
     `freqs`, whatever the bands."""
-    data, code, nsamp, nchans = _host_block(data, nbits)
-    delays, max_delay = dispersion_delays(freqs, dms, tsamp, kdm)
-    if delays.shape[1] != nchans:
-        raise ValueError("freqs must have one entry per channel of data")
-    mask = _checked_mask(mask, nchans)
-    bands = _checked_bands(bands, nchans)
-    if max_delay >= nsamp:
-        raise ValueError(f"the largest delay ({max_delay} samples) is not below the {nsamp} samples of the data")
-    out = np.empty((delays.shape[0], bands.shape[0], nsamp - max_delay), dtype=np.float32)
-    _check(_L.rt_dedisperse_bands(_lib.ptr(data), code, nsamp, nchans, _lib.ptr(delays),
-                                  None if mask is None else _lib.ptr(mask), delays.shape[0], _lib.ptr(bands),
-                                  bands.shape[0], max_delay, _lib.ptr(out), _flags(zero_dm)))
-    return out
+    return _dedisperse(data, freqs, tsamp, dms, bands, mask, kdm, zero_dm, nbits)
+
+
+def _checked_sample_type(fb):
+    """nbits of a reading.PackedFilterbank, None for a Filterbank; ValueError
+    for samples no entry point takes."""
+    nbits = getattr(fb, "nbits", None)
+    if nbits is None and np.dtype(fb.dtype).name not in DEDISP_DTYPES:
+        raise ValueError("the filterbank's samples must be uint8, int8 or float32")
+    if nbits is not None and nbits not in DEDISP_PACKED_NBITS:
+        raise ValueError("a packed filterbank must hold 1-, 2-, 4- or 16-bit samples")
+    return nbits
 
 
 def _gulp_layout(fb):
@@ -323,12 +321,8 @@ def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, n
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else
                        (device.index if isinstance(device, torch.device) else int(device)))
     nsamp, nchans = fb.nsamp, fb.nchans
-    nbits = getattr(fb, "nbits", None)
+    nbits = _checked_sample_type(fb)
     row_elems, dtype = _gulp_layout(fb)
-    if nbits is None and dtype not in _DTYPE_CODES:
-        raise ValueError("the filterbank's samples must be uint8, int8 or float32")
-    if nbits is not None and nbits not in _NBITS_CODES:
-        raise ValueError("a packed filterbank must hold 1-, 2-, 4- or 16-bit samples")
     if (dtype != np.float32 and nbits != 16) and nchans > MAX_CHANS_8BIT:
         raise ValueError(f"8-bit data with {nchans} channels: sums are exact only up to {MAX_CHANS_8BIT} channels "
                          "(255 * nchans must be below 2^24)")
@@ -361,19 +355,14 @@ def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, n
         d_delays = torch.from_numpy(delays.astype(np.int32)).to(dev)
         d_mask = None if mask is None else torch.from_numpy(mask).to(dev)
         workspace = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        if bands is None:
-            out = torch.empty((ndm, nout), dtype=torch.float32, device=dev)
+        out = torch.empty((ndm, nout) if bands is None else (ndm, bands.shape[0], nout), dtype=torch.float32,
+                          device=dev)
+        d_bands = None if bands is None else torch.from_numpy(bands.view(np.int32)).to(dev)
 
-            def process(block, start):
-                engine.dedisperse_device(block, d_delays, max_delay, mask=d_mask, out=out, out_offset=start,
-                                         workspace=workspace, zero_dm=zero_dm, nbits=nbits)
-        else:
-            out = torch.empty((ndm, bands.shape[0], nout), dtype=torch.float32, device=dev)
-            d_bands = torch.from_numpy(bands.view(np.int32)).to(dev)
-
-            def process(block, start):
-                engine.dedisperse_bands_device(block, d_delays, max_delay, d_bands, mask=d_mask, out=out,
-                                               out_offset=start, workspace=workspace, zero_dm=zero_dm, nbits=nbits)
+        def process(block, start):
+            # dedisperse_device, or with a table dedisperse_bands_device
+            engine._dedisperse_device(block, d_delays, max_delay, d_bands, d_mask, out, start, workspace, None,
+                                      zero_dm, nbits)
 
         stream_gulps(fb, dev, gulp, need_in, max_delay, process)
     return out

@@ -445,17 +445,17 @@ def single_pulse_device(data, widths, threshold, radius=None, dense=False, max_e
 # 'u16' are the packed types: the block is then uint8 rows of nchans * nbits / 8
 # bytes (reading.unpack_samples has the format)
 DEDISP_DTYPES = {"uint8": 0, "int8": 1, "float32": 2, "u1": 0x101, "u2": 0x102, "u4": 0x104, "u16": 0x110}
+DEDISP_PACKED_NBITS = (1, 2, 4, 16)    # the nbits of the packed keys; every other key is a numpy dtype's name
+DEDISP_ZERO_DM = 1    # RT_DEDISP_ZERO_DM, the one flag bit
+# (dedispersion.py and rfi.py take the codes and the flag from here)
 
 
 def _dedisp_name(dtype, nbits):
     """The key of DEDISP_DTYPES for a dtype name, or for packed `nbits`."""
     name = str(dtype) if nbits is None else f"u{int(nbits)}"
-    if name not in DEDISP_DTYPES or (nbits is not None and int(nbits) not in (1, 2, 4, 16)):
+    if name not in DEDISP_DTYPES or (nbits is not None and int(nbits) not in DEDISP_PACKED_NBITS):
         raise ValueError("the sample type must be uint8, int8, float32, or packed with nbits 1, 2, 4 or 16")
     return name
-
-
-DEDISP_ZERO_DM = 1    # RT_DEDISP_ZERO_DM
 
 
 def checked_bands(bands, nchans):
@@ -500,6 +500,13 @@ def _dedisp_block(block, nbits=None):
     return name, block.shape[0], block.shape[1]
 
 
+def _check_device_mask(mask, block, nchans):
+    import torch
+    if mask is not None and (mask.dtype != torch.uint8 or mask.device != block.device or not mask.is_contiguous()
+                             or tuple(mask.shape) != (nchans,)):
+        raise ValueError("mask must be a contiguous uint8 [nchans] tensor on the block's device")
+
+
 def zero_dm_mean_device(block, mask=None, out=None, stream=None, nbits=None):
     """The zero-DM time series of one resident block (rt_zero_dm_mean_device,
     the row-mean kernel alone): float32 [nsamp_blk], every time sample's mean
@@ -510,9 +517,7 @@ def zero_dm_mean_device(block, mask=None, out=None, stream=None, nbits=None):
     Stream-ordered, no host synchronisation."""
     import torch
     name, nsamp_blk, nchans = _dedisp_block(block, nbits)
-    if mask is not None and (mask.dtype != torch.uint8 or mask.device != block.device or not mask.is_contiguous()
-                             or tuple(mask.shape) != (nchans,)):
-        raise ValueError("mask must be a contiguous uint8 [nchans] tensor on the block's device")
+    _check_device_mask(mask, block, nchans)
     s = stream if stream is not None else torch.cuda.current_stream(block.device)
     with torch.cuda.device(block.device), torch.cuda.stream(s):
         if out is None:
@@ -563,6 +568,65 @@ def channel_stats_device(block, acc, workspace=None, stream=None, nbits=None):
     return acc
 
 
+def _dedisperse_device(block, delays, max_delay, bands, mask, out, out_offset, workspace, stream, zero_dm, nbits):
+    """dedisperse_device (bands None) and dedisperse_bands_device: what they
+    share -- block, delays, mask, max_delay, workspace and stream -- checked
+    once, out by the rule of whichever it is, then the one call."""
+    import torch
+    name, nsamp_blk, nchans = _dedisp_block(block, nbits)
+    if (delays.dim() != 2 or delays.dtype != torch.int32 or delays.device != block.device
+            or not delays.is_contiguous() or delays.shape[1] != nchans):
+        raise ValueError("delays must be a contiguous int32 [ndm, nchans] tensor on the block's device")
+    ndm = delays.shape[0]
+    _check_device_mask(mask, block, nchans)
+    max_delay, out_offset = int(max_delay), int(out_offset)
+    nout = nsamp_blk - max_delay
+    s = stream if stream is not None else torch.cuda.current_stream(block.device)
+    with torch.cuda.device(block.device), torch.cuda.stream(s):
+        if bands is not None:
+            if not torch.is_tensor(bands):
+                bands = torch.from_numpy(checked_bands(bands, nchans).view(np.int32)).to(block.device)
+            if (bands.dim() != 2 or bands.dtype != torch.int32 or bands.device != block.device
+                    or not bands.is_contiguous() or bands.shape[1] != 2):
+                raise ValueError("bands must be uint32 [nbands, 2] (as a tensor: contiguous int32 on the block's "
+                                 "device)")
+            nbands = bands.shape[0]
+        # validates the shape before anything is allocated
+        need = dedisperse_workspace_bytes(name, nsamp_blk, nchans, zero_dm)
+        if not 0 <= max_delay < nsamp_blk:
+            raise ValueError(f"max_delay {max_delay} must be in [0, {nsamp_blk}): the block is no longer than the "
+                             "largest delay")
+        if out is None:
+            out = torch.empty((ndm, nout) if bands is None else (ndm, nbands, nout), dtype=torch.float32,
+                              device=block.device)
+        elif bands is None:
+            if (out.dim() != 2 or out.dtype != torch.float32 or out.device != block.device or out.shape[0] != ndm
+                    or out.stride(1) != 1 or out.shape[1] < out_offset + nout
+                    or (ndm > 1 and out.stride(0) < out.shape[1])):
+                raise ValueError(f"out must be float32 [{ndm}, >= {out_offset + nout}] rows with unit stride on "
+                                 "the block's device")
+        elif (out.dim() != 3 or out.dtype != torch.float32 or out.device != block.device
+              or tuple(out.shape[:2]) != (ndm, nbands) or not out.is_contiguous() or out.shape[2] < out_offset + nout):
+            raise ValueError(f"out must be a contiguous float32 [{ndm}, {nbands}, >= {out_offset + nout}] "
+                             "tensor on the block's device")
+        if workspace is None:
+            workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=block.device)
+        elif (workspace.dtype != torch.uint8 or workspace.device != block.device or not workspace.is_contiguous()
+              or workspace.numel() < need):
+            raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on the block's device")
+        head = (_lib.ptr(block), DEDISP_DTYPES[name], nsamp_blk, nchans, _lib.ptr(delays),
+                None if mask is None else _lib.ptr(mask), ndm)
+        tail = (out_offset, _lib.ptr(workspace), workspace.numel(), _stream_handle(s),
+                DEDISP_ZERO_DM if zero_dm else 0)
+        if bands is None:
+            _check(_L.rt_dedisperse_device_opt(*head, max_delay, _lib.ptr(out),
+                                               out.stride(0) if ndm > 1 else out.shape[1], *tail))
+        else:
+            _check(_L.rt_dedisperse_bands_device(*head, _lib.ptr(bands) if nbands else None, nbands, max_delay,
+                                                 _lib.ptr(out), out.shape[2], *tail))
+    return out
+
+
 def dedisperse_device(block, delays, max_delay, mask=None, out=None, out_offset=0, workspace=None, stream=None,
                       zero_dm=False, nbits=None):
     """Incoherent dedispersion of one resident block (rt_dedisperse_device):
@@ -587,45 +651,7 @@ def dedisperse_device(block, delays, max_delay, mask=None, out=None, out_offset=
     (zero_dm_mean_device), and every dtype is then summed in float32 in channel
     order; the workspace is the larger one of dedisperse_workspace_bytes(...,
     zero_dm=True)."""
-    import torch
-    name, nsamp_blk, nchans = _dedisp_block(block, nbits)
-    if (delays.dim() != 2 or delays.dtype != torch.int32 or delays.device != block.device
-            or not delays.is_contiguous() or delays.shape[1] != nchans):
-        raise ValueError("delays must be a contiguous int32 [ndm, nchans] tensor on the block's device")
-    ndm = delays.shape[0]
-    if mask is not None and (mask.dtype != torch.uint8 or mask.device != block.device or not mask.is_contiguous()
-                             or tuple(mask.shape) != (nchans,)):
-        raise ValueError("mask must be a contiguous uint8 [nchans] tensor on the block's device")
-    max_delay = int(max_delay)
-    nout = nsamp_blk - max_delay
-    s = stream if stream is not None else torch.cuda.current_stream(block.device)
-    with torch.cuda.device(block.device), torch.cuda.stream(s):
-        # validates the shape before anything is allocated
-        need = dedisperse_workspace_bytes(name, nsamp_blk, nchans, zero_dm)
-        if not 0 <= max_delay < nsamp_blk:
-            raise ValueError(f"max_delay {max_delay} must be in [0, {nsamp_blk}): the block is no longer than the "
-                             "largest delay")
-        if out is None:
-            out = torch.empty((ndm, nout), dtype=torch.float32, device=block.device)
-        elif (out.dim() != 2 or out.dtype != torch.float32 or out.device != block.device or out.shape[0] != ndm
-              or out.stride(1) != 1 or out.shape[1] < int(out_offset) + nout
-              or (ndm > 1 and out.stride(0) < out.shape[1])):
-            raise ValueError(f"out must be float32 [{ndm}, >= {int(out_offset) + nout}] rows with unit stride on "
-                             "the block's device")
-        if workspace is None:
-            workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=block.device)
-        elif (workspace.dtype != torch.uint8 or workspace.device != block.device or not workspace.is_contiguous()
-              or workspace.numel() < need):
-            raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on the block's device")
-        args = (_lib.ptr(block), DEDISP_DTYPES[name], nsamp_blk, nchans, _lib.ptr(delays),
-                None if mask is None else _lib.ptr(mask), ndm, max_delay, _lib.ptr(out),
-                out.stride(0) if ndm > 1 else out.shape[1], int(out_offset), _lib.ptr(workspace), workspace.numel(),
-                _stream_handle(s))
-        if zero_dm:
-            _check(_L.rt_dedisperse_device_opt(*args, DEDISP_ZERO_DM))
-        else:
-            _check(_L.rt_dedisperse_device(*args))
-    return out
+    return _dedisperse_device(block, delays, max_delay, None, mask, out, out_offset, workspace, stream, zero_dm, nbits)
 
 
 def dedisperse_bands_device(block, delays, max_delay, bands, mask=None, out=None, out_offset=0, workspace=None,
@@ -644,48 +670,7 @@ def dedisperse_bands_device(block, delays, max_delay, bands, mask=None, out=None
     (contiguous; allocated [ndm, nbands, nsamp_blk - max_delay] when None).
     One pass over the block for all bands; block, delays, mask, workspace and
     nbits as for dedisperse_device."""
-    import torch
-    name, nsamp_blk, nchans = _dedisp_block(block, nbits)
-    if (delays.dim() != 2 or delays.dtype != torch.int32 or delays.device != block.device
-            or not delays.is_contiguous() or delays.shape[1] != nchans):
-        raise ValueError("delays must be a contiguous int32 [ndm, nchans] tensor on the block's device")
-    ndm = delays.shape[0]
-    if mask is not None and (mask.dtype != torch.uint8 or mask.device != block.device or not mask.is_contiguous()
-                             or tuple(mask.shape) != (nchans,)):
-        raise ValueError("mask must be a contiguous uint8 [nchans] tensor on the block's device")
-    max_delay = int(max_delay)
-    nout = nsamp_blk - max_delay
-    s = stream if stream is not None else torch.cuda.current_stream(block.device)
-    with torch.cuda.device(block.device), torch.cuda.stream(s):
-        if not torch.is_tensor(bands):
-            bands = torch.from_numpy(checked_bands(bands, nchans).view(np.int32)).to(block.device)
-        if (bands.dim() != 2 or bands.dtype != torch.int32 or bands.device != block.device
-                or not bands.is_contiguous() or bands.shape[1] != 2):
-            raise ValueError("bands must be uint32 [nbands, 2] (as a tensor: contiguous int32 on the block's device)")
-        nbands = bands.shape[0]
-        # validates the shape before anything is allocated
-        need = dedisperse_workspace_bytes(name, nsamp_blk, nchans, zero_dm)
-        if not 0 <= max_delay < nsamp_blk:
-            raise ValueError(f"max_delay {max_delay} must be in [0, {nsamp_blk}): the block is no longer than the "
-                             "largest delay")
-        if out is None:
-            out = torch.empty((ndm, nbands, nout), dtype=torch.float32, device=block.device)
-        elif (out.dim() != 3 or out.dtype != torch.float32 or out.device != block.device
-              or tuple(out.shape[:2]) != (ndm, nbands) or not out.is_contiguous()
-              or out.shape[2] < int(out_offset) + nout):
-            raise ValueError(f"out must be a contiguous float32 [{ndm}, {nbands}, >= {int(out_offset) + nout}] "
-                             "tensor on the block's device")
-        if workspace is None:
-            workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=block.device)
-        elif (workspace.dtype != torch.uint8 or workspace.device != block.device or not workspace.is_contiguous()
-              or workspace.numel() < need):
-            raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on the block's device")
-        _check(_L.rt_dedisperse_bands_device(_lib.ptr(block), DEDISP_DTYPES[name], nsamp_blk, nchans,
-                                             _lib.ptr(delays), None if mask is None else _lib.ptr(mask), ndm,
-                                             _lib.ptr(bands) if nbands else None, nbands, max_delay, _lib.ptr(out),
-                                             out.shape[2], int(out_offset), _lib.ptr(workspace), workspace.numel(),
-                                             _stream_handle(s), DEDISP_ZERO_DM if zero_dm else 0))
-    return out
+    return _dedisperse_device(block, delays, max_delay, bands, mask, out, out_offset, workspace, stream, zero_dm, nbits)
 
 
 def profile_enable(on=True):

@@ -14,7 +14,7 @@ dedispersion.dedisperse* and of search_filterbank.
 """
 import numpy as np
 
-from .dedispersion import DEFAULT_GULP_BYTES, _DTYPE_CODES, _NBITS_CODES, _checked_mask, _gulp_layout, stream_gulps
+from .dedispersion import DEFAULT_GULP_BYTES, _checked_mask, _checked_sample_type, _gulp_layout, stream_gulps
 
 __all__ = ["ChannelStats", "channel_stats", "channel_mask", "zero_dm_series"]
 
@@ -40,11 +40,7 @@ def _device_and_rows(fb, nsamp, gulp, device):
     import torch
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else
                        (device.index if isinstance(device, torch.device) else int(device)))
-    nbits = getattr(fb, "nbits", None)
-    if nbits is None and np.dtype(fb.dtype) not in _DTYPE_CODES:
-        raise ValueError("the filterbank's samples must be uint8, int8 or float32")
-    if nbits is not None and nbits not in _NBITS_CODES:
-        raise ValueError("a packed filterbank must hold 1-, 2-, 4- or 16-bit samples")
+    _checked_sample_type(fb)
     row_elems, dtype = _gulp_layout(fb)
     nrows = fb.nsamp if nsamp is None else int(nsamp)
     if not 0 < nrows <= fb.nsamp:

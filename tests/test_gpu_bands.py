@@ -158,6 +158,51 @@ def test_full_band_equals_the_plain_call(torch, kind, zero_dm):
             assert np.array_equal(out, host)
 
 
+KINDS = ["uint8", "int8", "float32", "u1", "u2", "u4", "u16"]
+
+
+@pytest.mark.parametrize("zero_dm", [False, True])
+@pytest.mark.parametrize("kind", KINDS)
+def test_every_sample_type_with_bands(torch, kind, zero_dm):
+    """Every sample type x the zero-DM filter through the band call, against
+    dedisperse_bands_host by test_full_band_equals_the_plain_call's comparison:
+    the host's bits for integer sums, both inside the float64 bound for float32
+    sums.  40 channels: 1-bit rows of 5 bytes (byte loads), 4-bit rows of 20
+    (dword loads), two 16-channel steps and a tail of 8; 17 DMs and 257 outputs:
+    one live row in the second DM tile, one sample in the second time tile; one
+    channel masked.  The row of [0, 40) has the plain call's bits and the empty
+    band is zero."""
+    from riptide_amd.dedispersion import dedisperse_bands_host, dispersion_delays, zero_dm_mean_host
+    from riptide_amd.reading import pack_samples, unpack_samples
+    nchans, ndm, nout = 40, 17, 257
+    bands = np.array([[0, 40], [5, 21], [16, 16], [33, 40]], dtype=np.uint32)
+    delays, max_delay = dispersion_delays(dc.band(nchans), np.linspace(0.0, 8.0, ndm), dc.TSAMP)
+    assert 20 <= max_delay <= 60
+    rng = np.random.RandomState(KINDS.index(kind))
+    nbits = int(kind[1:]) if kind in ("u1", "u2", "u4", "u16") else None
+    if nbits:
+        x = pack_samples(rng.randint(0, 1 << nbits, size=(max_delay + nout, nchans)), nbits)
+        assert x.shape[1] == nchans * nbits // 8
+    else:
+        x = dc.samples(rng, max_delay + nout, nchans, kind)
+    mask = np.zeros(nchans, dtype=bool)
+    mask[18] = True
+    out = run_bands(torch, x, delays, max_delay, bands, mask=mask, zero_dm=zero_dm, nbits=nbits)
+    host = dedisperse_bands_host(x, delays, max_delay, bands, mask=mask, nout=nout, zero_dm=zero_dm, nbits=nbits)
+    assert out.shape == host.shape == (ndm, len(bands), nout)
+    if zero_dm or kind in ("float32", "u16"):
+        vals = x if nbits is None else unpack_samples(x, nbits, nchans)
+        rows = vals.astype(np.float32)
+        if zero_dm:
+            rows = rows - zero_dm_mean_host(x, mask=mask, nbits=nbits)[:, None]
+        assert_band_rows(out, rows, delays, nout, bands, mask)
+        assert_band_rows(host, rows, delays, nout, bands, mask)
+    else:
+        assert np.array_equal(out, host)
+    assert np.array_equal(out[:, 0], run_plain(torch, x, delays, max_delay, mask=mask, zero_dm=zero_dm, nbits=nbits))
+    assert not out[:, 2].any() and out[:, 3].any()
+
+
 def test_output_window(torch):
     """test_gpu_dedisp.py's window case: the host-buffer form equals the block
     call, out_offset is honoured and a sentinel outside the window survives."""
