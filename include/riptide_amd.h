@@ -758,6 +758,88 @@ int rt_channel_stats_workspace_bytes(size_t nsamp_blk, size_t nchans, size_t* by
 int rt_channel_stats_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans, double* d_acc,
                             void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the block mask: interference narrow in frequency and intermittent in time */
+/* A mask in time and frequency.  Time is cut into blocks of block_len samples,
+ * block b the absolute samples [b * block_len, (b + 1) * block_len) of the
+ * observation; cells is uint8 [nblocks, nchans], non-zero = that channel is
+ * flagged during that block.  fill holds one value per channel in the sample's
+ * own type: uint8 [nchans] for RT_DEDISP_U8, int8 for RT_DEDISP_I8, float32
+ * for RT_DEDISP_F32 (4-byte aligned), uint16 for RT_DEDISP_U16 (2-byte
+ * aligned), and for the 1/2/4-bit types uint8 [nchans], one unpacked value per
+ * byte of which only the low nbits bits are used.  Every bit pattern is a
+ * valid sample: nothing is range-checked.  t_origin is the absolute sample
+ * index of row 0 of the block or gulp the call is given.  The mask is a pure
+ * replacement in front of everything else:
+ *   x'[t, c] = fill[c]  if cells[(t_origin + t) / block_len, c] != 0
+ *              x[t, c]  otherwise
+ * and every other definition of this header (the channel mask, the zero-DM
+ * mean over the unmasked channels, y = x' - m, the sums, the band sums, the
+ * exactness of integer data) is applied to x' unchanged; a channel the channel
+ * mask skips stays skipped whatever its cells say.  So rt_block_replace_host
+ * followed by the existing host specification is the specification of the
+ * _cells calls below, and the device gives the bits of its plain call on x'.
+ * A NULL pointer to the struct means no block mask.  A call whose rows reach
+ * past the mask, t_origin + nsamp > nblocks * block_len, is RT_EINVAL, as are
+ * block_len == 0, a NULL cells or fill, and t_origin + nsamp >= 2^64 (the
+ * sum is formed in 64 bits): no load leaves the cells.  The
+ * kernels index the cells in 64 bits: nblocks * nchans has no limit of its
+ * own.  The mask needs no workspace (rt_dedisperse_workspace_bytes_opt is
+ * unchanged).  The host-buffer calls rt_dedisperse, rt_dedisperse_opt and
+ * rt_dedisperse_bands take no block mask. */
+typedef struct rt_block_mask {
+    const uint8_t* cells;      /* [nblocks, nchans] */
+    size_t         nblocks;
+    size_t         block_len;  /* >= 1 */
+    uint64_t       t_origin;
+    const void*    fill;       /* [nchans], the sample's own type */
+} rt_block_mask;
+/* Host only, no device: the specification of the replacement.  out = x' in
+ * x's own format (packed rows stay packed), [nsamp, row_bytes of
+ * rt_dedisp_row_bytes]; out may be x.  cells and fill are host arrays.  A NULL
+ * bm copies.  RT_EINVAL for an unknown type code, nchans == 0, packed rows
+ * that are not whole bytes, and a mask refused as above. */
+int rt_block_replace_host(const void* x, int dtype, size_t nsamp, size_t nchans, const rt_block_mask* bm, void* out);
+/* Host only, no device: WRITES stats, float64 [nblk, 2, nchans] with nblk =
+ * ceil(nsamp / block_len): stats[b][0][c] the sum and stats[b][1][c] the sum
+ * of squares of x[t, c] over the rows of block b, blocks counted from row 0
+ * of x (the last one may be partial; int8 samples as signed values).  Integer
+ * samples give exact integers.  In float64 the order is fixed, and the device
+ * follows it, so both give the same bits for every sample type: a block is cut
+ * into chunks of 2048 rows from its first row; within a chunk row j (from 0)
+ * is added to partial sum j mod 4, each from 0.0 in row order; the chunk's sum
+ * is ((p0 + p1) + p2) + p3; the block's sum is the chunks' sums added in
+ * order from 0.0.  A square is one float64 product (exact for float32 and
+ * 16-bit samples).  RT_EINVAL for block_len == 0, an unknown type code and
+ * nchans == 0. */
+int rt_block_stats_host(const void* x, int dtype, size_t nsamp, size_t nchans, size_t block_len, double* stats);
+/* Device workspace bytes of rt_block_stats_device: none for block_len <= 2048,
+ * the per-chunk partial sums of longer blocks otherwise. */
+int rt_block_stats_workspace_bytes(size_t nsamp_blk, size_t nchans, size_t block_len, size_t* bytes);
+/* The same statistics of one resident block into d_stats, float64 [nblk, 2,
+ * nchans] in device memory (written, not accumulated), bit for bit the host's.
+ * No atomics.  Stream-ordered.  d_stats and d_workspace must be 8-byte aligned
+ * (d_workspace may be NULL when no bytes are needed).  RT_EINVAL (nothing is
+ * launched) for block_len == 0 and everything rt_channel_stats_device
+ * refuses. */
+int rt_block_stats_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans, size_t block_len,
+                          double* d_stats, void* d_workspace, size_t workspace_bytes, void* stream);
+/* The resident-block dedispersion call with an optional band table and an
+ * optional block mask: d_bands NULL with nbands == 0 is
+ * rt_dedisperse_device_opt, a table rt_dedisperse_bands_device; bm NULL is
+ * that call itself (the same kernels), a mask (cells and fill in device
+ * memory) gives the bits of that call on a block holding x'.  RT_EINVAL
+ * (nothing is launched) for a mask refused as above, a misaligned fill, and
+ * everything those calls refuse. */
+int rt_dedisperse_device_cells(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans,
+                               const int32_t* d_delays, const uint8_t* d_mask, size_t ndm, const uint32_t* d_bands,
+                               size_t nbands, int64_t max_delay, float* d_out, size_t out_stride, size_t out_offset,
+                               void* d_workspace, size_t workspace_bytes, void* stream, uint32_t flags,
+                               const rt_block_mask* bm);
+/* rt_zero_dm_mean_device with an optional block mask: the mean series of x',
+ * the bits of the plain call on a block holding x'. */
+int rt_zero_dm_mean_device_cells(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans,
+                                 const uint8_t* d_mask, float* d_m, void* stream, const rt_block_mask* bm);
+
 /* --------------------------- file input (device) --------------------------- */
 /* 8-bit SIGPROC samples (riptide/time_series.py:352-357) to float32 in device
  * memory: d_raw holds n bytes, int8 when is_signed else uint8; exact as

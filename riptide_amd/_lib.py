@@ -148,7 +148,27 @@ _SIGNATURES = {
     "rt_channel_stats_workspace_bytes": (_c_i, [_c_sz, _c_sz, _psz]),
     # block, dtype, nsamp_blk, nchans, acc, workspace, workspace bytes, stream
     "rt_channel_stats_device": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _c_sz, _vp]),
+    # the block mask: `bm` is a pointer to a BlockMaskStruct (rt_block_mask), or None
+    # x, dtype, nsamp, nchans, bm, out
+    "rt_block_replace_host": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp]),
+    # x, dtype, nsamp, nchans, block_len, stats (float64 [nblk, 2, nchans])
+    "rt_block_stats_host": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _c_sz, _vp]),
+    # nsamp_blk, nchans, block_len, bytes
+    "rt_block_stats_workspace_bytes": (_c_i, [_c_sz, _c_sz, _c_sz, _psz]),
+    # block, dtype, nsamp_blk, nchans, block_len, stats, workspace, workspace bytes, stream
+    "rt_block_stats_device": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _c_sz, _vp, _vp, _c_sz, _vp]),
+    # rt_dedisperse_bands_device's arguments (bands None, nbands 0: no table), then bm
+    "rt_dedisperse_device_cells": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _c_sz, _vp, _c_sz, ctypes.c_int64, _vp,
+                                          _c_sz, _c_sz, _vp, _c_sz, _vp, ctypes.c_uint32, _vp]),
+    # rt_zero_dm_mean_device's arguments, then bm
+    "rt_zero_dm_mean_device_cells": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _vp, _vp]),
 }
+
+
+class BlockMaskStruct(ctypes.Structure):
+    """rt_block_mask (include/riptide_amd.h); pass ctypes.byref of one as `bm`."""
+    _fields_ = [("cells", _vp), ("nblocks", _c_sz), ("block_len", _c_sz), ("t_origin", ctypes.c_uint64),
+                ("fill", _vp)]
 
 EXPORTED = tuple(_SIGNATURES)
 

@@ -193,7 +193,8 @@ class _SeriesShape(namedtuple("_SeriesShape", "nsamp tsamp")):
 
 
 def build_candidates_filterbank(clusters, fb_or_fname, range_confs, deredden_params, nsub=32, mask=None,
-                                zero_dm=False, kdm=None, nout=None, budget_bytes=None, device=None, refine=False):
+                                zero_dm=False, kdm=None, nout=None, budget_bytes=None, device=None, refine=False,
+                                block_mask=None):
     """Candidates of a list of PeakClusters, by decreasing S/N, straight from
     the channelised file (a name for reading.open_filterbank, or a Filterbank /
     PackedFilterbank): build_candidates without a load_series, and every
@@ -212,7 +213,7 @@ def build_candidates_filterbank(clusters, fb_or_fname, range_confs, deredden_par
 
     nout: samples of every series (default: nsamp minus the largest delay over
     those DMs; pass the search's own nout to fold exactly what was searched).
-    mask, zero_dm, kdm: as for search_filterbank.  tsmeta is the file's
+    mask, zero_dm, kdm, block_mask: as for search_filterbank.  tsmeta is the file's
     metadata with `dm` set, as search_filterbank's trials have it.  A cluster
     that cannot be folded is logged and left out.
 
@@ -252,7 +253,7 @@ def build_candidates_filterbank(clusters, fb_or_fname, range_confs, deredden_par
     for b0 in range(0, len(dms), batch):
         group = dms[b0:b0 + batch]
         series, _ = band_series(fb, group, bands, deredden_params, nout, mask=mask, zero_dm=zero_dm, kdm=kdm,
-                                device=device, budget_bytes=budget_bytes)
+                                device=device, budget_bytes=budget_bytes, block_mask=block_mask)
         todo, specs = [], []
         for i, dm in enumerate(group):
             for cl in by_dm[dm]:

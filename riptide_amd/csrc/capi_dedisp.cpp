@@ -1,7 +1,10 @@
 // C ABI, filterbank side: incoherent dedispersion, the zero-DM filter and the
 // channel statistics, with the shape limits of their kernels' 32-bit indices
-// and grids.  The six dedispersion calls are two cores, the resident-block one
-// and the host-buffer one, each with an optional band table.
+// and grids.  The seven dedispersion calls are two cores, the resident-block
+// one and the host-buffer one, each with an optional band table; the
+// resident-block core also takes an optional block mask (rt_block_mask), as
+// the zero-DM mean does, and the block statistics stand beside the channel
+// statistics.
 #include "riptide_amd.h"
 
 #include <mutex>
@@ -53,14 +56,36 @@ void dedisp_check_bands(size_t ndm, size_t nbands)
         throw std::invalid_argument("dedisperse: ndm * nbands rows overflow 32 bits");
 }
 
-// rt_dedisperse_device, _device_opt and rt_dedisperse_bands_device (bt->table in device memory)
+// A block mask of a device call over nsamp_blk rows (the shape is checked):
+// the shared check, the fill aligned to its type, then the kernels' form of
+// it.  No mask (a null pointer) is no DedispCells: the plain kernels.
+struct DeviceCells {
+    DedispCells cells{};
+    bool set = false;
+    DeviceCells(const rt_block_mask* bm, int dtype, size_t nsamp_blk)
+    {
+        dedisp_check_block_mask(bm, nsamp_blk);
+        if (!bm) return;
+        if ((uintptr_t)bm->fill % dedisp_fill_bytes(dtype))
+            throw std::invalid_argument("block_mask: misaligned fill");
+        cells = DedispCells{bm->cells, bm->fill, bm->t_origin, (uint64_t)bm->block_len};
+        set = true;
+    }
+    const DedispCells* get() const { return set ? &cells : nullptr; }
+};
+
+// rt_dedisperse_device, _device_opt, rt_dedisperse_bands_device (bt->table in
+// device memory) and rt_dedisperse_device_cells (bm: cells and fill in device
+// memory)
 int dedisperse_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans, const int32_t* d_delays,
                       const uint8_t* d_mask, size_t ndm, const BandTable* bt, int64_t max_delay, float* d_out,
-                      size_t out_stride, size_t out_offset, void* d_ws, size_t ws_bytes, void* stream, uint32_t flags)
+                      size_t out_stride, size_t out_offset, void* d_ws, size_t ws_bytes, void* stream, uint32_t flags,
+                      const rt_block_mask* bm = nullptr)
 {
     return guarded([&] {
         dedisp_check_flags(flags);
         dedisp_check_shape(dtype, nsamp_blk, nchans, ndm, max_delay);
+        const DeviceCells dc(bm, dtype, nsamp_blk);
         if (bt) dedisp_check_bands(ndm, bt->nbands);
         const size_t nout = nsamp_blk - (size_t)max_delay;
         if (out_offset > out_stride || nout > out_stride - out_offset)
@@ -74,7 +99,7 @@ int dedisperse_device(const void* d_block, int dtype, size_t nsamp_blk, size_t n
             throw std::invalid_argument("workspace too small");
         ck(launch_dedisperse(d_block, dtype, (uint32_t)nsamp_blk, (uint32_t)nchans, d_delays, d_mask, (uint32_t)ndm,
                              (uint32_t)max_delay, d_out + out_offset, out_stride, d_ws, flags, (hipStream_t)stream,
-                             bt ? bt->table : nullptr, bt ? (uint32_t)bt->nbands : 0u),
+                             bt ? bt->table : nullptr, bt ? (uint32_t)bt->nbands : 0u, dc.get()),
            "dedisperse");
         return RT_OK;
     });
@@ -130,6 +155,16 @@ void chanstats_check_shape(int dtype, size_t nsamp_blk, size_t nchans)
     dedisp_check_shape(RT_DEDISP_F32, nsamp_blk, nchans, 1, 0);
     if (!dedisp_known_dtype(dtype)) throw std::invalid_argument("channel_stats: unknown sample type code");
     if (dedisp_packed_bits(dtype)) dedisp_row_bytes(dtype, nchans);
+}
+
+// The block length the statistics kernels run with: a block longer than the
+// resident block is the same single block, so the length stays below 2^31
+// and the grid's x (at most nsamp_blk workgroups, or a few per 2048 rows)
+// below 2^31 too.
+size_t blockstats_block_len(size_t nsamp_blk, size_t block_len)
+{
+    if (!block_len) throw std::invalid_argument("block_stats: block_len must be at least 1");
+    return block_len < nsamp_blk ? block_len : nsamp_blk;
 }
 
 }  // namespace
@@ -199,17 +234,63 @@ int rt_dedisperse_bands(const void* x, int dtype, size_t nsamp, size_t nchans, c
     return dedisperse_buffers(x, dtype, nsamp, nchans, delays, mask, ndm, &bt, max_delay, out, flags);
 }
 
+int rt_dedisperse_device_cells(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans,
+                               const int32_t* d_delays, const uint8_t* d_mask, size_t ndm, const uint32_t* d_bands,
+                               size_t nbands, int64_t max_delay, float* d_out, size_t out_stride, size_t out_offset,
+                               void* d_ws, size_t ws_bytes, void* stream, uint32_t flags, const rt_block_mask* bm)
+{
+    const BandTable bt{d_bands, nbands};
+    return dedisperse_device(d_block, dtype, nsamp_blk, nchans, d_delays, d_mask, ndm,
+                             d_bands || nbands ? &bt : nullptr, max_delay, d_out, out_stride, out_offset, d_ws,
+                             ws_bytes, stream, flags, bm);
+}
+
 int rt_zero_dm_mean_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans, const uint8_t* d_mask,
                            float* d_m, void* stream)
 {
+    return rt_zero_dm_mean_device_cells(d_block, dtype, nsamp_blk, nchans, d_mask, d_m, stream, nullptr);
+}
+
+int rt_zero_dm_mean_device_cells(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans,
+                                 const uint8_t* d_mask, float* d_m, void* stream, const rt_block_mask* bm)
+{
     return guarded([&] {
         dedisp_check_shape(dtype, nsamp_blk, nchans, 1, 0);
+        const DeviceCells dc(bm, dtype, nsamp_blk);
         if (!d_block || !d_m) throw std::invalid_argument("zero_dm_mean: null device pointer");
         if ((uintptr_t)d_m % 4 || (dtype == RT_DEDISP_F32 && (uintptr_t)d_block % 4))
             throw std::invalid_argument("zero_dm_mean: misaligned device pointer");
         ck(launch_zero_dm_mean(d_block, dtype, (uint32_t)nsamp_blk, (uint32_t)nchans, d_mask, d_m,
-                               (hipStream_t)stream),
+                               (hipStream_t)stream, dc.get()),
            "zero_dm_mean");
+        return RT_OK;
+    });
+}
+
+int rt_block_stats_workspace_bytes(size_t nsamp_blk, size_t nchans, size_t block_len, size_t* bytes)
+{
+    return guarded([&] {
+        if (!bytes) throw std::invalid_argument("block_stats: bytes is NULL");
+        chanstats_check_shape(RT_DEDISP_F32, nsamp_blk, nchans);
+        *bytes = (size_t)blockstats_workspace_bytes(nsamp_blk, nchans, blockstats_block_len(nsamp_blk, block_len));
+        return RT_OK;
+    });
+}
+
+int rt_block_stats_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans, size_t block_len,
+                          double* d_stats, void* d_ws, size_t ws_bytes, void* stream)
+{
+    return guarded([&] {
+        chanstats_check_shape(dtype, nsamp_blk, nchans);
+        const size_t blen = blockstats_block_len(nsamp_blk, block_len);
+        const uint64_t need = blockstats_workspace_bytes(nsamp_blk, nchans, blen);
+        if (!d_block || !d_stats || (need && !d_ws)) throw std::invalid_argument("block_stats: null device pointer");
+        if ((uintptr_t)d_stats % 8 || (uintptr_t)d_ws % 8 || (dtype == RT_DEDISP_F32 && (uintptr_t)d_block % 4))
+            throw std::invalid_argument("block_stats: misaligned device pointer");
+        if (ws_bytes < need) throw std::invalid_argument("workspace too small");
+        ck(launch_block_stats(d_block, dtype, (uint32_t)nsamp_blk, (uint32_t)nchans, (uint32_t)blen, d_stats, d_ws,
+                              (hipStream_t)stream),
+           "block_stats");
         return RT_OK;
     });
 }

@@ -6,6 +6,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -100,6 +101,72 @@ void channel_stats(const T* x, size_t nsamp, size_t nchans, double* acc)
             acc[c] += v;
             acc[nchans + c] += v * v;
         }
+}
+
+// The block statistics (riptide_amd.h, rt_block_stats_host): stats [nblk, 2,
+// nchans], per block of block_len rows the sum and the sum of squares, in the
+// float64 order the header states -- chunks of kStatsChunk rows from the
+// block's first row, four interleaved partial sums per chunk from 0.0 added as
+// ((p0 + p1) + p2) + p3, the chunks added in order from 0.0.  Integer samples
+// give exact integers in any order.
+constexpr size_t kStatsChunk = 2048;
+
+template <class T>
+void block_stats(const T* x, size_t nsamp, size_t nchans, size_t block_len, double* stats)
+{
+    size_t b = 0;
+    for (size_t start = 0; start < nsamp; ++b) {
+        const size_t stop = block_len > nsamp - start ? nsamp : start + block_len;
+        for (size_t c = 0; c < nchans; ++c) {
+            double s = 0.0, q = 0.0;
+            for (size_t t0 = start; t0 < stop; t0 += kStatsChunk) {
+                const size_t t1 = kStatsChunk > stop - t0 ? stop : t0 + kStatsChunk;
+                double ps[4] = {0.0, 0.0, 0.0, 0.0}, pq[4] = {0.0, 0.0, 0.0, 0.0};
+                for (size_t t = t0; t < t1; ++t) {
+                    const double v = (double)x[t * nchans + c];
+                    ps[(t - t0) & 3] += v;
+                    pq[(t - t0) & 3] += v * v;
+                }
+                s += ((ps[0] + ps[1]) + ps[2]) + ps[3];
+                q += ((pq[0] + pq[1]) + pq[2]) + pq[3];
+            }
+            stats[(b * 2) * nchans + c] = s;
+            stats[(b * 2 + 1) * nchans + c] = q;
+        }
+        start = stop;
+    }
+}
+
+// The replacement of a block mask (riptide_amd.h, rt_block_replace_host): out
+// is x with every flagged cell's sample set to its channel's fill, in x's own
+// format.  out may be x.
+void block_replace(const void* x, int dtype, size_t nsamp, size_t nchans, const rt_block_mask* bm, void* out)
+{
+    const size_t rb = dedisp_row_bytes(dtype, nchans);
+    if (out != x) std::memcpy(out, x, nsamp * rb);
+    if (!bm) return;
+    const int nbits = dedisp_packed_bits(dtype);
+    const size_t esize = dedisp_fill_bytes(dtype);
+    const uint8_t* fill = (const uint8_t*)bm->fill;
+    for (size_t t = 0; t < nsamp; ++t) {
+        const uint8_t* flags = bm->cells + (size_t)((bm->t_origin + t) / bm->block_len) * nchans;
+        uint8_t* row = (uint8_t*)out + t * rb;
+        for (size_t c = 0; c < nchans; ++c) {
+            if (!flags[c]) continue;
+            if (nbits == 16) {   // the fill is a uint16 of the host, the row little-endian
+                uint16_t v;
+                std::memcpy(&v, fill + 2 * c, 2);
+                row[2 * c] = (uint8_t)(v & 0xFFu);
+                row[2 * c + 1] = (uint8_t)(v >> 8);
+            } else if (nbits) {   // the low nbits bits of the fill's byte into the channel's field
+                const size_t bit = c * (size_t)nbits;
+                const unsigned field = (1u << nbits) - 1u, sh = (unsigned)(bit & 7);
+                row[bit >> 3] = (uint8_t)((row[bit >> 3] & ~(field << sh)) | ((fill[c] & field) << sh));
+            } else {
+                std::memcpy(row + c * esize, fill + c * esize, esize);
+            }
+        }
+    }
 }
 
 // ---- the sample types (dedisp_types.hpp; riptide_amd.h, RT_DEDISP_U8 .. RT_DEDISP_U16)
@@ -259,6 +326,30 @@ int rt_channel_stats_host(const void* x, int dtype, size_t nsamp, size_t nchans,
         if (!nsamp) return RT_OK;
         if (!x) throw std::invalid_argument("channel_stats: null buffer");
         with_samples(x, dtype, nsamp, nchans, [&](const auto* v) { channel_stats(v, nsamp, nchans, acc); });
+        return RT_OK;
+    });
+}
+
+int rt_block_replace_host(const void* x, int dtype, size_t nsamp, size_t nchans, const rt_block_mask* bm, void* out)
+{
+    return guarded([&] {
+        dedisp_check_dtype(dtype, nchans, false, "block_mask");
+        dedisp_check_block_mask(bm, nsamp);
+        if (!nsamp) return RT_OK;
+        if (!x || !out) throw std::invalid_argument("block_mask: null buffer");
+        block_replace(x, dtype, nsamp, nchans, bm, out);
+        return RT_OK;
+    });
+}
+
+int rt_block_stats_host(const void* x, int dtype, size_t nsamp, size_t nchans, size_t block_len, double* stats)
+{
+    return guarded([&] {
+        dedisp_check_dtype(dtype, nchans, false, "block_stats");   // the statistics have no channel cap
+        if (!block_len) throw std::invalid_argument("block_stats: block_len must be at least 1");
+        if (!nsamp) return RT_OK;
+        if (!x || !stats) throw std::invalid_argument("block_stats: null buffer");
+        with_samples(x, dtype, nsamp, nchans, [&](const auto* v) { block_stats(v, nsamp, nchans, block_len, stats); });
         return RT_OK;
     });
 }

@@ -32,6 +32,15 @@
 //   dedisp_chanstats*_kernel  per-channel sum and sum of squares: partial sums
 //                             per chunk of time, folded in chunk order (no
 //                             atomics: the same bits every time)
+//   dedisp_blockstats*_kernel the same sums per (block of block_len time
+//                             samples, channel): rt_block_stats_device
+//   Cells = DdCells           the block mask (rt_block_mask, riptide_amd.h) as
+//                             the last template argument of every kernel that
+//                             reads the time-major block: a flagged cell's
+//                             sample is replaced by its channel's fill as it
+//                             is read.  Cells = DdNoCells (empty, the default)
+//                             is the plain kernel: every masked statement is
+//                             under `if constexpr`
 //
 // No load leaves its buffer: the transpose reads x only at t < nsamp, the
 // staging loads are clamped to the row's padded pitch inside the workspace,
@@ -71,21 +80,88 @@ struct DdSpan {
     static constexpr uint32_t dwords = sizeof(T) == 1 ? 264 : 520;
 };
 
+// ---- the block mask (rt_block_mask, riptide_amd.h)
+// Which samples a kernel reading the time-major block replaces, its last
+// argument, as Sel is dedisp_sum_kernel's.  DdNoCells (empty: the plain call)
+// replaces nothing.  DdCells: sample (t, c) of the block is fill[c] where
+// cells[(t_origin + t) / block_len, c] is not zero; the caller has checked
+// that every row t < nsamp lies in a block below nblocks
+// (rt_dedisperse_device_cells), and no kernel looks a cell up for any other
+// row or for a channel at or past nchans.  fill holds one value per channel in
+// the sample's own type (dedisp_fill_bytes).
+struct DdNoCells {};
+using DdCells = DedispCells;   // kernels.hpp: cells, fill, t_origin, block_len
+
+template <class Cells>
+constexpr bool kDdMasked = !std::is_same<Cells, DdNoCells>::value;
+
+// The flag of one channel along the rows of a tile, held in a register: rows
+// are asked for in ascending order, and the flag is loaded again only when a
+// row lies past the block it was loaded for -- a load per block the tile
+// touches, not per sample.  `first` is the absolute sample of tile row 0.
+struct DdCellFlag {
+    const uint8_t* col;   // cells + c
+    uint64_t first;
+    uint32_t nchans;
+    uint64_t block_len;
+    uint32_t end = 0;     // first tile row past the block `flag` is of (0: nothing loaded)
+    uint32_t flag = 0;
+    __device__ inline DdCellFlag(const DdCells& k, uint64_t t0, uint32_t c, uint32_t nch)
+        : col(k.cells + c), first(k.t_origin + t0), nchans(nch), block_len(k.block_len)
+    {
+    }
+    __device__ inline bool at(uint32_t i)
+    {
+        if (i >= end) {
+            const uint64_t blk = (first + i) / block_len;
+            const uint64_t e = (blk + 1) * block_len - first;   // > i
+            end = (uint32_t)min(e, (uint64_t)0xFFFFFFFFu);
+            flag = col[blk * nchans];
+        }
+        return flag != 0;
+    }
+};
+
+// A lane's state of the mask along a tile's rows in a kernel's one load loop:
+// State (DdCellFlag, DdPackedCells) with a mask, nothing without one, so the
+// loop holds a single masked statement under `if constexpr`.
+struct DdNoState {
+    template <class... A>
+    __device__ inline DdNoState(const A&...)
+    {
+    }
+};
+template <class Cells, class State>
+using DdStateOf = typename std::conditional<kDdMasked<Cells>, State, DdNoState>::type;
+
 // 8-bit: tile of 64 channels x 256 samples, read a byte per lane along the
-// channels, written a dword per lane along time.
+// channels, written a dword per lane along time.  A tile row has one t for
+// the whole wave and a lane one channel for all rows: the masked form keeps
+// the lane's fill (biased as the samples are) and its cell in registers.
+template <class Cells = DdNoCells>
 __global__ __launch_bounds__(kDdThreads) void dedisp_transpose8_kernel(
     const uint8_t* __restrict__ x, uint32_t nsamp, uint32_t nchans, uint8_t* __restrict__ ws, uint64_t pitch,
-    uint32_t flip)
+    uint32_t flip, Cells cells)
 {
     __shared__ __attribute__((aligned(16))) uint8_t tile[64][260];
     const uint32_t tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const uint64_t t0 = (uint64_t)blockIdx.x * 256;
     const uint32_t c0 = blockIdx.y * 64;
     const uint32_t c = c0 + tx;
+    [[maybe_unused]] DdStateOf<Cells, DdCellFlag> cf(cells, t0, c, nchans);
+    [[maybe_unused]] uint32_t fv = 0;
+    if constexpr (kDdMasked<Cells>) {
+        if (c < nchans) fv = (uint32_t)static_cast<const uint8_t*>(cells.fill)[c] ^ flip;
+    }
     for (uint32_t i = ty; i < 256; i += 4) {
         const uint64_t t = t0 + i;
         uint32_t v = 0;
-        if (c < nchans && t < nsamp) v = x[t * nchans + c] ^ flip;
+        if (c < nchans && t < nsamp) {
+            v = x[t * nchans + c] ^ flip;
+            if constexpr (kDdMasked<Cells>) {
+                if (cf.at(i)) v = fv;
+            }
+        }
         tile[tx][i] = (uint8_t)v;
     }
     __syncthreads();
@@ -136,6 +212,61 @@ struct DdRow<DdBits<NBITS>> {
     }
 };
 
+// (fill pointer of a block mask, c) -> the channel's fill as DdRow<T>::get
+// returns a sample: T itself for the plain types, for packed rows the low
+// NBITS bits of a byte (1/2/4 bit) or a uint16
+template <class T>
+struct DdFill {
+    static __device__ inline T get(const void* fill, uint32_t c) { return static_cast<const T*>(fill)[c]; }
+};
+template <int NBITS>
+struct DdFill<DdBits<NBITS>> {
+    static __device__ inline uint32_t get(const void* fill, uint32_t c)
+    {
+        if constexpr (NBITS == 16) return static_cast<const uint16_t*>(fill)[c];
+        else return static_cast<const uint8_t*>(fill)[c] & ((1u << NBITS) - 1u);
+    }
+};
+
+// The cells of the nb packed bytes from byte b of a row (nb * 8 / NBITS
+// channels, nb = 1 or 4: what a lane of dedisp_unpack_transpose_kernel loads
+// at once), as bits in the packed word itself: `fillw` is the fills of those
+// channels packed as the samples are, `selw` has every bit of a flagged
+// channel's field set, so the replacement of all the word's channels is
+//   (w & ~selw) | (fillw & selw)
+// -- replacing after unpacking, channel by channel, gives the same bits.  selw
+// is loaded again only when a row lies past the block it was loaded for.  A
+// byte below row_bytes holds channels below nchans only (rows are whole bytes).
+template <int NBITS>
+struct DdPackedCells {
+    static constexpr uint32_t kPer = 8 / NBITS;
+    static constexpr uint32_t kField = (1u << NBITS) - 1u;
+    const uint8_t* col;   // cells + the word's first channel
+    uint64_t first, block_len;
+    uint32_t nchans, nch;   // nch: channels of the word
+    uint32_t end = 0, fillw = 0, selw = 0;
+    __device__ inline DdPackedCells(const DdCells& k, uint64_t t0, uint32_t b, uint32_t nb, uint32_t nchans_)
+        : col(k.cells + (uint64_t)b * kPer), first(k.t_origin + t0), block_len(k.block_len), nchans(nchans_),
+          nch(nb * kPer)
+    {
+        const uint8_t* f = static_cast<const uint8_t*>(k.fill) + (uint64_t)b * kPer;
+        for (uint32_t j = 0; j < nch; ++j) fillw |= ((uint32_t)f[j] & kField) << (j * NBITS);
+    }
+    __device__ inline uint32_t replace(uint32_t w, uint32_t i)
+    {
+        if (i >= end) {
+            const uint64_t blk = (first + i) / block_len;
+            const uint64_t e = (blk + 1) * block_len - first;   // > i
+            end = (uint32_t)min(e, (uint64_t)0xFFFFFFFFu);
+            const uint8_t* row = col + blk * nchans;
+            selw = 0;
+            for (uint32_t j = 0; j < nch; ++j)
+                if (row[j]) selw |= kField << (j * NBITS);
+        }
+        return (w & ~selw) | (fillw & selw);
+    }
+};
+
 // 1/2/4 bit: packed rows to the 8-bit workspace rows dedisp_transpose8_kernel
 // writes, the values unbiased, for dedisp_sum_kernel<uint8_t> with bias 0.
 // Tile of 64 packed bytes x 256 samples, that is 512, 256 or 128 channels: a
@@ -150,10 +281,13 @@ struct DdRow<DdBits<NBITS>> {
 // loads otherwise.  A load touches byte b < row_bytes of a row t < nsamp only
 // (the dword path: b + 3 < row_bytes, both multiples of 4), nothing at or
 // beyond nsamp * row_bytes.
-template <int NBITS>
+// The masked form replaces in the packed word as it is loaded (DdPackedCells),
+// where a lane keeps its bytes -- its channels -- across rows; the tile then
+// holds x' and the rest of the kernel is the plain one.
+template <int NBITS, class Cells = DdNoCells>
 __global__ __launch_bounds__(kDdThreads) void dedisp_unpack_transpose_kernel(
     const uint8_t* __restrict__ x, uint32_t nsamp, uint32_t nchans, uint32_t row_bytes, uint8_t* __restrict__ ws,
-    uint64_t pitch, uint32_t dwords)
+    uint64_t pitch, uint32_t dwords, Cells cells)
 {
     constexpr uint32_t kPer = 8 / NBITS;                              // channels of a packed byte
     constexpr uint32_t kMask = ((1u << NBITS) - 1u) * 0x01010101u;    // the low field of each of four bytes
@@ -164,10 +298,14 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_unpack_transpose_kernel(
     if (dwords) {   // uniform over the grid
         const uint32_t j = tx & 15, r = tx >> 4;
         const uint32_t b = b0 + 4 * j;
+        [[maybe_unused]] DdStateOf<Cells, DdPackedCells<NBITS>> pc(cells, t0, b, b < row_bytes ? 4u : 0u, nchans);
         for (uint32_t i = ty * 4 + r; i < 256; i += 16) {
             const uint64_t t = t0 + i;
             uint32_t v = 0;
-            if (b < row_bytes && t < nsamp) v = *reinterpret_cast<const uint32_t*>(x + t * row_bytes + b);
+            if (b < row_bytes && t < nsamp) {
+                v = *reinterpret_cast<const uint32_t*>(x + t * row_bytes + b);
+                if constexpr (kDdMasked<Cells>) v = pc.replace(v, i);
+            }
             tile[4 * j][i] = (uint8_t)v;
             tile[4 * j + 1][i] = (uint8_t)(v >> 8);
             tile[4 * j + 2][i] = (uint8_t)(v >> 16);
@@ -175,10 +313,14 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_unpack_transpose_kernel(
         }
     } else {
         const uint32_t b = b0 + tx;
+        [[maybe_unused]] DdStateOf<Cells, DdPackedCells<NBITS>> pc(cells, t0, b, b < row_bytes ? 1u : 0u, nchans);
         for (uint32_t i = ty; i < 256; i += 4) {
             const uint64_t t = t0 + i;
             uint32_t v = 0;
-            if (b < row_bytes && t < nsamp) v = x[t * row_bytes + b];
+            if (b < row_bytes && t < nsamp) {
+                v = x[t * row_bytes + b];
+                if constexpr (kDdMasked<Cells>) v = pc.replace(v, i);
+            }
             tile[tx][i] = (uint8_t)v;
         }
     }
@@ -199,17 +341,30 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_unpack_transpose_kernel(
 }
 
 // float: tile of 64 channels x 64 samples.
+template <class Cells = DdNoCells>
 __global__ __launch_bounds__(kDdThreads) void dedisp_transpose32_kernel(
-    const float* __restrict__ x, uint32_t nsamp, uint32_t nchans, float* __restrict__ ws, uint64_t pitch)
+    const float* __restrict__ x, uint32_t nsamp, uint32_t nchans, float* __restrict__ ws, uint64_t pitch, Cells cells)
 {
     __shared__ float tile[64][65];
     const uint32_t tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const uint64_t t0 = (uint64_t)blockIdx.x * 64;
     const uint32_t c0 = blockIdx.y * 64;
     const uint32_t c = c0 + tx;
+    [[maybe_unused]] DdStateOf<Cells, DdCellFlag> cf(cells, t0, c, nchans);
+    [[maybe_unused]] float fv = 0.0f;
+    if constexpr (kDdMasked<Cells>) {
+        if (c < nchans) fv = static_cast<const float*>(cells.fill)[c];
+    }
     for (uint32_t i = ty; i < 64; i += 4) {
         const uint64_t t = t0 + i;
-        tile[tx][i] = (c < nchans && t < nsamp) ? x[t * nchans + c] : 0.0f;
+        float v = 0.0f;
+        if (c < nchans && t < nsamp) {
+            v = x[t * nchans + c];
+            if constexpr (kDdMasked<Cells>) {
+                if (cf.at(i)) v = fv;
+            }
+        }
+        tile[tx][i] = v;
     }
     __syncthreads();
     const uint64_t t = t0 + tx;
@@ -238,15 +393,56 @@ __device__ inline float dd_value(T v)
 // lane holds the same total, summed in an order that depends on nchans alone.
 // Packed rows are read through DdRow: 1/2/4 bit in int32 (at most 65793 * 15),
 // 16 bit in float64 (integers below 2^16 * 2^22 channels: exact).
-template <class T>
+// The masked form sums x' in the same order: a lane still adds its channels
+// lane, lane + 64, ... of a row one after the other and the butterfly is the
+// same, so it gives the bits the plain kernel gives on a block holding x'.
+// Only the loops are exchanged -- the wave's four rows inside the channel
+// loop, a sum per row -- so that a lane loads its channel's fill once and the
+// cell once per block the four rows touch.
+template <class T, class Cells = DdNoCells>
 __global__ __launch_bounds__(kDdThreads) void dedisp_rowmean_kernel(
     const T* __restrict__ x, uint32_t nsamp, uint32_t nchans, const uint8_t* __restrict__ mask,
-    float* __restrict__ m)
+    float* __restrict__ m, Cells cells)
 {
     using R = DdRow<T>;
     using Acc = typename std::conditional<R::kIntSums, int32_t, double>::type;
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t t0 = (uint64_t)blockIdx.x * kRmRowsPerWg + wave * kRmRows;
+    if constexpr (kDdMasked<Cells>) {
+        if (t0 >= nsamp) return;   // wave-uniform
+        const uint32_t nr = (uint32_t)min((uint64_t)kRmRows, nsamp - t0);
+        uint64_t blk[kRmRows];
+#pragma unroll
+        for (uint32_t r = 0; r < kRmRows; ++r) blk[r] = (cells.t_origin + t0 + min(r, nr - 1)) / cells.block_len;
+        Acc s[kRmRows];
+#pragma unroll
+        for (uint32_t r = 0; r < kRmRows; ++r) s[r] = 0;
+        int32_t nu = 0;
+        for (uint32_t c = lane; c < nchans; c += 64) {
+            if (mask && mask[c]) continue;
+            const auto fv = DdFill<T>::get(cells.fill, c);
+            uint32_t flag = cells.cells[blk[0] * nchans + c];
+#pragma unroll
+            for (uint32_t r = 0; r < kRmRows; ++r) {
+                if (r >= nr) break;
+                if (r && blk[r] != blk[r - 1]) flag = cells.cells[blk[r] * nchans + c];
+                const auto v = R::get(R::at(x, t0 + r, nchans), c);
+                s[r] += flag ? (Acc)fv : (Acc)v;
+            }
+            ++nu;
+        }
+#pragma unroll
+        for (uint32_t r = 0; r < kRmRows; ++r) {
+#pragma unroll
+            for (uint32_t off = 32; off > 0; off >>= 1) s[r] += __shfl_xor(s[r], off, 64);
+        }
+#pragma unroll
+        for (uint32_t off = 32; off > 0; off >>= 1) nu += __shfl_xor(nu, off, 64);
+#pragma unroll
+        for (uint32_t r = 0; r < kRmRows; ++r)
+            if (lane == 0 && r < nr) m[t0 + r] = nu ? (float)((double)s[r] / (double)nu) : 0.0f;
+        return;
+    }
     for (uint32_t r = 0; r < kRmRows; ++r) {
         const uint64_t t = t0 + r;
         if (t >= nsamp) return;   // wave-uniform
@@ -272,16 +468,21 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_rowmean_kernel(
 // floats, its padding (and every t >= nsamp) written as zero.  T may be a
 // packed row type (DdRow); kMean = false is the plain transpose of 16-bit rows
 // to float32 (the values converted exactly, m not read).
-template <class T, bool kMean = true>
+template <class T, bool kMean = true, class Cells = DdNoCells>
 __global__ __launch_bounds__(kDdThreads) void dedisp_transpose_zdm_kernel(
     const T* __restrict__ x, uint32_t nsamp, uint32_t nchans, const float* __restrict__ m, float* __restrict__ ws,
-    uint64_t pitch)
+    uint64_t pitch, Cells cells)
 {
     __shared__ float tile[64][65];
     const uint32_t tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const uint64_t t0 = (uint64_t)blockIdx.x * 64;
     const uint32_t c0 = blockIdx.y * 64;
     const uint32_t c = c0 + tx;
+    [[maybe_unused]] DdStateOf<Cells, DdCellFlag> cf(cells, t0, c, nchans);
+    [[maybe_unused]] float fv = 0.0f;   // the fill as the value it stands for
+    if constexpr (kDdMasked<Cells>) {
+        if (c < nchans) fv = dd_value(DdFill<T>::get(cells.fill, c));
+    }
     for (uint32_t i = ty; i < 64; i += 4) {
         const uint64_t t = t0 + i;
         float v = 0.0f;
@@ -290,6 +491,9 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_transpose_zdm_kernel(
             if constexpr (kMean) mt = m[t];
             if (c < nchans) {
                 v = dd_value(DdRow<T>::get(DdRow<T>::at(x, t, nchans), c));
+                if constexpr (kDdMasked<Cells>) {
+                    if (cf.at(i)) v = fv;
+                }
                 if constexpr (kMean) v = v - mt;
             }
         }
@@ -310,9 +514,13 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_transpose_zdm_kernel(
 // 2^31 / 2^32), float samples in float64.  part is [nchunks, 2, nchans].
 // Packed rows (DdRow): 1/2/4 bit as integers (at most 512 x 15^2), 16 bit in
 // float64 (512 x 65535^2 < 2^41: exact).
+// dd_chunk_stats is the body of both statistics kernels: part[chunk] = those
+// sums over the rows [t0, t1), t1 - t0 <= kCsChunk.  In float64 the order is:
+// wave w adds the rows t0 + w, t0 + w + 4, ... one after the other from 0.0,
+// then ((p0 + p1) + p2) + p3.
 template <class T>
-__global__ __launch_bounds__(kDdThreads) void dedisp_chanstats_kernel(
-    const T* __restrict__ x, uint32_t nsamp, uint32_t nchans, double* __restrict__ part)
+__device__ inline void dd_chunk_stats(const T* __restrict__ x, uint64_t t0, uint64_t t1, uint32_t nchans,
+                                      double* __restrict__ part, uint32_t chunk)
 {
     constexpr bool kBytes = DdRow<T>::kIntSums;
     using Sum = typename std::conditional<kBytes, int32_t, double>::type;
@@ -320,8 +528,6 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_chanstats_kernel(
     __shared__ double red[2][kDdWaves][64];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t c = blockIdx.y * 64 + lane;
-    const uint64_t t0 = (uint64_t)blockIdx.x * kCsChunk;
-    const uint64_t t1 = min(t0 + kCsChunk, (uint64_t)nsamp);
     Sum s = 0;
     Sq q = 0;
     if (c < nchans)
@@ -337,8 +543,48 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_chanstats_kernel(
         double a = red[wave][0][lane];
 #pragma unroll
         for (uint32_t w = 1; w < kDdWaves; ++w) a += red[wave][w][lane];
-        part[((uint64_t)blockIdx.x * 2 + wave) * nchans + c] = a;
+        part[((uint64_t)chunk * 2 + wave) * nchans + c] = a;
     }
+}
+
+// The channel statistics: chunk blockIdx.x of the whole block.
+template <class T>
+__global__ __launch_bounds__(kDdThreads) void dedisp_chanstats_kernel(
+    const T* __restrict__ x, uint32_t nsamp, uint32_t nchans, double* __restrict__ part)
+{
+    const uint64_t t0 = (uint64_t)blockIdx.x * kCsChunk;
+    const uint64_t t1 = min(t0 + kCsChunk, (uint64_t)nsamp);
+    dd_chunk_stats(x, t0, t1, nchans, part, blockIdx.x);
+}
+
+// The same sums per block of block_len time samples, blocks counted from row 0
+// (rt_block_stats_device): workgroup blockIdx.x is chunk k = blockIdx.x % cpb
+// of block b = blockIdx.x / cpb, the rows [b * block_len + k * kCsChunk, + kCsChunk)
+// that lie in the block and below nsamp (none: zeros), cpb = ceil(block_len /
+// kCsChunk).  dst is [nblk * cpb, 2, nchans]: the result itself when cpb == 1,
+// the per-chunk partial sums otherwise.  The integer bounds are the chunk's.
+template <class T>
+__global__ __launch_bounds__(kDdThreads) void dedisp_blockstats_kernel(
+    const T* __restrict__ x, uint32_t nsamp, uint32_t nchans, uint32_t block_len, uint32_t cpb,
+    double* __restrict__ dst)
+{
+    const uint32_t b = blockIdx.x / cpb, k = blockIdx.x - b * cpb;
+    const uint64_t t0 = (uint64_t)b * block_len + (uint64_t)k * kCsChunk;
+    const uint64_t t1 = min(min(t0 + kCsChunk, ((uint64_t)b + 1) * block_len), (uint64_t)nsamp);
+    dd_chunk_stats(x, t0, t1, nchans, dst, blockIdx.x);
+}
+
+// out[b, k, c] = the partial sums of block b's cpb chunks added in chunk order
+// from 0.0 (written, not accumulated): one thread per (b, k, c)
+__global__ __launch_bounds__(kDdThreads) void dedisp_blockstats_fold_kernel(
+    const double* __restrict__ part, uint32_t cpb, uint64_t total, uint32_t nchans, double* __restrict__ out)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * kDdThreads + threadIdx.x;   // (b * 2 + k) * nchans + c
+    if (i >= total) return;
+    const uint64_t b = i / (2ull * nchans), rest = i - b * 2ull * nchans;
+    double a = 0.0;
+    for (uint32_t k = 0; k < cpb; ++k) a += part[(b * cpb + k) * 2ull * nchans + rest];
+    out[i] = a;
 }
 
 // acc[k, c] += the chunks' partial sums, in chunk order: one thread per (k, c)
@@ -542,6 +788,15 @@ void dd_dispatch(int dtype, F f)
     }
 }
 
+// f(cells), cells the last argument of a kernel reading the block: no block
+// mask is DdNoCells, the plain instantiation
+template <class F>
+void dd_cells(const DedispCells* bm, F f)
+{
+    if (bm) f(*bm);
+    else f(DdNoCells{});
+}
+
 }  // namespace
 
 uint64_t dedisp_pitch_bytes(int dtype, uint64_t nsamp_blk)
@@ -558,13 +813,15 @@ uint64_t dedisp_workspace_bytes(int dtype, uint64_t nsamp_blk, uint64_t nchans, 
 }
 
 hipError_t launch_zero_dm_mean(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
-                               const uint8_t* d_mask, float* m, hipStream_t s)
+                               const uint8_t* d_mask, float* m, hipStream_t s, const DedispCells* bm)
 {
     const dim3 grid((nsamp_blk + kRmRowsPerWg - 1) / kRmRowsPerWg);
     dd_dispatch(dtype, [&](auto tag) {
         using T = decltype(tag);
-        hipLaunchKernelGGL(dedisp_rowmean_kernel<T>, grid, dim3(kDdThreads), 0, s, (const T*)block, nsamp_blk, nchans,
-                           d_mask, m);
+        dd_cells(bm, [&](auto cells) {
+            hipLaunchKernelGGL((dedisp_rowmean_kernel<T, decltype(cells)>), grid, dim3(kDdThreads), 0, s,
+                               (const T*)block, nsamp_blk, nchans, d_mask, m, cells);
+        });
     });
     return hipGetLastError();
 }
@@ -590,14 +847,49 @@ hipError_t launch_channel_stats(const void* block, int dtype, uint32_t nsamp_blk
     return hipGetLastError();
 }
 
+// chunks of one block, and of the whole call (the grid's x: the caller keeps it below 2^31)
+uint64_t blockstats_chunks(uint64_t nsamp_blk, uint64_t block_len)
+{
+    const uint64_t cpb = (block_len + kCsChunk - 1) / kCsChunk;
+    return (nsamp_blk + block_len - 1) / block_len * cpb;
+}
+
+uint64_t blockstats_workspace_bytes(uint64_t nsamp_blk, uint64_t nchans, uint64_t block_len)
+{
+    if (block_len <= kCsChunk) return 0;   // a block is one chunk: written in place
+    return blockstats_chunks(nsamp_blk, block_len) * 2 * nchans * sizeof(double);
+}
+
+hipError_t launch_block_stats(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans, uint32_t block_len,
+                              double* stats, void* ws, hipStream_t s)
+{
+    const uint32_t cpb = (uint32_t)(((uint64_t)block_len + kCsChunk - 1) / kCsChunk);
+    const uint32_t nchunks = (uint32_t)blockstats_chunks(nsamp_blk, block_len);
+    const dim3 grid(nchunks, (nchans + 63) / 64);
+    double* dst = cpb == 1 ? stats : (double*)ws;
+    dd_dispatch(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(dedisp_blockstats_kernel<T>, grid, dim3(kDdThreads), 0, s, (const T*)block, nsamp_blk,
+                           nchans, block_len, cpb, dst);
+    });
+    if (cpb > 1) {
+        const uint64_t total = (uint64_t)(nchunks / cpb) * 2 * nchans;
+        hipLaunchKernelGGL(dedisp_blockstats_fold_kernel, dim3((uint32_t)((total + kDdThreads - 1) / kDdThreads)),
+                           dim3(kDdThreads), 0, s, (const double*)ws, cpb, total, nchans, stats);
+    }
+    return hipGetLastError();
+}
+
 // Two steps.  The block goes to channel-major rows in the workspace: float32
 // rows for float and 16-bit data and for every type under the zero-DM filter
 // (x - m, m behind the rows), 8-bit rows otherwise (signed samples biased by
 // 128, 1/2/4-bit samples unpacked).  Then one sum over whichever rows they are.
+// With a block mask the first step's kernels are the DdCells instantiations:
+// the workspace then holds x' (or x' - m), and the sum is the same launch.
 hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
                              const int32_t* d_delays, const uint8_t* d_mask, uint32_t ndm, uint32_t max_delay,
                              float* out, uint64_t out_stride, void* ws, uint32_t flags, hipStream_t s,
-                             const uint32_t* d_bands, uint32_t nbands)
+                             const uint32_t* d_bands, uint32_t nbands, const DedispCells* bm)
 {
     const uint32_t nout = nsamp_blk - max_delay;
     const int nbits = dedisp_packed_bits(dtype);
@@ -610,19 +902,27 @@ hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, u
         const dim3 grid((uint32_t)((pitch + 63) / 64), (nchans + 63) / 64);
         if (zero_dm) {
             float* m = (float*)ws + pitch * nchans;
-            const hipError_t e = launch_zero_dm_mean(block, dtype, nsamp_blk, nchans, d_mask, m, s);
+            const hipError_t e = launch_zero_dm_mean(block, dtype, nsamp_blk, nchans, d_mask, m, s, bm);
             if (e != hipSuccess) return e;
             dd_dispatch(dtype, [&](auto tag) {
                 using T = decltype(tag);
-                hipLaunchKernelGGL(dedisp_transpose_zdm_kernel<T>, grid, dim3(kDdThreads), 0, s, (const T*)block,
-                                   nsamp_blk, nchans, (const float*)m, (float*)ws, pitch);
+                dd_cells(bm, [&](auto cells) {
+                    hipLaunchKernelGGL((dedisp_transpose_zdm_kernel<T, true, decltype(cells)>), grid, dim3(kDdThreads),
+                                       0, s, (const T*)block, nsamp_blk, nchans, (const float*)m, (float*)ws, pitch,
+                                       cells);
+                });
             });
         } else if (nbits == 16) {   // exact float32 values
-            hipLaunchKernelGGL((dedisp_transpose_zdm_kernel<DdBits<16>, false>), grid, dim3(kDdThreads), 0, s,
-                               (const DdBits<16>*)block, nsamp_blk, nchans, (const float*)nullptr, (float*)ws, pitch);
+            dd_cells(bm, [&](auto cells) {
+                hipLaunchKernelGGL((dedisp_transpose_zdm_kernel<DdBits<16>, false, decltype(cells)>), grid,
+                                   dim3(kDdThreads), 0, s, (const DdBits<16>*)block, nsamp_blk, nchans,
+                                   (const float*)nullptr, (float*)ws, pitch, cells);
+            });
         } else {
-            hipLaunchKernelGGL(dedisp_transpose32_kernel, grid, dim3(kDdThreads), 0, s, (const float*)block, nsamp_blk,
-                               nchans, (float*)ws, pitch);
+            dd_cells(bm, [&](auto cells) {
+                hipLaunchKernelGGL(dedisp_transpose32_kernel<decltype(cells)>, grid, dim3(kDdThreads), 0, s,
+                                   (const float*)block, nsamp_blk, nchans, (float*)ws, pitch, cells);
+            });
         }
         launch_sum(sum_grid, s, (const float*)ws, pitch, nchans, d_delays, d_mask, ndm, max_delay, nout, out, out_stride,
                    0, d_bands, nbands);
@@ -632,17 +932,22 @@ hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, u
             const uint32_t dwords = row_bytes % 4 == 0 && (uintptr_t)block % 4 == 0;
             const dim3 grid((uint32_t)((pitch_bytes + 255) / 256), (row_bytes + 63) / 64);
             const auto unpack = [&](auto tag) {
-                hipLaunchKernelGGL(dedisp_unpack_transpose_kernel<decltype(tag)::kBits>, grid, dim3(kDdThreads), 0, s,
-                                   (const uint8_t*)block, nsamp_blk, nchans, row_bytes, (uint8_t*)ws, pitch_bytes,
-                                   dwords);
+                dd_cells(bm, [&](auto cells) {
+                    hipLaunchKernelGGL((dedisp_unpack_transpose_kernel<decltype(tag)::kBits, decltype(cells)>), grid,
+                                       dim3(kDdThreads), 0, s, (const uint8_t*)block, nsamp_blk, nchans, row_bytes,
+                                       (uint8_t*)ws, pitch_bytes, dwords, cells);
+                });
             };
             if (nbits == 1) unpack(DdBits<1>{});
             else if (nbits == 2) unpack(DdBits<2>{});
             else unpack(DdBits<4>{});
         } else {
             const dim3 grid((uint32_t)((pitch_bytes + 255) / 256), (nchans + 63) / 64);
-            hipLaunchKernelGGL(dedisp_transpose8_kernel, grid, dim3(kDdThreads), 0, s, (const uint8_t*)block, nsamp_blk,
-                               nchans, (uint8_t*)ws, pitch_bytes, dtype == RT_DEDISP_I8 ? 0x80u : 0u);
+            dd_cells(bm, [&](auto cells) {
+                hipLaunchKernelGGL(dedisp_transpose8_kernel<decltype(cells)>, grid, dim3(kDdThreads), 0, s,
+                                   (const uint8_t*)block, nsamp_blk, nchans, (uint8_t*)ws, pitch_bytes,
+                                   dtype == RT_DEDISP_I8 ? 0x80u : 0u, cells);
+            });
         }
         launch_sum(sum_grid, s, (const uint8_t*)ws, pitch_bytes, nchans, d_delays, d_mask, ndm, max_delay, nout, out,
                    out_stride, dtype == RT_DEDISP_I8 ? 128 : 0, d_bands, nbands);

@@ -78,4 +78,30 @@ inline void dedisp_check_band_table(const uint32_t* bands, size_t nbands, size_t
                                         ") is not a channel range lo <= hi <= " + std::to_string(nchans));
 }
 
+// bytes of one channel's fill of a block mask: the sample's own type, for
+// 1/2/4-bit data one unpacked value per byte
+constexpr size_t dedisp_fill_bytes(int dtype)
+{
+    return dtype == RT_DEDISP_F32 ? 4 : dtype == RT_DEDISP_U16 ? 2 : 1;
+}
+
+// a block mask (NULL: none) in front of `nsamp` rows from its t_origin: a block
+// length, both arrays, and every row inside the nblocks * block_len samples the
+// cells cover, so that no load leaves them
+inline void dedisp_check_block_mask(const rt_block_mask* bm, size_t nsamp)
+{
+    if (!bm) return;
+    if (!bm->block_len) throw std::invalid_argument("block_mask: block_len must be at least 1");
+    if (!bm->cells || !bm->fill) throw std::invalid_argument("block_mask: cells or fill is NULL");
+    // t_origin + t is computed in 64 bits everywhere: it must not wrap
+    if (bm->t_origin > UINT64_MAX - nsamp)
+        throw std::invalid_argument("block_mask: t_origin + nsamp overflows 64 bits");
+    const unsigned __int128 covered = (unsigned __int128)bm->nblocks * bm->block_len;
+    if ((unsigned __int128)bm->t_origin + nsamp > covered)
+        throw std::invalid_argument("block_mask: the rows [" + std::to_string(bm->t_origin) + ", " +
+                                    std::to_string(bm->t_origin) + " + " + std::to_string(nsamp) +
+                                    ") reach past the mask's " + std::to_string(bm->nblocks) + " blocks of " +
+                                    std::to_string(bm->block_len) + " samples");
+}
+
 }  // namespace rt

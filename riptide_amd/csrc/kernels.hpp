@@ -101,22 +101,41 @@ uint64_t dedisp_pitch_bytes(int dtype, uint64_t nsamp_blk);
 // bytes of ws for these flags: the rows, with RT_DEDISP_ZERO_DM float rows plus
 // one more pitch for m [nsamp_blk]
 uint64_t dedisp_workspace_bytes(int dtype, uint64_t nsamp_blk, uint64_t nchans, uint32_t flags);
+// A block mask in device memory (rt_block_mask of riptide_amd.h, checked by
+// the caller: every row of the block lies in a block of cells): sample (t, c)
+// is read as fill[c] where cells[(t_origin + t) / block_len, c] != 0; fill is
+// one value per channel in the sample's own type.
+struct DedispCells {
+    const uint8_t* cells;   // [nblocks, nchans]
+    const void* fill;       // [nchans]
+    uint64_t t_origin;
+    uint64_t block_len;
+};
 // d_bands: nullptr, or uint32 [nbands][2] channel ranges [lo, hi) in device
 // memory (clamped to nchans as they are read): out[(d * nbands + b) *
 // out_stride + t] is then the sum over band b alone; nbands <= 65535
 // (RT_DEDISP_MAX_BANDS), a grid layer per band.
+// bm: nullptr (the plain kernels), or a block mask (their DdCells forms).
 hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
                              const int32_t* d_delays, const uint8_t* d_mask, uint32_t ndm, uint32_t max_delay,
                              float* out, uint64_t out_stride, void* ws, uint32_t flags, hipStream_t s,
-                             const uint32_t* d_bands = nullptr, uint32_t nbands = 0);
+                             const uint32_t* d_bands = nullptr, uint32_t nbands = 0,
+                             const DedispCells* bm = nullptr);
 // m[t] = (float32)(sum over unmasked c of block[t, c] / their number), t < nsamp_blk
 hipError_t launch_zero_dm_mean(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
-                               const uint8_t* d_mask, float* m, hipStream_t s);
+                               const uint8_t* d_mask, float* m, hipStream_t s, const DedispCells* bm = nullptr);
 // acc [2, nchans] float64 += the block's per-channel sums and sums of squares;
 // ws: chanstats_workspace_bytes of per-chunk partial sums
 uint64_t chanstats_workspace_bytes(uint64_t nsamp_blk, uint64_t nchans);
 hipError_t launch_channel_stats(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans, double* acc,
                                 void* ws, hipStream_t s);
+// stats [ceil(nsamp_blk / block_len), 2, nchans] float64 = those sums per block
+// of block_len rows (written); ws: blockstats_workspace_bytes (none up to 2048
+// rows a block).  blockstats_chunks: the workgroups along x, below 2^31
+uint64_t blockstats_chunks(uint64_t nsamp_blk, uint64_t block_len);
+uint64_t blockstats_workspace_bytes(uint64_t nsamp_blk, uint64_t nchans, uint64_t block_len);
+hipError_t launch_block_stats(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans, uint32_t block_len,
+                              double* stats, void* ws, hipStream_t s);
 
 // harmonic_kernels.hip
 // One tile of the harmonic pair matrix: rows [i0, i0 + rows) of the n ranked

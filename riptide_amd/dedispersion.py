@@ -239,6 +239,40 @@ def _gulp_layout(fb):
     return fb.nchans, np.dtype(fb.dtype)
 
 
+def _block_mask_bytes(fb, block_mask):
+    """Device bytes of a block mask's cells and fill for this file (0 for None)."""
+    if block_mask is None:
+        return 0
+    nbits = getattr(fb, "nbits", None)
+    esize = 2 if nbits == 16 else 1 if nbits is not None else np.dtype(fb.dtype).itemsize
+    return int(block_mask.cells.size) + int(block_mask.cells.shape[1]) * esize
+
+
+def _upload_block_mask(fb, block_mask, dev, nrows):
+    """A rfi.BlockMask as the engine.DeviceBlockMask of file `fb` on `dev`:
+    the cells as uint8 and the fill in the file's sample type, uploaded once
+    for every gulp of a call that reads rows [0, nrows).  None for None.
+    ValueError when the mask's channel count is not the file's, or its blocks
+    do not cover the rows read."""
+    if block_mask is None:
+        return None
+    import torch
+    from . import engine
+    cells = np.asarray(block_mask.cells)
+    if cells.ndim != 2 or cells.shape[1] != fb.nchans:
+        raise ValueError(f"the block mask has {cells.shape[1] if cells.ndim == 2 else '?'} channels, the file "
+                         f"{fb.nchans}")
+    block_len = int(block_mask.block_len)
+    if block_len < 1:
+        raise ValueError("block_mask: block_len must be at least 1")
+    if cells.shape[0] * block_len < nrows:
+        raise ValueError(f"the block mask covers {cells.shape[0]} blocks of {block_len} samples, fewer than the "
+                         f"{nrows} samples read")
+    fill = np.ascontiguousarray(block_mask.typed_fill(fb))
+    d_cells = torch.from_numpy(np.ascontiguousarray(cells.astype(bool), dtype=np.uint8)).to(dev)
+    return engine.DeviceBlockMask(d_cells, torch.from_numpy(fill).to(dev), block_len)
+
+
 def stream_gulps(fb, dev, gulp, nrows, overlap, process):
     """Stream rows [0, nrows) of a reading.Filterbank's memory map to `dev` in
     gulps of `gulp` time samples that overlap by `overlap`, through two
@@ -291,7 +325,7 @@ def stream_gulps(fb, dev, gulp, nrows, overlap, process):
 
 
 def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, nout=None,
-                          budget_bytes=DEFAULT_BUDGET_BYTES, zero_dm=False, bands=None):
+                          budget_bytes=DEFAULT_BUDGET_BYTES, zero_dm=False, bands=None, block_mask=None):
     """Dedisperse a reading.Filterbank (or PackedFilterbank: the rows are
     uploaded packed) at the trial DMs into one device tensor
     float32 [ndm, nout], nout = nsamp - max_delay (or a smaller `nout`: the
@@ -313,9 +347,20 @@ def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, n
     from the same single pass over the file (engine.dedisperse_bands_device),
     and the output counted against the budget is ndm * nbands * nout * 4 bytes.
 
+    block_mask (a rfi.BlockMask, from rfi.block_mask(rfi.block_stats(fb))): a
+    mask in time and frequency.  Every sample of a flagged cell is replaced by
+    its channel's fill in the file's sample type as the block is read on the
+    device, in front of everything above (the channel mask, the zero-DM mean,
+    the sums): the result is that of the same call on a file holding the
+    replaced samples (rfi.apply_block_mask_host), bit for bit, and does not
+    depend on gulp.  The cells and the fill are uploaded once and count
+    against the budget.
+
     ValueError -- nothing is launched -- when max_delay >= nsamp, for 8-bit
-    data of more than 65793 channels, and when the output (ndm * nout * 4
-    bytes) plus the gulp buffers exceed budget_bytes: pass fewer DMs per call."""
+    data of more than 65793 channels, for a block mask of another channel
+    count or one that does not cover the rows read, and when the output (ndm *
+    nout * 4 bytes) plus the gulp buffers exceed budget_bytes: pass fewer DMs
+    per call."""
     import torch
     from . import engine
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else
@@ -347,7 +392,7 @@ def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, n
     if bands is not None:
         bands = _checked_bands(bands, nchans)
     out_bytes = ndm * (1 if bands is None else bands.shape[0]) * nout * 4
-    total = out_bytes + 2 * gulp * row_bytes + ws_bytes
+    total = out_bytes + 2 * gulp * row_bytes + ws_bytes + _block_mask_bytes(fb, block_mask)
     if total > int(budget_bytes):
         raise ValueError(f"dedispersing {ndm} DMs needs {total} bytes of device memory ({out_bytes} of output "
                          f"plus the gulp buffers), over the budget of {int(budget_bytes)}: pass fewer DMs per call")
@@ -358,18 +403,19 @@ def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, n
         out = torch.empty((ndm, nout) if bands is None else (ndm, bands.shape[0], nout), dtype=torch.float32,
                           device=dev)
         d_bands = None if bands is None else torch.from_numpy(bands.view(np.int32)).to(dev)
+        d_bm = _upload_block_mask(fb, block_mask, dev, need_in)
 
         def process(block, start):
             # dedisperse_device, or with a table dedisperse_bands_device
             engine._dedisperse_device(block, d_delays, max_delay, d_bands, d_mask, out, start, workspace, None,
-                                      zero_dm, nbits)
+                                      zero_dm, nbits, d_bm, start)
 
         stream_gulps(fb, dev, gulp, need_in, max_delay, process)
     return out
 
 
 def band_series(fb, dms, bands, deredden_params, nout, mask=None, zero_dm=False, kdm=KDM, device=None,
-                budget_bytes=DEFAULT_BUDGET_BYTES):
+                budget_bytes=DEFAULT_BUDGET_BYTES, block_mask=None):
     """The series a candidate's frequency-phase diagnostic is folded from:
     (device tensor float32 [ndm, nbands, nout], bool [nbands]).  The file is
     dedispersed into every band at every DM by one pass
@@ -378,7 +424,7 @@ def band_series(fb, dms, bands, deredden_params, nout, mask=None, zero_dm=False,
     normalised by one batched engine.deredden_normalise call, as the search
     does with a DM trial.  The second result marks the bands with no unmasked
     channel: their rows are left zero and are not normalised (the variance of
-    a constant row is zero)."""
+    a constant row is zero).  block_mask as for dedisperse_filterbank."""
     import torch
     from . import engine
     bands = _checked_bands(bands, fb.nchans)
@@ -386,7 +432,7 @@ def band_series(fb, dms, bands, deredden_params, nout, mask=None, zero_dm=False,
     live = np.ones(fb.nchans, dtype=bool) if mask is None else mask == 0
     empty = np.array([not live[lo:hi].any() for lo, hi in bands], dtype=bool)
     raw = dedisperse_filterbank(fb, dms, mask=mask, device=device, kdm=kdm, nout=nout, budget_bytes=budget_bytes,
-                                zero_dm=zero_dm, bands=bands)
+                                zero_dm=zero_dm, bands=bands, block_mask=block_mask)
     ndm, nbands, nout = raw.shape
     width = int(round(deredden_params["rmed_width"] / fb.tsamp))
     minpts = int(deredden_params["rmed_minpts"])

@@ -214,7 +214,8 @@ class EngineSearcher:
         (8-bit data converted on the device), results in input order."""
         return self.submit_samples(samples, tsamps, metadatas)()
 
-    def search_filterbank(self, fb, dms, mask=None, nout=None, kdm=None, zero_dm=False, pulses=None):
+    def search_filterbank(self, fb, dms, mask=None, nout=None, kdm=None, zero_dm=False, pulses=None,
+                          block_mask=None):
         """Dedisperse a reading.Filterbank or PackedFilterbank at the trial DMs on the device
         (dedispersion.dedisperse_filterbank) and search every series: one peak
         list per DM, in the order given (the __call__ contract).  The series
@@ -226,7 +227,10 @@ class EngineSearcher:
         is the dispersion constant of the delay table (default:
         dedispersion.KDM); `zero_dm` puts the zero-DM filter in front of the
         sum (dedispersion.dedisperse_filterbank; rfi.channel_mask builds a
-        `mask` from the file's channel statistics).
+        `mask` from the file's channel statistics); `block_mask` (a
+        rfi.BlockMask, from rfi.block_mask(rfi.block_stats(fb))) replaces the
+        samples of its flagged (time block, channel) cells by the channel's
+        fill as the file is read.
 
         pulses: None, or a dict of single_pulse.search_pulses parameters
         (widths, threshold, radius, time_radius, dm_gap, max_events): every
@@ -240,13 +244,14 @@ class EngineSearcher:
         kdm = KDM if kdm is None else float(kdm)
         dms = [float(d) for d in dms]
         if pulses is not None:
-            return self._search_filterbank_pulses(fb, dms, mask, nout, kdm, zero_dm, dict(pulses))
+            return self._search_filterbank_pulses(fb, dms, mask, nout, kdm, zero_dm, dict(pulses), block_mask)
         if not dms:
             return []
         dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else
                            (self.device.index if isinstance(self.device, torch.device) else int(self.device)))
         with torch.cuda.device(dev):
-            series = dedisperse_filterbank(fb, dms, mask=mask, device=dev, nout=nout, kdm=kdm, zero_dm=zero_dm)
+            series = dedisperse_filterbank(fb, dms, mask=mask, device=dev, nout=nout, kdm=kdm, zero_dm=zero_dm,
+                                           block_mask=block_mask)
             metas = [fb.metadata(dm) for dm in dms]
             slices = [(b0, min(b0 + self.batch, len(dms))) for b0 in range(0, len(dms), self.batch)]
             per, pending = [], None
@@ -258,7 +263,7 @@ class EngineSearcher:
             per.extend(self._detect(pending))
         return per
 
-    def _search_filterbank_pulses(self, fb, dms, mask, nout, kdm, zero_dm, kw):
+    def _search_filterbank_pulses(self, fb, dms, mask, nout, kdm, zero_dm, kw, block_mask=None):
         """search_filterbank with the single-pulse search beside the
         periodicity search: the same calls in the same order, and each slice's
         normalised series handed to engine.single_pulse_device as well."""
@@ -274,7 +279,8 @@ class EngineSearcher:
         dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else
                            (self.device.index if isinstance(self.device, torch.device) else int(self.device)))
         with torch.cuda.device(dev):
-            series = dedisperse_filterbank(fb, dms, mask=mask, device=dev, nout=nout, kdm=kdm, zero_dm=zero_dm)
+            series = dedisperse_filterbank(fb, dms, mask=mask, device=dev, nout=nout, kdm=kdm, zero_dm=zero_dm,
+                                           block_mask=block_mask)
             widths = single_pulse._default_widths(kw.get("widths"), series.shape[1])
             metas = [fb.metadata(dm) for dm in dms]
             slices = [(b0, min(b0 + self.batch, len(dms))) for b0 in range(0, len(dms), self.batch)]
@@ -360,7 +366,8 @@ def search_files(fnames, pool, group=None, chunksize=None):
     return _gather_tagged(tagged, group, world)
 
 
-def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=None, zero_dm=False, pulses=None):
+def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=None, zero_dm=False, pulses=None,
+                      block_mask=None):
     """Search a channelised SIGPROC file (a file name, opened by
     reading.open_filterbank: 1-, 2-, 4-, 8-, 16- or 32-bit samples; or a
     Filterbank / PackedFilterbank) at the trial DMs without leaving the
@@ -373,7 +380,9 @@ def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=Non
     list's largest delay, so the result does not depend on the sharding.
     `kdm` is the dispersion constant of the delay table, on every rank
     (default: dedispersion.KDM); `zero_dm` subtracts every time sample's mean
-    over the unmasked channels before the sum (the zero-DM filter).
+    over the unmasked channels before the sum (the zero-DM filter);
+    `block_mask` (a rfi.BlockMask) replaces the samples of its flagged (time
+    block, channel) cells by the channel's fill in front of both.
 
     pulses: None, or a dict of single_pulse.search_pulses parameters: every
     rank then also runs the single-pulse search on its normalised series
@@ -397,6 +406,8 @@ def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=Non
         extra = {"zero_dm": True} if zero_dm else {}
         if pulses is not None:
             extra["pulses"] = pulses
+        if block_mask is not None:    # as zero_dm: only when set
+            extra["block_mask"] = block_mask
         local = searcher.search_filterbank(fb, [dms[i] for i in mine], mask=mask, nout=fb.nsamp - max_delay,
                                           kdm=kdm, **extra)
         if pulses is not None:

@@ -507,17 +507,66 @@ def _check_device_mask(mask, block, nchans):
         raise ValueError("mask must be a contiguous uint8 [nchans] tensor on the block's device")
 
 
-def zero_dm_mean_device(block, mask=None, out=None, stream=None, nbits=None):
+# dtype names a block mask's fill may have, by sample type name: the sample's
+# own type (include/riptide_amd.h, rt_block_mask); 1/2/4-bit data takes one
+# unpacked value per byte, 16-bit data uint16 (or int16 holding the same bits)
+_FILL_DTYPES = {"uint8": ("uint8",), "int8": ("int8",), "float32": ("float32",), "u1": ("uint8",), "u2": ("uint8",),
+                "u4": ("uint8",), "u16": ("uint16", "int16")}
+
+
+class DeviceBlockMask:
+    """A block mask in device memory, the block_mask= argument of
+    dedisperse_device, dedisperse_bands_device and zero_dm_mean_device
+    (rt_block_mask in include/riptide_amd.h): `cells` uint8 [nblocks, nchans],
+    non-zero = the channel is flagged during block b, the absolute samples
+    [b * block_len, (b + 1) * block_len); `fill` [nchans] in the sample's own
+    type (uint8 for uint8 and 1/2/4-bit data, int8, float32, uint16); the int
+    `block_len`.  A holder: the calls validate it against their block."""
+
+    def __init__(self, cells, fill, block_len):
+        self.cells, self.fill, self.block_len = cells, fill, int(block_len)
+
+    def __repr__(self):
+        return f"DeviceBlockMask(cells={tuple(self.cells.shape)}, block_len={self.block_len})"
+
+
+def _block_mask_struct(block_mask, t_origin, block, name, nchans):
+    """The rt_block_mask of a block_mask= argument, validated the way
+    _check_device_mask validates a channel mask; None for None.  Whether the
+    rows lie inside the mask is the entry point's check."""
+    import torch
+    if block_mask is None:
+        return None
+    cells, fill, block_len = block_mask.cells, block_mask.fill, int(block_mask.block_len)
+    if block_len < 1:
+        raise ValueError("block_mask: block_len must be at least 1")
+    if not 0 <= int(t_origin) < 1 << 64:
+        raise ValueError("t_origin must be in [0, 2^64)")
+    if (not torch.is_tensor(cells) or cells.dtype != torch.uint8 or cells.device != block.device or cells.dim() != 2
+            or not cells.is_contiguous() or cells.shape[1] != nchans):
+        raise ValueError(f"block_mask.cells must be a contiguous uint8 [nblocks, {nchans}] tensor on the block's "
+                         "device")
+    wanted = _FILL_DTYPES[name]
+    if (not torch.is_tensor(fill) or str(fill.dtype).replace("torch.", "") not in wanted
+            or fill.device != block.device or not fill.is_contiguous() or tuple(fill.shape) != (nchans,)):
+        raise ValueError(f"block_mask.fill must be a contiguous {wanted[0]} [{nchans}] tensor on the block's device: "
+                         "one value per channel in the sample's own type")
+    return _lib.BlockMaskStruct(cells.data_ptr(), cells.shape[0], block_len, int(t_origin), fill.data_ptr())
+
+
+def zero_dm_mean_device(block, mask=None, out=None, stream=None, nbits=None, block_mask=None, t_origin=0):
     """The zero-DM time series of one resident block (rt_zero_dm_mean_device,
     the row-mean kernel alone): float32 [nsamp_blk], every time sample's mean
     over the unmasked channels -- the sum exact for 8-bit data, in float64 for
     float32 data, divided in float64 and rounded to float32 once; all zero
-    when every channel is masked.  block, mask and nbits as for
-    dedisperse_device (packed sums are exact integers too).
+    when every channel is masked.  block, mask, nbits, block_mask and t_origin
+    as for dedisperse_device (packed sums are exact integers too): with a block
+    mask the series is that of x', the bits of the plain call on x'.
     Stream-ordered, no host synchronisation."""
     import torch
     name, nsamp_blk, nchans = _dedisp_block(block, nbits)
     _check_device_mask(mask, block, nchans)
+    bm = _block_mask_struct(block_mask, t_origin, block, name, nchans)
     s = stream if stream is not None else torch.cuda.current_stream(block.device)
     with torch.cuda.device(block.device), torch.cuda.stream(s):
         if out is None:
@@ -526,9 +575,55 @@ def zero_dm_mean_device(block, mask=None, out=None, stream=None, nbits=None):
               or tuple(out.shape) != (nsamp_blk,)):
             raise ValueError(f"out must be a contiguous float32 [{nsamp_blk}] tensor on the block's device")
         if nsamp_blk:
-            _check(_L.rt_zero_dm_mean_device(_lib.ptr(block), DEDISP_DTYPES[name], nsamp_blk, nchans,
-                                             None if mask is None else _lib.ptr(mask), _lib.ptr(out),
-                                             _stream_handle(s)))
+            args = (_lib.ptr(block), DEDISP_DTYPES[name], nsamp_blk, nchans, None if mask is None else _lib.ptr(mask),
+                    _lib.ptr(out), _stream_handle(s))
+            if bm is None:
+                _check(_L.rt_zero_dm_mean_device(*args))
+            else:
+                _check(_L.rt_zero_dm_mean_device_cells(*args, ctypes.byref(bm)))
+    return out
+
+
+def block_stats_workspace_bytes(nsamp_blk, nchans, block_len):
+    """Device workspace bytes of block_stats_device for a block of this shape
+    (none for block_len <= 2048)."""
+    b = ctypes.c_size_t()
+    _check(_L.rt_block_stats_workspace_bytes(int(nsamp_blk), int(nchans), int(block_len), ctypes.byref(b)))
+    return b.value
+
+
+def block_stats_device(block, block_len, out=None, workspace=None, stream=None, nbits=None):
+    """Per (block of block_len time samples, channel) sum and sum of squares of
+    one resident block (rt_block_stats_device): float64 [nblk, 2, nchans] on
+    the block's device, nblk = ceil(nsamp_blk / block_len), blocks counted from
+    the block's row 0, the last one possibly partial; written, not added.
+    Integer samples give exact integers; float32 sums follow the fixed order of
+    rt_block_stats_host and equal it bit for bit.  No atomics: the same bits
+    every time.  block and nbits as for dedisperse_device.  Stream-ordered, no
+    host synchronisation.  Returns out."""
+    import torch
+    name, nsamp_blk, nchans = _dedisp_block(block, nbits)
+    block_len = int(block_len)
+    if block_len < 1:
+        raise ValueError("block_stats: block_len must be at least 1")
+    nblk = -(-nsamp_blk // block_len)
+    s = stream if stream is not None else torch.cuda.current_stream(block.device)
+    with torch.cuda.device(block.device), torch.cuda.stream(s):
+        if out is None:
+            out = torch.empty((nblk, 2, nchans), dtype=torch.float64, device=block.device)
+        elif (out.dtype != torch.float64 or out.device != block.device or not out.is_contiguous()
+              or tuple(out.shape) != (nblk, 2, nchans)):
+            raise ValueError(f"out must be a contiguous float64 [{nblk}, 2, {nchans}] tensor on the block's device")
+        if not nsamp_blk:
+            return out
+        need = block_stats_workspace_bytes(nsamp_blk, nchans, block_len)
+        if workspace is None:
+            workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=block.device)
+        elif (workspace.dtype != torch.uint8 or workspace.device != block.device or not workspace.is_contiguous()
+              or workspace.numel() < need):
+            raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on the block's device")
+        _check(_L.rt_block_stats_device(_lib.ptr(block), DEDISP_DTYPES[name], nsamp_blk, nchans, block_len,
+                                        _lib.ptr(out), _lib.ptr(workspace), workspace.numel(), _stream_handle(s)))
     return out
 
 
@@ -568,12 +663,16 @@ def channel_stats_device(block, acc, workspace=None, stream=None, nbits=None):
     return acc
 
 
-def _dedisperse_device(block, delays, max_delay, bands, mask, out, out_offset, workspace, stream, zero_dm, nbits):
+def _dedisperse_device(block, delays, max_delay, bands, mask, out, out_offset, workspace, stream, zero_dm, nbits,
+                       block_mask=None, t_origin=0):
     """dedisperse_device (bands None) and dedisperse_bands_device: what they
-    share -- block, delays, mask, max_delay, workspace and stream -- checked
-    once, out by the rule of whichever it is, then the one call."""
+    share -- block, delays, mask, max_delay, workspace, stream and the block
+    mask -- checked once, out by the rule of whichever it is, then the one
+    call: without a block mask the entry point it always was, with one
+    rt_dedisperse_device_cells."""
     import torch
     name, nsamp_blk, nchans = _dedisp_block(block, nbits)
+    bm = _block_mask_struct(block_mask, t_origin, block, name, nchans)
     if (delays.dim() != 2 or delays.dtype != torch.int32 or delays.device != block.device
             or not delays.is_contiguous() or delays.shape[1] != nchans):
         raise ValueError("delays must be a contiguous int32 [ndm, nchans] tensor on the block's device")
@@ -618,7 +717,16 @@ def _dedisperse_device(block, delays, max_delay, bands, mask, out, out_offset, w
                 None if mask is None else _lib.ptr(mask), ndm)
         tail = (out_offset, _lib.ptr(workspace), workspace.numel(), _stream_handle(s),
                 DEDISP_ZERO_DM if zero_dm else 0)
-        if bands is None:
+        if bm is not None:
+            # the entry point reads "no table, nbands 0" as the plain call: an empty table is refused here,
+            # as rt_dedisperse_bands_device refuses it
+            if bands is not None and not nbands:
+                raise ValueError("dedisperse: nbands must be at least 1")
+            table = (None, 0) if bands is None else (_lib.ptr(bands), nbands)
+            stride = (out.stride(0) if ndm > 1 else out.shape[1]) if bands is None else out.shape[2]
+            _check(_L.rt_dedisperse_device_cells(*head, *table, max_delay, _lib.ptr(out), stride, *tail,
+                                                 ctypes.byref(bm)))
+        elif bands is None:
             _check(_L.rt_dedisperse_device_opt(*head, max_delay, _lib.ptr(out),
                                                out.stride(0) if ndm > 1 else out.shape[1], *tail))
         else:
@@ -628,7 +736,7 @@ def _dedisperse_device(block, delays, max_delay, bands, mask, out, out_offset, w
 
 
 def dedisperse_device(block, delays, max_delay, mask=None, out=None, out_offset=0, workspace=None, stream=None,
-                      zero_dm=False, nbits=None):
+                      zero_dm=False, nbits=None, block_mask=None, t_origin=0):
     """Incoherent dedispersion of one resident block (rt_dedisperse_device):
     block uint8 / int8 / float32 [nsamp_blk, nchans] (time-major, contiguous),
     delays int32 [ndm, nchans] and mask (uint8 [nchans], non-zero = skipped, or
@@ -650,12 +758,23 @@ def dedisperse_device(block, delays, max_delay, mask=None, out=None, out_offset=
     Every time sample first loses its mean over the unmasked channels
     (zero_dm_mean_device), and every dtype is then summed in float32 in channel
     order; the workspace is the larger one of dedisperse_workspace_bytes(...,
-    zero_dm=True)."""
-    return _dedisperse_device(block, delays, max_delay, None, mask, out, out_offset, workspace, stream, zero_dm, nbits)
+    zero_dm=True).
+
+    block_mask (a DeviceBlockMask) with t_origin, the absolute sample index of
+    the block's row 0: every sample (t, c) with block_mask.cells[(t_origin +
+    t) // block_len, c] != 0 is read as block_mask.fill[c], in front of
+    everything above -- the result is, bit for bit, that of the same call
+    without a block mask on a block holding the replaced samples
+    (rfi.apply_block_mask_host).  ValueError, nothing launched, when the rows
+    [t_origin, t_origin + nsamp_blk) reach past the nblocks * block_len
+    samples the cells cover, or the fill is not of the sample's type.  No
+    workspace of its own."""
+    return _dedisperse_device(block, delays, max_delay, None, mask, out, out_offset, workspace, stream, zero_dm, nbits,
+                              block_mask, t_origin)
 
 
 def dedisperse_bands_device(block, delays, max_delay, bands, mask=None, out=None, out_offset=0, workspace=None,
-                            stream=None, zero_dm=False, nbits=None):
+                            stream=None, zero_dm=False, nbits=None, block_mask=None, t_origin=0):
     """dedisperse_device for every band of a table at once
     (rt_dedisperse_bands_device): bands is uint32 [nbands, 2] of channel
     ranges [lo, hi) -- a numpy array, or a contiguous int32 tensor on the
@@ -668,9 +787,10 @@ def dedisperse_bands_device(block, delays, max_delay, bands, mask=None, out=None
     With zero_dm the mean is over the unmasked channels of the whole block.
     Returns out, float32 [ndm, nbands, >= out_offset + nsamp_blk - max_delay]
     (contiguous; allocated [ndm, nbands, nsamp_blk - max_delay] when None).
-    One pass over the block for all bands; block, delays, mask, workspace and
-    nbits as for dedisperse_device."""
-    return _dedisperse_device(block, delays, max_delay, bands, mask, out, out_offset, workspace, stream, zero_dm, nbits)
+    One pass over the block for all bands; block, delays, mask, workspace,
+    nbits, block_mask and t_origin as for dedisperse_device."""
+    return _dedisperse_device(block, delays, max_delay, bands, mask, out, out_offset, workspace, stream, zero_dm, nbits,
+                              block_mask, t_origin)
 
 
 def profile_enable(on=True):

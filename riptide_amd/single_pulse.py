@@ -183,13 +183,13 @@ def search_pulses(series, tsamp, dms, widths=None, threshold=8.0, radius=None, t
 
 def search_filterbank_pulses(fb_or_fname, dms, deredden_params, widths=None, threshold=8.0, mask=None, zero_dm=False,
                              kdm=None, nout=None, batch=8, device=None, radius=None, time_radius=None, dm_gap=1,
-                             max_events=1 << 20):
+                             max_events=1 << 20, block_mask=None):
     """Single-pulse search of a channelised SIGPROC file (a file name, a
     reading.Filterbank or PackedFilterbank) at the trial DMs without leaving
     the device: dedispersion.dedisperse_filterbank, then slices of `batch` DMs
     through engine.deredden_normalise (deredden_params: rmed_width in
     seconds, rmed_minpts) and engine.single_pulse_device, one download of the
-    events and cluster_events.  mask, zero_dm, kdm, nout: as for
+    events and cluster_events.  mask, zero_dm, kdm, nout, block_mask: as for
     dispatch.search_filterbank.  Returns (pulses, events); `series` of an
     event is its index into dms."""
     import torch
@@ -206,7 +206,8 @@ def search_filterbank_pulses(fb_or_fname, dms, deredden_params, widths=None, thr
     batch = max(1, int(batch))
     parts = []
     with torch.cuda.device(dev):
-        series = dedisperse_filterbank(fb, dms, mask=mask, device=dev, nout=nout, kdm=kdm, zero_dm=zero_dm)
+        series = dedisperse_filterbank(fb, dms, mask=mask, device=dev, nout=nout, kdm=kdm, zero_dm=zero_dm,
+                                       block_mask=block_mask)
         w = _default_widths(widths, series.shape[1])
         ws = int(round(deredden_params["rmed_width"] / fb.tsamp))
         for b0 in range(0, len(dms), batch):

@@ -22,6 +22,12 @@ with the N sub-bands of dedispersion.band_edges: the same reads and additions
 as the plain call, N times its output.  Reported next to the plain call's time
 with both outputs' bytes and the time the plain call would take for the extra
 output at the bandwidth it achieved.
+--block-mask writes the block to a file in --stream-dir and times
+dedisperse_filterbank on it with and without a block mask (5 % of the cells of
+--block-len samples flagged, the same build's plain call beside it,
+alternating), the resident-block call with and without it (kernels only,
+alternating too; with --zero-dm also the zero-DM call and the row mean alone),
+and rfi.block_stats; a mask that flags nothing must give the plain call's bits.
 A record, not a gate: prints one JSON line and writes it to --out.
 
     python tools/bench_dedisperse.py --out profiles/<tag>_dedisperse.json
@@ -52,6 +58,10 @@ def main():
     ap.add_argument("--bands", type=int, default=0, help="also time the sub-band call with this many bands")
     ap.add_argument("--stream", action="store_true", help="also time dedisperse_filterbank on a file of the block")
     ap.add_argument("--stream-dir", default="/tmp")
+    ap.add_argument("--block-mask", action="store_true",
+                    help="also time dedisperse_filterbank and the resident call with and without a block mask, and "
+                         "rfi.block_stats, on a file of the block")
+    ap.add_argument("--block-len", type=int, default=2048, help="time samples of a block of --block-mask")
     args = ap.parse_args()
     if args.repeats < 10:
         ap.error("--repeats must be at least 10")
@@ -210,6 +220,98 @@ def main():
         os.remove(fname)
         extra.update({"stream_ms_median": float(np.median(sms)), "stream_ms_min": float(np.min(sms)),
                       "stream_ms_max": float(np.max(sms)), "stream_file_bytes": block_bytes})
+    if args.block_mask:
+        # the same rows as a file: dedisperse_filterbank with and without a block
+        # mask (blocks of --block-len samples, 5 % of the cells flagged at
+        # random, the fill the channels' means), the resident-block call with
+        # and without it, and rfi.block_stats (upload + kernels + download)
+        import time
+        from riptide_amd import rfi
+        fname = os.path.join(args.stream_dir, f"bench_blockmask_{dname}.fil")
+        header = {"tsamp": tsamp, "nbits": nbits or 8, "fch1": float(freqs[0]), "foff": float(freqs[1] - freqs[0]),
+                  "nchans": nchans, "nifs": 1}
+        host_rows = block.cpu().numpy()
+        write_sigproc(fname, host_rows.ravel() if nbits else host_rows, header)
+        del host_rows
+        fb = open_filterbank(fname)
+        blen = args.block_len
+        stats = rfi.block_stats(fb, block_len=blen)      # warm-up
+        st_ms = []
+        for _ in range(args.repeats):
+            t0 = time.perf_counter()
+            stats = rfi.block_stats(fb, block_len=blen)
+            st_ms.append((time.perf_counter() - t0) * 1e3)
+        cells = np.random.RandomState(1).rand(stats.sum.shape[0], nchans) < 0.05
+        bm = rfi.BlockMask(cells, blen, stats.sum.sum(axis=0) / stats.nsamp)
+        clear = rfi.BlockMask(np.zeros_like(cells), blen, bm.fill)
+        plain_first = dedisperse_filterbank(fb, dms)
+        assert torch.equal(dedisperse_filterbank(fb, dms, block_mask=clear), plain_first), \
+            "a block mask that flags nothing changes the result"
+        del plain_first
+        torch.cuda.synchronize()
+        pms, mms = [], []
+        for _ in range(args.repeats):      # alternating, so drift falls on both alike
+            for kw, into in (({}, pms), ({"block_mask": bm}, mms)):
+                a.record()
+                res = dedisperse_filterbank(fb, dms, **kw)
+                b.record()
+                b.synchronize()
+                into.append(a.elapsed_time(b))
+                del res
+        os.remove(fname)
+        d_bm = engine.DeviceBlockMask(torch.from_numpy(cells.astype(np.uint8)).cuda(),
+                                      torch.from_numpy(bm.typed_fill(fb)).cuda(), blen)
+
+        def run_masked():
+            engine.dedisperse_device(block, d_delays, max_delay, out=out, workspace=ws, nbits=nbits, block_mask=d_bm)
+
+        def alternating(plain_fn, masked_fn):
+            """(plain ms, masked ms), one call of each in turn."""
+            masked_fn()
+            torch.cuda.synchronize()
+            pl, mk = [], []
+            for _ in range(args.repeats):
+                for fn, into in ((plain_fn, pl), (masked_fn, mk)):
+                    a.record()
+                    fn()
+                    b.record()
+                    b.synchronize()
+                    into.append(a.elapsed_time(b))
+            return pl, mk
+
+        rpl, rms = alternating(run, run_masked)
+        if args.zero_dm:
+            # the zero-DM call and the row mean alone, with and without the mask
+            def run_zero_dm_masked():
+                engine.dedisperse_device(block, d_delays, max_delay, out=out, workspace=zws, zero_dm=True, nbits=nbits,
+                                         block_mask=d_bm)
+
+            def run_mean_masked():
+                engine.zero_dm_mean_device(block, out=mean, nbits=nbits, block_mask=d_bm)
+
+            zpl, zmk = alternating(run_zero_dm, run_zero_dm_masked)
+            mpl, mmk = alternating(run_mean, run_mean_masked)
+            extra.update({"zero_dm_resident_plain_ms_median": float(np.median(zpl)),
+                          "zero_dm_resident_masked_ms_median": float(np.median(zmk)),
+                          "zero_dm_resident_masked_ms_min": float(np.min(zmk)),
+                          "zero_dm_resident_masked_ms_max": float(np.max(zmk)),
+                          "zero_dm_resident_masked_to_plain_ratio": float(np.median(zmk) / np.median(zpl)),
+                          "row_mean_plain_ms_median": float(np.median(mpl)),
+                          "row_mean_masked_ms_median": float(np.median(mmk)),
+                          "row_mean_masked_ms_min": float(np.min(mmk)), "row_mean_masked_ms_max": float(np.max(mmk)),
+                          "row_mean_masked_to_plain_ratio": float(np.median(mmk) / np.median(mpl))})
+        pmed, mmed, rmed, rpmed = (float(np.median(v)) for v in (pms, mms, rms, rpl))
+        extra.update({"block_len": blen, "block_mask_fraction": bm.fraction,
+                      "block_mask_cells_bytes": int(cells.size),
+                      "file_plain_ms_median": pmed, "file_plain_ms_min": float(np.min(pms)),
+                      "file_plain_ms_max": float(np.max(pms)),
+                      "file_masked_ms_median": mmed, "file_masked_ms_min": float(np.min(mms)),
+                      "file_masked_ms_max": float(np.max(mms)), "file_masked_to_plain_ratio": mmed / pmed,
+                      "resident_plain_ms_median": rpmed, "resident_masked_ms_median": rmed,
+                      "resident_masked_ms_min": float(np.min(rms)), "resident_masked_ms_max": float(np.max(rms)),
+                      "resident_masked_to_plain_ratio": rmed / rpmed,
+                      "block_stats_ms_median": float(np.median(st_ms)), "block_stats_ms_min": float(np.min(st_ms)),
+                      "block_stats_ms_max": float(np.max(st_ms))})
     with open(os.path.join(REPO, "BENCH_r06.json")) as f:
         search_ms = json.load(f)["parsed"]["ms_per_step"] / 16.0
     result = {"nchans": nchans, "nsamp": nsamp, "ndm": ndm, "tsamp": tsamp, "dm_max": float(dms[-1]),
