@@ -179,6 +179,30 @@ def test_truncation(lib):
     assert rows[0, 1].tolist() == [100, 500, CANARY_ROW, CANARY_ROW]
 
 
+@pytest.mark.parametrize("chunk_rows", [64, 0])
+def test_threshold_equality_and_rounding(lib, chunk_rows):
+    """The device twin of test_peaks_cluster_host's test of the same name:
+    S/N equal to the threshold or to smin, and polynomials for which a fused
+    multiply-add changes the comparison (peak_threshold's __dadd_rn(__dmul_rn())
+    on the device), in both directions."""
+    import peaks_select_common as pc
+    pc.check_equality_cases()
+    pc.check_rounding_cases()
+    logf, freqs = ph.synthetic(pc.EQ_LENGTH)
+    for name, s, coeffs, smin, want in pc.equality_cases():
+        hc = assert_device_is_host(lib, s[None], logf, freqs, coeffs[None], 0.1, cap=8, chunk_rows=chunk_rows,
+                                   smin=smin)
+        assert hc[0].tolist() == [len(w) for w in want], name
+        _, rows, _ = device_find(lib, s[None], logf, freqs, coeffs[None], smin, 0.1, 8, chunk_rows)
+        assert [rows[0, iw, :len(w)].tolist() for iw, w in enumerate(want)] == want, name
+    for degree in pc.RND_EACH:
+        snrs, logf, freqs, coeffs, smin, r, want = pc.rounding_batch(degree)
+        hc = assert_device_is_host(lib, snrs, logf, freqs, coeffs, r, cap=4, chunk_rows=chunk_rows, smin=smin)
+        assert hc.tolist() == [[len(w) for w in trial] for trial in want], degree
+        _, rows, _ = device_find(lib, snrs, logf, freqs, coeffs, smin, r, 4, chunk_rows)
+        assert [[i] for i in rows[0, :, 0].tolist()] == want[0], degree
+
+
 def test_empty_shapes(lib):
     """length 0 zeroes the counts; batch or widths of 0 launch nothing."""
     import torch

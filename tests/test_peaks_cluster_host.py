@@ -252,6 +252,41 @@ def test_cap_below_the_cluster_count(lib):
     assert [len(r[0]) for r in ref] == [9, 2]
 
 
+def test_threshold_equality_and_rounding(lib):
+    """The walk's selection where `>=` for `>` or a fused y * x + c would
+    show (peaks_select_common): an S/N equal to the constant threshold or to
+    smin is not selected while the float32 one ulp above it is, and
+    polynomials for which a fused multiply-add changes the comparison follow
+    np.polyval's two roundings per step (the host's -ffp-contract=off), in
+    both directions.  Every selected row is a cluster of its own, so the
+    peaks are the selected rows."""
+    import peaks_select_common as pc
+    pc.check_equality_cases()
+    pc.check_rounding_cases()
+    logf, freqs = synthetic(pc.EQ_LENGTH)
+    for name, s, coeffs, smin, want in pc.equality_cases():
+        ref = check(lib, s, logf, freqs, coeffs, 0.1, cap=8, smin=smin)
+        assert [list(r[0]) for r in ref] == want, name
+    for degree in pc.RND_EACH:
+        snrs, logf, freqs, coeffs, smin, r, want = pc.rounding_batch(degree)
+        for b in range(2):
+            ref = check(lib, snrs[b], logf, freqs, coeffs[b], r, cap=4, smin=smin)
+            assert [list(x[0]) for x in ref] == want[b], (degree, b)
+            # behind a leading +0.0 coefficient, as poly1d_table stores a trimmed fit
+            padded = np.concatenate([np.zeros((coeffs.shape[1], 1)), coeffs[b]], axis=1)
+            ref = check(lib, snrs[b], logf, freqs, padded, r, cap=4, smin=smin)
+            assert [list(x[0]) for x in ref] == want[b], (degree, b)
+
+
+def test_peak_finder_inputs_hold_their_conditions():
+    """The synthetic S/N PeakFinder's paths are compared on
+    (tests/test_gpu_peaks_select.py), against find_peaks alone: lists over
+    the cap, within it and empty in the same trial, in both threshold
+    branches."""
+    import peaks_select_common as pc
+    pc.check_finder_case()
+
+
 def test_invalid_arguments(lib):
     from riptide_amd import _lib
     need = ctypes.c_size_t(123)
