@@ -37,7 +37,9 @@ void expect(bool ok, const char* what)
 void run_shape(size_t B, size_t S, size_t N, size_t K, size_t J)
 {
     std::vector<double> f(B), periods(J), dms(K);
-    for (size_t b = 0; b < B; ++b) f[b] = 1500.0 - 37.0 * (double)b - 3.0 * (double)(b * b);
+    // unevenly spaced and positive: narrower bands where there are many
+    const double df = B > 16 ? 1.25 : 37.0, ddf = B > 16 ? 0.001 : 3.0;
+    for (size_t b = 0; b < B; ++b) f[b] = 1500.0 - df * (double)b - ddf * (double)(b * b);
     const double P = 0.5, T = 600.0, dm = 50.0, kdm = 4148.808;
     for (size_t j = 0; j < J; ++j) periods[j] = 1.0 / (1.0 / P - ((double)j - (double)(J / 2)) * 1.7 / ((double)N * T));
     for (size_t k = 0; k < K; ++k) dms[k] = dm + ((double)k - (double)(K / 2)) * 900.0;
@@ -166,6 +168,10 @@ int main()
     run_shape(7, 2, 65, 3, 3);
     run_shape(3, 33, 64, 3, 3);
     run_shape(7, 2, 257, 5, 3);
+    // more than 256 rows of each table, and 700 bins (tests/test_refine_host.py)
+    run_shape(513, 2, 31, 3, 3);
+    run_shape(2, 513, 16, 3, 3);
+    run_shape(3, 2, 700, 2, 2);
     run_errors();
     if (g_failed) return 1;
     std::printf("refine_check OK\n");

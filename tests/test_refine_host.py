@@ -68,7 +68,9 @@ def test_shift_table_errors():
         refine_shifts(0.5, 1e6, 16, 3, f, 10.0, [0.5, 1e-12], dms)
 
 
-HOST_SHAPES = [(1, 1, 2), (2, 1, 3), (7, 2, 65), (3, 33, 64)]
+# the last three: three chunks of band and of sub-integration rows (the device
+# loads 256 rows of shifts at a time), and three bins per device thread
+HOST_SHAPES = [(1, 1, 2), (2, 1, 3), (7, 2, 65), (3, 33, 64), (513, 2, 31), (2, 513, 16), (3, 2, 700)]
 
 
 @pytest.mark.parametrize("B,S,N", HOST_SHAPES)
@@ -77,6 +79,9 @@ def test_host_against_numpy(oracle, B, S, N):
     rng = np.random.RandomState(B * 1000 + S * 10 + N)
     d, p = rc.tables(rng, B, S, N, 3, 3)
     assert d.min() == 0 and d.max() == N - 1 and p.min() == 0 and p.max() == N - 1
+    for t in (d, p):
+        if t.shape[1] > rc.CHUNK:
+            rc.check_chunked_table(t, N)
     w = rc.widths_for(N)
     assert w[0] == 1 and w[-1] == N - 1
     stdnoise = 1.7
@@ -95,6 +100,59 @@ def test_host_against_numpy(oracle, B, S, N):
     ok, msg = snr_close(snr.reshape(-1, w.size), oracle.snr2(prof.reshape(-1, N), w, stdnoise), rtol=1e-4)
     assert ok, msg
     assert np.array_equal(refine_host(x, d, p, w, stdnoise), snr)       # without the profile output
+
+
+@pytest.mark.parametrize("B,S,N,K,J", rc.OFFSET_SHAPES)
+def test_host_snr_with_an_offset(B, S, N, K, J):
+    """Profiles about 100 B S high: (h + b) * dmax - b * sum cancels most of
+    two large terms, and the S/N is compared by the rounding of those terms
+    (rc.snr1_bound), not by its own size.  The numpy restatement of refine_snr1
+    gives the host's bits, and the host is within the bound of the expression
+    in float64: the bound the device is held to (test_gpu_refine.py) is not
+    too tight.  Largest |error| / bound of the host: 0.115 at (8, 8, 64), 0.081
+    at (3, 2, 700)."""
+    from riptide_amd.refine import refine_host
+    g = rc.offset_job(B, S, N, K, J)
+    assert list(g[3]) == [1, N // 3, N - 1] and g[4] == 1.7
+    snr, prof = refine_host(*g, profiles=True)
+    assert abs(float(prof.mean()) / (rc.OFFSET * B * S) - 1) < 0.01
+    f32, f64, bound = rc.snr1_bound(prof, g[3], g[4])
+    snr = snr.reshape(f32.shape)
+    assert np.array_equal(snr.view(np.uint32), f32.view(np.uint32))
+    ratio = np.abs(snr.astype(np.float64) - f64) / bound
+    print(f"host S/N with an offset {(B, S, N)}: largest |error| / bound {ratio.max():.3f}, "
+          f"largest |S/N| {np.abs(f64).max():.3f}, largest bound {bound.max():.3e}")
+    assert (ratio <= 1.0).all(), ratio.max()
+
+
+def test_workspace_bytes_of_a_batch():
+    """rt_refine_workspace_bytes (host only): the descriptor table rounded up
+    to 256 bytes, then y [K, S, N] floats per candidate; the planner's errors."""
+    import ctypes
+    from riptide_amd import _lib
+    from riptide_amd.refine import pack_refine
+    L = _lib.load()
+    table = pack_refine(rc.batch_jobs())[3]
+    shapes = rc.batch_shapes()
+    assert table.size == rc.BATCH_SIZE == 40
+    # the device's descriptor of a candidate (RefineCand, refine_host.hpp):
+    # seven 64-bit offsets and twelve 32-bit fields
+    entry = 7 * 8 + 12 * 4
+    need = ctypes.c_size_t()
+    _lib.check(L.rt_refine_workspace_bytes(_lib.ptr(table), table.size, ctypes.byref(need)))
+    assert need.value == -(-table.size * entry // 256) * 256 + 4 * sum(K * S * N for _, S, N, K, _ in shapes)
+    one = table[:1].copy()
+    _lib.check(L.rt_refine_workspace_bytes(_lib.ptr(one), 1, ctypes.byref(need)))
+    assert need.value == 256 + 4 * shapes[0][3] * shapes[0][1] * shapes[0][2]
+    _lib.check(L.rt_refine_workspace_bytes(None, 0, ctypes.byref(need)))
+    assert need.value == 0
+    for field, bad, text in (("bins", 1, "bins must be in"), ("bins", 1025, "bins must be in"),
+                             ("bands", 0, "must be >= 1"), ("subints", 0, "must be >= 1"), ("ndm", 0, "must be >= 1"),
+                             ("nper", 0, "must be >= 1"), ("nw", 0, "no trial widths")):
+        t = table.copy()
+        t[field][17] = bad
+        with pytest.raises(ValueError, match=text):
+            _lib.check(L.rt_refine_workspace_bytes(_lib.ptr(t), t.size, ctypes.byref(need)))
 
 
 def test_host_errors():
