@@ -526,6 +526,37 @@ int rt_single_pulse_device(const float* d_x, size_t nseries, size_t size, size_t
                            size_t capacity, uint64_t* d_count, float* d_best, int32_t* d_kbest, void* d_workspace,
                            size_t workspace_bytes, void* stream);
 
+/* ------------------- resampling (the acceleration search) ------------------ */
+/* Time-domain resampling of series x[B][0..N) (float32, rows ldx floats
+ * apart): output row r (rows ldo floats apart) is source row src[r] stretched
+ * by the float64 factor f = factor[r], nearest neighbour:
+ *   q_j = j * (N - j)                          exact, j = 0 .. N - 1
+ *   s_j = (int64) rint(f * (double)q_j)        one IEEE double multiply, round-half-even
+ *   out[r][j] = x[src[r]][clamp(j - s_j, 0, N - 1)]
+ * a copy of the float's bits (NaN payloads, -0.0 and denormals included), so
+ * host and device results have the same bits.  With f = accel * tsamp / (2 c),
+ * accel in m/s^2 positive when the source accelerates away, a uniformly
+ * accelerated signal becomes strictly periodic at its mid-observation
+ * frequency.  f = 0 is a copy.  out must not overlap x.
+ * RT_EINVAL (nothing is written or launched) for N above
+ * RT_RESAMPLE_MAX_SAMPLES (q_j must stay exact in a double), R above
+ * RT_RESAMPLE_MAX_ROWS, and, when R * N > 0: a null pointer, ldx < N, ldo < N,
+ * a src[r] outside [0, B), a factor that is not finite or has
+ * fabs(f) * (double)N >= 1.0 (below that the map is monotone).  R == 0 or
+ * N == 0 is RT_OK and does nothing. */
+#define RT_RESAMPLE_MAX_SAMPLES 134217728
+#define RT_RESAMPLE_MAX_ROWS 65535
+/* Host only: the specification, sequential. */
+int rt_resample_host(const float* x, size_t nseries, size_t size, size_t ldx, const int32_t* src,
+                     const double* factor, size_t nrows, float* out, size_t ldo);
+/* The same map of device-resident series.  Stream-ordered: no host
+ * synchronisation, no device allocation and no workspace; src and factor are
+ * host memory, read before the call returns (they travel as kernel
+ * arguments, RT_RESAMPLE_LAUNCH_ROWS rows a launch). */
+#define RT_RESAMPLE_LAUNCH_ROWS 128
+int rt_resample_device(const float* d_x, size_t nseries, size_t size, size_t ldx, const int32_t* src,
+                       const double* factor, size_t nrows, float* d_out, size_t ldo, void* stream);
+
 /* --------------------------- harmonic flagging ----------------------------- */
 /* riptide/pipeline/harmonic_testing.py (hdiag, htest) and the pair loop of
  * Pipeline.flag_harmonics (pipeline/pipeline.py:217-249).  A cluster is its

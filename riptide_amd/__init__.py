@@ -22,10 +22,10 @@ from .peak_cluster import PeakCluster
 from .candidate import Candidate, build_candidates, build_candidates_filterbank
 from .harmonic_testing import apply_candidate_filters, flag_harmonics, hdiag, htest
 from .reading import Filterbank, PackedFilterbank, open_filterbank
-from .dispatch import search_filterbank
+from .dispatch import search_filterbank, search_filterbank_accel
 from .refine import Refinement, refine_candidates, refine_cube
 from .single_pulse import SinglePulse, search_filterbank_pulses
-from . import dedispersion, rfi, single_pulse
+from . import acceleration, dedispersion, rfi, single_pulse
 
 __all__ = [
     "Candidate", "PeakCluster", "build_candidates", "build_candidates_filterbank", "flag_harmonics",
@@ -36,4 +36,5 @@ __all__ = [
     "PackedFilterbank", "open_filterbank",
     "dedispersion", "rfi", "Refinement", "refine_cube", "refine_candidates",
     "SinglePulse", "search_filterbank_pulses", "single_pulse",
+    "acceleration", "search_filterbank_accel",
 ]

@@ -59,6 +59,10 @@ _SIGNATURES = {
     # as the host form with device x, events, count, best, kbest; then workspace, workspace bytes, stream
     "rt_single_pulse_device": (_c_i, [_vp, _c_sz, _c_sz, _c_sz, _vp, _c_sz, _c_f, _c_sz, _vp, _c_sz, _vp, _vp, _vp,
                                       _vp, _c_sz, _vp]),
+    # x, nseries, size, ldx, src (int32, host), factor (float64, host), nrows, out, ldo
+    "rt_resample_host": (_c_i, [_vp, _c_sz, _c_sz, _c_sz, _vp, _vp, _c_sz, _vp, _c_sz]),
+    # the same with device x and out; then stream
+    "rt_resample_device": (_c_i, [_vp, _c_sz, _c_sz, _c_sz, _vp, _vp, _c_sz, _vp, _c_sz, _vp]),
     "rt_periodogram_length": (_c_i,[_c_sz, _c_d, _c_d, _c_d, _c_sz, _c_sz, _psz]),
     "rt_periodogram": (_c_i, [_vp, _c_sz, _c_d, _vp, _c_sz, _c_d, _c_d, _c_sz, _c_sz, _vp, _vp, _vp]),
     "rt_running_median": (_c_i, [_vp, _c_sz, _c_sz, _vp]),

@@ -7,6 +7,7 @@
 #include "fold_host.hpp"
 #include "harmonic.hpp"
 #include "refine_host.hpp"
+#include "resample_host.hpp"
 
 namespace rt {
 
@@ -136,6 +137,13 @@ uint64_t blockstats_chunks(uint64_t nsamp_blk, uint64_t block_len);
 uint64_t blockstats_workspace_bytes(uint64_t nsamp_blk, uint64_t nchans, uint64_t block_len);
 hipError_t launch_block_stats(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans, uint32_t block_len,
                               double* stats, void* ws, hipStream_t s);
+
+// resample_kernels.hip
+// out[r, j] = x[T.src[r], resample_index(T.factor[r], j, N)] for r < rows <=
+// kResampleLaunchRows, j < N; the caller has checked the table
+// (resample_check_args of resample_host.hpp)
+hipError_t launch_resample(const float* x, uint64_t ldx, uint32_t N, const ResampleRows& T, uint32_t rows,
+                           float* out, uint64_t ldo, hipStream_t s);
 
 // harmonic_kernels.hip
 // One tile of the harmonic pair matrix: rows [i0, i0 + rows) of the n ranked

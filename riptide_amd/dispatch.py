@@ -111,12 +111,19 @@ class EngineSearcher:
         """Queue a device batch's deredden + normalise and every range's
         periodogram on the current stream; returns the pending batch for
         _detect.  Nothing here waits for the device."""
-        import torch
+        return self._enqueue_series(self._normalise(raw, tsamp), tsamp, [m.get("dm") for m in metadatas])
+
+    def _normalise(self, raw, tsamp):
+        """deredden + normalise of a device batch, queued on the current stream."""
         from . import engine
-        B, n = raw.shape
         ws = int(round(self.deredden_params["rmed_width"] / tsamp))
-        x = engine.deredden_normalise(raw, ws, self.deredden_params["rmed_minpts"])
-        dms = [m.get("dm") for m in metadatas]
+        return engine.deredden_normalise(raw, ws, self.deredden_params["rmed_minpts"])
+
+    def _enqueue_series(self, x, tsamp, dms):
+        """_enqueue behind the normalisation: every range's periodogram of the
+        normalised batch x, one row per entry of dms."""
+        import torch
+        B, n = x.shape
         main = torch.cuda.current_stream(x.device)
         if os.environ.get("RIPTIDE_AMD_PEAKS_SERIAL"):
             return {"serial": True, "x": x, "n": n, "tsamp": tsamp, "dms": dms}
@@ -263,6 +270,64 @@ class EngineSearcher:
             per.extend(self._detect(pending))
         return per
 
+    def search_device_accel(self, raw, tsamp, metadatas, accels):
+        """The acceleration search of a device batch raw [D, N] (float32), one
+        dedispersed series per DM: every series at every trial acceleration of
+        `accels` (m/s^2, acceleration.accel_trials).  Each series is dereddened
+        and normalised once, in slices of `batch` DMs; its (DM, accel) rows,
+        DM-major, are stretched by engine.resample_device in slices of at most
+        `batch` rows, and every slice goes the way of a search_device batch,
+        slice k + 1 queued before slice k's detection.  Returns one list of
+        acceleration.AccelPeak per DM, in accel order, then range order."""
+        from . import engine
+        from .acceleration import AccelPeak, accel_factor
+        accels = [float(a) for a in accels]
+        D, A = raw.shape[0], len(accels)
+        out = [[] for _ in range(D)]
+        if not D or not A:
+            return out
+        factors = np.array([accel_factor(a, tsamp) for a in accels], dtype=np.float64)
+        dms = [m.get("dm") for m in metadatas]
+
+        def collect(rows, pend):
+            for r, peaks in zip(rows, self._detect(pend)):
+                out[r // A].extend(AccelPeak(*p, accels[r % A]) for p in peaks)
+
+        pending = None
+        for d0 in range(0, D, self.batch):
+            d1 = min(d0 + self.batch, D)
+            x = self._normalise(raw[d0:d1], tsamp)
+            for r0 in range(d0 * A, d1 * A, self.batch):
+                rows = np.arange(r0, min(r0 + self.batch, d1 * A))
+                y = engine.resample_device(x, factors[rows % A], src=rows // A - d0)
+                pend = self._enqueue_series(y, tsamp, [dms[r // A] for r in rows])
+                if pending is not None:
+                    collect(*pending)
+                pending = (rows, pend)
+        collect(*pending)
+        return out
+
+    def search_filterbank_accel(self, fb, dms, accels, mask=None, nout=None, kdm=None, zero_dm=False,
+                                block_mask=None):
+        """search_filterbank with an acceleration axis: the file dedispersed at
+        the trial DMs on the device, then search_device_accel of the series.
+        One list of acceleration.AccelPeak per DM, in the order given; fb, mask,
+        nout, kdm, zero_dm and block_mask as for search_filterbank.  With
+        accels = [0.0] the peaks are search_filterbank's.  The single-pulse
+        search (pulses=) is not combined with it."""
+        import torch
+        from .dedispersion import KDM, dedisperse_filterbank
+        kdm = KDM if kdm is None else float(kdm)
+        dms = [float(d) for d in dms]
+        if not dms:
+            return []
+        dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else
+                           (self.device.index if isinstance(self.device, torch.device) else int(self.device)))
+        with torch.cuda.device(dev):
+            series = dedisperse_filterbank(fb, dms, mask=mask, device=dev, nout=nout, kdm=kdm, zero_dm=zero_dm,
+                                           block_mask=block_mask)
+            return self.search_device_accel(series, fb.tsamp, [fb.metadata(dm) for dm in dms], accels)
+
     def _search_filterbank_pulses(self, fb, dms, mask, nout, kdm, zero_dm, kw, block_mask=None):
         """search_filterbank with the single-pulse search beside the
         periodicity search: the same calls in the same order, and each slice's
@@ -311,16 +376,17 @@ def _rank_world(group):
     return 0, 1
 
 
-def _gather_tagged(tagged, group, world):
+def _gather_tagged(tagged, group, world, make=Peak):
     """All ranks' (trial index, peak tuples) lists, gathered once (KB-scale),
-    in trial order, flattened to the WorkerPool contract."""
+    in trial order, flattened to the WorkerPool contract; `make` is the peaks'
+    type."""
     if world > 1:
         import torch.distributed as dist
         gathered = [None] * world
         dist.all_gather_object(gathered, tagged, group=group)
         tagged = [t for part in gathered for t in part]
     tagged.sort(key=lambda t: t[0])
-    return [Peak(*p) for _, plist in tagged for p in plist]
+    return [make(*p) for _, plist in tagged for p in plist]
 
 
 def search_trials(trials, searcher, group=None, loader=None, chunksize=None):
@@ -433,3 +499,39 @@ def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=Non
     widths = single_pulse._default_widths(pulses.get("widths"), nsamp) if dms else None
     return peaks, single_pulse.cluster_events(events, dms, fb.tsamp, time_radius=pulses.get("time_radius"),
                                               dm_gap=pulses.get("dm_gap", 1), widths=widths)
+
+
+def search_filterbank_accel(fb_or_fname, dms, accels, searcher, group=None, mask=None, kdm=None, zero_dm=False,
+                            block_mask=None):
+    """search_filterbank with an acceleration axis: each rank dedisperses its
+    round-robin share of `dms` from the one file, searches every series at
+    every trial acceleration of `accels` (m/s^2;
+    searcher.search_filterbank_accel, an EngineSearcher), and the tagged peak
+    lists are gathered once.  Returns the full list of acceleration.AccelPeak
+    on every rank, in the order of `dms`, then of `accels`, then range order.
+    Every rank cuts its series to the length the whole DM list leaves, so the
+    result does not depend on the sharding -- the stretch is defined on that
+    common length.  fb_or_fname, mask, kdm, zero_dm and block_mask as for
+    search_filterbank; the single-pulse search is not combined with it."""
+    from .acceleration import AccelPeak
+    from .dedispersion import KDM, dispersion_delays
+    from .reading import Filterbank, open_filterbank
+    kdm = KDM if kdm is None else float(kdm)
+    fb = fb_or_fname if isinstance(fb_or_fname, Filterbank) else open_filterbank(fb_or_fname)
+    dms = [float(d) for d in dms]
+    accels = [float(a) for a in accels]
+    rank, world = _rank_world(group)
+    tagged = []
+    if dms:
+        _, max_delay = dispersion_delays(fb.freqs, dms, fb.tsamp, kdm)
+        if max_delay >= fb.nsamp:
+            raise ValueError(f"the largest delay ({max_delay} samples) is not below the {fb.nsamp} samples of the "
+                             "file")
+        mine = shard(len(dms), rank, world)
+        local = searcher.search_filterbank_accel(fb, [dms[i] for i in mine], accels, mask=mask,
+                                                 nout=fb.nsamp - max_delay, kdm=kdm, zero_dm=zero_dm,
+                                                 block_mask=block_mask)
+        if len(local) != len(mine):
+            raise RuntimeError("searcher must return one peak list per DM")
+        tagged = [(i, [tuple(p) for p in plist]) for i, plist in zip(mine, local)]
+    return _gather_tagged(tagged, group, world, make=AccelPeak)

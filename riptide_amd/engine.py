@@ -441,6 +441,44 @@ def single_pulse_device(data, widths, threshold, radius=None, dense=False, max_e
     return (events, best, kbest) if dense else events
 
 
+def resample_device(data, factors, src=None, out=None, stream=None):
+    """Time-domain resampling of a batch of device series for the acceleration
+    search (rt_resample_device; the specification: acceleration.resample_host,
+    bit for bit): data float32 [N] or [B, N] with unit sample stride (rows may
+    be any distance >= N apart: slices of a wider tensor are read in place),
+    factors float64 values on the host (acceleration.accel_factor), src None
+    -- every row with every factor, row-major [B, len(factors)] -- or one
+    source row per factor.  Returns out, float32 [R, N] on the data's device
+    (allocated when None; rows with unit sample stride, any distance >= N
+    apart, not overlapping data).  Stream-ordered, no host synchronisation, no
+    workspace.  ValueError, nothing launched, for N above 2^27, R above 65535,
+    a src outside [0, B), a factor that is not finite or has |f| * N >= 1."""
+    import torch
+    from .acceleration import resample_rows
+    if data.dim() == 1:
+        data = data.unsqueeze(0)
+    if data.dim() != 2 or data.dtype != torch.float32 or data.device.type != "cuda" or data.stride(1) != 1:
+        raise ValueError("data must be float32 [B, N] device rows with unit stride")
+    B, N = data.shape
+    if B > 1 and data.stride(0) < N:
+        raise ValueError("resample: input row stride below the series length")
+    rows, f = resample_rows(B, factors, src)
+    R = rows.size
+    s = stream if stream is not None else torch.cuda.current_stream(data.device)
+    with torch.cuda.device(data.device), torch.cuda.stream(s):
+        if out is None:
+            out = torch.empty((R, N), dtype=torch.float32, device=data.device)
+        elif (out.dim() != 2 or tuple(out.shape) != (R, N) or out.dtype != torch.float32
+              or out.device != data.device or out.stride(1) != 1):
+            raise ValueError(f"out must be float32 [{R}, {N}] rows with unit stride on the data's device")
+        elif R > 1 and out.stride(0) < N:
+            raise ValueError("resample: output row stride below the series length")
+        _check(_L.rt_resample_device(_lib.ptr(data), B, N, data.stride(0) if B > 1 else max(N, 1), _lib.ptr(rows),
+                                     _lib.ptr(f), R, _lib.ptr(out), out.stride(0) if R > 1 else max(N, 1),
+                                     _stream_handle(s)))
+    return out
+
+
 # RT_DEDISP_* sample type codes (include/riptide_amd.h); 'u1', 'u2', 'u4' and
 # 'u16' are the packed types: the block is then uint8 rows of nchans * nbits / 8
 # bytes (reading.unpack_samples has the format)

@@ -77,6 +77,24 @@ class TimeSeries:
         from .folding import fold
         return fold(self, period, bins, subints=subints)
 
+    def resample(self, accel):
+        """The series stretched for a trial acceleration in m/s^2, positive
+        when the source accelerates away (engine.resample_device with the
+        factor acceleration.accel_factor(accel, tsamp); nearest neighbour, the
+        same samples in a new order): a new TimeSeries of the same length whose
+        metadata is a copy with `accel` set.  A uniformly accelerated signal
+        comes out periodic at its mid-observation period, which is the period
+        an AccelPeak reports: a build_candidates load_series that returns
+        load(dm).resample(accel) folds an accelerated candidate."""
+        import torch
+        from . import engine
+        from .acceleration import accel_factor
+        x = torch.from_numpy(np.ascontiguousarray(self.data, dtype=np.float32)).cuda()
+        out = engine.resample_device(x, [accel_factor(accel, self.tsamp)])[0].cpu().numpy()
+        meta = Metadata(self.metadata)
+        meta["accel"] = float(accel)
+        return TimeSeries(out, self.tsamp, metadata=meta)
+
     @classmethod
     def generate(cls, length, tsamp, period, phi0=0.5, ducy=0.02, amplitude=10.0, stdnoise=1.0):
         """Noisy von Mises pulse train (time_series.py:170-218)."""
