@@ -508,6 +508,14 @@ int rt_single_pulse_host(const float* x, size_t nseries, size_t size, size_t ldx
  * tiles of this many outputs with a halo of radius + largest width on each
  * side) and RT_PULSE_MAX_WIDTH (*max_width). */
 int rt_single_pulse_limits(size_t* tile, size_t* max_width);
+/* Host only, read-only: the device form's LDS plan for a largest width `wmax`
+ * and a radius (pulse_plan, pulse_host.hpp; neither the series nor their
+ * number enter it).  *chunk: the outputs, halo included, whose partial sums
+ * are in LDS at once, a multiple of RT_PULSE_SEGMENT; *chunk_segs: the
+ * segments those need; *lds_bytes: the workgroup's dynamic LDS.  Any pointer
+ * may be NULL.  RT_EINVAL for wmax < 1, wmax or radius above
+ * RT_PULSE_MAX_WIDTH. */
+int rt_single_pulse_plan(size_t wmax, size_t radius, size_t* chunk, size_t* chunk_segs, size_t* lds_bytes);
 /* Host only: device workspace bytes of a call of this shape. */
 int rt_single_pulse_workspace_bytes(size_t nseries, size_t size, size_t num_widths, size_t capacity, size_t* bytes);
 /* The same search of device-resident series.  Stream-ordered: no host

@@ -54,6 +54,8 @@ _SIGNATURES = {
     # kbest
     "rt_single_pulse_host": (_c_i, [_vp, _c_sz, _c_sz, _c_sz, _vp, _c_sz, _c_f, _c_sz, _vp, _c_sz, _vp, _vp, _vp]),
     "rt_single_pulse_limits": (_c_i, [_psz, _psz]),
+    # wmax, radius, chunk, chunk_segs, lds_bytes
+    "rt_single_pulse_plan": (_c_i, [_c_sz, _c_sz, _psz, _psz, _psz]),
     # nseries, size, nw, capacity, bytes
     "rt_single_pulse_workspace_bytes": (_c_i, [_c_sz, _c_sz, _c_sz, _c_sz, _psz]),
     # as the host form with device x, events, count, best, kbest; then workspace, workspace bytes, stream

@@ -124,6 +124,16 @@ void run_errors()
     expect(rt_single_pulse_workspace_bytes(3, 10000, 5, 100, &bytes) == RT_OK && bytes >= 100 * sizeof(rt_pulse_event),
            "workspace bytes");
     expect(rt_single_pulse_workspace_bytes(3, 10000, 0, 100, &bytes) == RT_EINVAL, "workspace: no widths");
+    size_t chunk = 0, segs = 0, lds = 0;
+    expect(rt_single_pulse_plan(RT_PULSE_MAX_WIDTH, RT_PULSE_MAX_WIDTH, &chunk, &segs, &lds) == RT_OK && chunk >= 1024 &&
+               chunk % RT_PULSE_SEGMENT == 0 && segs == (chunk + RT_PULSE_MAX_WIDTH + 2045) / 1024 &&
+               lds <= (160u << 10) && lds > segs * 8 * 1088, "plan at the limits");
+    expect(rt_single_pulse_plan(1, 0, nullptr, nullptr, nullptr) == RT_OK, "plan: null outputs");
+    expect(rt_single_pulse_plan(0, 4, &chunk, &segs, &lds) == RT_EINVAL, "plan: width 0");
+    expect(rt_single_pulse_plan(RT_PULSE_MAX_WIDTH + 1, 4, &chunk, &segs, &lds) == RT_EINVAL,
+           "plan: width above the limit");
+    expect(rt_single_pulse_plan(64, RT_PULSE_MAX_WIDTH + 1, &chunk, &segs, &lds) == RT_EINVAL,
+           "plan: radius above the limit");
 }
 
 }  // namespace

@@ -31,6 +31,20 @@ int rt_single_pulse_limits(size_t* tile, size_t* max_width)
     return RT_OK;
 }
 
+int rt_single_pulse_plan(size_t wmax, size_t radius, size_t* chunk, size_t* chunk_segs, size_t* lds_bytes)
+{
+    return guarded([&] {
+        if (wmax < 1 || wmax > kPulseMaxWidth)
+            throw std::invalid_argument("single pulse: the largest width must be in [1, RT_PULSE_MAX_WIDTH]");
+        if (radius > kPulseMaxWidth) throw std::invalid_argument("single pulse: radius above RT_PULSE_MAX_WIDTH (6144)");
+        const PulsePlan P = pulse_plan(0, 0, 0, 0, (uint32_t)wmax, (uint32_t)radius);
+        if (chunk) *chunk = P.chunk;
+        if (chunk_segs) *chunk_segs = P.chunk_segs;
+        if (lds_bytes) *lds_bytes = P.lds_bytes;
+        return RT_OK;
+    });
+}
+
 int rt_single_pulse_workspace_bytes(size_t nseries, size_t size, size_t num_widths, size_t capacity, size_t* bytes)
 {
     return guarded([&] {

@@ -369,6 +369,17 @@ PULSE_TILE, PULSE_MAX_WIDTH = _pulse_limits()
 PULSE_EVENT_DTYPE = np.dtype([("series", np.int32), ("sample", np.int32), ("iwidth", np.int32), ("snr", np.float32)])
 
 
+def pulse_plan(wmax, radius):
+    """(chunk, chunk_segs, lds_bytes) of the single-pulse tile kernel for a
+    largest width and a radius (rt_single_pulse_plan; no device call): the
+    tile's T + 2 * radius outputs are worked through `chunk` at a time."""
+    if int(wmax) < 0 or int(radius) < 0:
+        raise ValueError("single pulse: wmax and radius must be >= 0")
+    chunk, segs, lds = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+    _check(_L.rt_single_pulse_plan(int(wmax), int(radius), ctypes.byref(chunk), ctypes.byref(segs), ctypes.byref(lds)))
+    return chunk.value, segs.value, lds.value
+
+
 class PulseEvents(typing.NamedTuple):
     """The events of single_pulse_device as columns (device tensors of one
     length), sorted by (series, sample)."""

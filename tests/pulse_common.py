@@ -78,3 +78,58 @@ def events_equal(a, b):
     a, b = np.asarray(a), np.asarray(b)
     return (a.shape == b.shape and all(np.array_equal(a[f], b[f]) for f in ("series", "sample", "iwidth"))
             and np.array_equal(a["snr"].view(np.uint32), b["snr"].view(np.uint32)))
+
+
+def tile_pulses(N, T):
+    """Pulses that hang over the row's ends, across the first tile boundary
+    and inside (no sample gets more than 4 in all: dyadic rows stay in range)."""
+    p = [(2, -3, 9, 1.5), (3, N - 4, 9, 1.5), (0, N // 2, 5, 2.0)]
+    if N > T + 8:
+        p += [(0, T - 3, 7, 1.75), (1, T - 1, 1, 3.0), (2, T, 1, 3.0), (1, T - 30, 63, 0.75)]
+    return p
+
+
+def run_device(torch, x, widths, thr, R, stream=None, stride_pad=0, **kw):
+    """engine.single_pulse_device on the host rows x, optionally as slices of
+    a wider tensor (NaN between the rows) and on a side stream.  Returns
+    (events EVENT_DTYPE, best, kbest) as host arrays."""
+    from riptide_amd import engine
+    from riptide_amd.single_pulse import events_to_host
+    B, N = x.shape
+    if stride_pad:
+        wide = torch.full((B, N + stride_pad), float("nan"), dtype=torch.float32, device="cuda")
+        wide[:, :N] = torch.from_numpy(x)
+        d = wide[:, :N]
+        assert d.stride(0) == N + stride_pad
+    else:
+        d = torch.from_numpy(x).cuda()
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream())
+    ev, best, kbest = engine.single_pulse_device(d, widths, thr, radius=R, dense=True, stream=stream, **kw)
+    if stream is not None:
+        stream.synchronize()
+    return events_to_host(ev), best.cpu().numpy(), kbest.cpu().numpy()
+
+
+def assert_same_results(got, ref, what):
+    """(events, best, kbest) twice: the same bits."""
+    (ev, best, kbest), (rev, rbest, rkbest) = got, ref
+    assert best.shape == rbest.shape and kbest.shape == rkbest.shape, what
+    bad = np.flatnonzero(best.view(np.uint32).ravel() != rbest.view(np.uint32).ravel())
+    assert bad.size == 0, f"{what}: {bad.size} of {best.size} best values differ, first at {bad[:5]}"
+    bad = np.flatnonzero(kbest.ravel() != rkbest.ravel())
+    assert bad.size == 0, f"{what}: {bad.size} of {kbest.size} kbest values differ, first at {bad[:5]}"
+    assert events_equal(ev, rev), (what, ev.size, rev.size)
+
+
+def assert_device_is_host(torch, x, widths, thr, R, stream=None, stride_pad=0, numpy_too=False, **kw):
+    """best, kbest and the events of the device call equal the host
+    specification's, bit for bit, and with numpy_too (dyadic rows only) the
+    restatement's above as well.  Returns the host events."""
+    from riptide_amd import single_pulse
+    got = run_device(torch, x, widths, thr, R, stream=stream, stride_pad=stride_pad, **kw)
+    host = single_pulse.single_pulse_host(x, widths, thr, radius=R, dense=True)
+    assert_same_results(got, host, "device against the host specification")
+    if numpy_too:
+        assert_same_results(got, numpy_single_pulse(x, widths, thr, R), "device against the numpy restatement")
+    return host[0]

@@ -26,40 +26,8 @@ def to_host(ev):
     return events_to_host(ev)
 
 
-def assert_device_is_host(torch, x, widths, thr, R, stream=None, stride_pad=0, **kw):
-    """best, kbest and the events of the device call equal the host
-    specification's, bit for bit.  Returns the host events."""
-    from riptide_amd import engine, single_pulse
-    B, N = x.shape
-    if stride_pad:
-        wide = torch.full((B, N + stride_pad), float("nan"), dtype=torch.float32, device="cuda")
-        wide[:, :N] = torch.from_numpy(x)
-        d = wide[:, :N]
-        assert d.stride(0) == N + stride_pad
-    else:
-        d = torch.from_numpy(x).cuda()
-    if stream is not None:
-        stream.wait_stream(torch.cuda.current_stream())
-    ev, best, kbest = engine.single_pulse_device(d, widths, thr, radius=R, dense=True, stream=stream, **kw)
-    if stream is not None:
-        stream.synchronize()
-    hev, hbest, hkbest = single_pulse.single_pulse_host(x, widths, thr, radius=R, dense=True)
-    best, kbest = best.cpu().numpy(), kbest.cpu().numpy()
-    bad = np.flatnonzero(best.view(np.uint32).ravel() != hbest.view(np.uint32).ravel())
-    assert bad.size == 0, f"{bad.size} of {best.size} best values differ, first at {bad[:5]}"
-    assert np.array_equal(kbest, hkbest)
-    got = to_host(ev)
-    assert pc.events_equal(got, hev), (got.size, hev.size)
-    return hev
-
-
-def tile_pulses(N, T):
-    """Pulses that hang over the row's ends, across the first tile boundary
-    and inside (no sample gets more than 4 in all: dyadic rows stay in range)."""
-    p = [(2, -3, 9, 1.5), (3, N - 4, 9, 1.5), (0, N // 2, 5, 2.0)]
-    if N > T + 8:
-        p += [(0, T - 3, 7, 1.75), (1, T - 1, 1, 3.0), (2, T, 1, 3.0), (1, T - 30, 63, 0.75)]
-    return p
+assert_device_is_host = pc.assert_device_is_host
+tile_pulses = pc.tile_pulses
 
 
 def with_end_events(x):

@@ -149,6 +149,41 @@ def test_errors(sp):
     assert ev.size == 0
 
 
+PLAN_WMAX = (1, 7, 64, 1023, 1024, 1025, 2048, 3000, 4096, 5000, 6144)
+PLAN_RADIUS = (0, 1, 64, 512, 1024, 2048, 3000, 4096, 5000, 6144)
+
+
+def test_plan_table(sp):
+    """engine.pulse_plan (rt_single_pulse_plan, the device form's planner)
+    over a table of (largest width, radius): the tile fits the 160 KiB of
+    LDS, the chunk is the whole T + 2R rounded up to segments or the largest
+    multiple of 1024 that fits by the header's own formula, and a full tile
+    takes 1, 2, 3, 4 or 6 chunks: the classes test_gpu_pulse_paths.py runs."""
+    from riptide_amd import engine
+    T, lds_max, seg_bytes = engine.PULSE_TILE, 160 << 10, 8 * 1088
+    classes = set()
+    for wmax in PLAN_WMAX:
+        for R in PLAN_RADIUS:
+            chunk, segs, lds = engine.pulse_plan(wmax, R)
+            what = (wmax, R, chunk, segs, lds)
+            fixed = 4 * (T + 2 * R) + 2 * T + 320
+            assert lds <= lds_max, what
+            assert chunk > 0 and chunk % 1024 == 0, what
+            assert segs == (chunk + wmax + 2045) // 1024, what
+            assert lds == fixed + seg_bytes * segs, what
+            whole = -(-(T + 2 * R) // 1024) * 1024
+            more = fixed + seg_bytes * ((chunk + 1024 + wmax + 2045) // 1024)
+            assert chunk == whole or (chunk < whole and more > lds_max), what
+            classes.add(-(-(T + 2 * R) // chunk))
+    assert classes == {1, 2, 3, 4, 6}
+    # the plan nearest the limit, and the limits themselves
+    assert engine.pulse_plan(5000, 2048) == (8192, 14, 163136)
+    assert engine.pulse_plan(6144, 6144) == (3072, 10, 161088)
+    for bad in ((0, 4), (engine.PULSE_MAX_WIDTH + 1, 4), (64, engine.PULSE_MAX_WIDTH + 1), (-1, 4), (64, -1)):
+        with pytest.raises(ValueError):
+            engine.pulse_plan(*bad)
+
+
 def test_generate_pulse_widths(sp):
     assert sp.generate_pulse_widths(1).tolist() == [1]
     assert sp.generate_pulse_widths(64).tolist() == [1, 2, 3, 4, 6, 9, 13, 19, 28, 42, 63]
