@@ -696,6 +696,21 @@ int rt_dedisperse_workspace_bytes(int dtype, size_t nsamp_blk, size_t nchans, si
 int rt_dedisperse_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans, const int32_t* d_delays,
                          const uint8_t* d_mask, size_t ndm, int64_t max_delay, float* d_out, size_t out_stride,
                          size_t out_offset, void* d_workspace, size_t workspace_bytes, void* stream);
+/* Host only, read-only, no device call: which of its two read paths the sum
+ * kernel of rt_dedisperse_device takes for one channel of one tile of 16 DMs x
+ * 256 outputs (dedisp_span, dedisp_types.hpp: the kernel's own rule).  esize
+ * is the bytes of a workspace row's element: 1 for 8-bit and 1/2/4-bit data, 4
+ * for float32 and 16-bit data and for every type under RT_DEDISP_ZERO_DM.  lo
+ * and hi are the smallest and largest delay, clamped to [0, max_delay], of the
+ * tile's 16 DM rows in that channel (a partial tile repeats the last DM).
+ * *ndw: the dwords from the one holding the first element read to the last
+ * one read, (256 + hi - (lo & ~3) + 3) / 4 for esize 1 and 256 + hi - lo for
+ * esize 4.  *staged: 1 when they are staged in LDS, ndw <= 264 (esize 1: hi -
+ * (lo & ~3) <= 800) or ndw <= 520 (esize 4: hi - lo <= 264); 0 when the
+ * channel is read from the workspace row directly.  Both paths give the same
+ * bits.  Either pointer may be NULL.  RT_EINVAL for an esize other than 1 or
+ * 4, lo < 0, lo > hi, hi >= 2^31. */
+int rt_dedisperse_span_plan(size_t esize, int64_t lo, int64_t hi, size_t* ndw, int* staged);
 /* Host-buffer form: uploads x [nsamp, nchans], the delays (int64, as
  * rt_dedisperse_delays writes them) and the mask, runs the kernels, copies out
  * [ndm, nsamp - max_delay] back.  Synchronous. */

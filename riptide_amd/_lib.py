@@ -129,8 +129,10 @@ _SIGNATURES = {
     # workspace, workspace bytes, stream
     "rt_dedisperse_device": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _c_sz, ctypes.c_int64, _vp, _c_sz, _c_sz,
                                     _vp, _c_sz, _vp]),
+    # esize, lo, hi, ndw, staged
+    "rt_dedisperse_span_plan": (_c_i, [_c_sz, ctypes.c_int64, ctypes.c_int64, _psz, ctypes.POINTER(_c_i)]),
     # x, dtype, nsamp, nchans, delays (int64), mask, ndm, max_delay, out
-    "rt_dedisperse": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _c_sz, ctypes.c_int64, _vp]),
+    "rt_dedisperse":(_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _c_sz, ctypes.c_int64, _vp]),
     # the four above with a trailing flags argument (before `bytes` in the workspace query)
     "rt_dedisperse_host_opt": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _c_sz, ctypes.c_int64, _c_sz, _vp,
                                       ctypes.c_uint32]),

@@ -12,7 +12,8 @@
 // sample types) against a recount, the same shapes with RT_DEDISP_ZERO_DM
 // and through the statistics, the packed sample types (1, 2, 4 and 16 bit:
 // whole-byte rows of 1 to 18 bytes, blocks that end on the array's last byte),
-// then every error return.  Exit status 0 iff all agree.
+// then every error return, and the staging rule's table and refusals
+// (rt_dedisperse_span_plan).  Exit status 0 iff all agree.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -432,6 +433,49 @@ void run_errors()
            "nchans == 0 (host)");
 }
 
+// rt_dedisperse_span_plan against the closed forms riptide_amd.h states: every
+// lo % 4, spreads around both thresholds, large delays, and the refusals
+void run_span_plan()
+{
+    const int64_t bases[] = {0, 1, 2, 3, 4, 7, 1000, 1001, 1002, 1003, 2147482000ll};
+    for (int64_t lo : bases)
+        for (int64_t spread = 0; spread <= 1200; ++spread) {
+            const int64_t hi = lo + spread;
+            if (hi >= 2147483648ll) break;
+            size_t ndw = 0;
+            int staged = -1;
+            expect(rt_dedisperse_span_plan(1, lo, hi, &ndw, &staged) == RT_OK, "span plan, 8-bit rows");
+            const int64_t w8 = hi - (lo & ~(int64_t)3);
+            expect((int64_t)ndw == (256 + w8 + 3) / 4 && staged == (w8 <= 800), "span plan table, 8-bit rows");
+            ndw = 0;
+            staged = -1;
+            expect(rt_dedisperse_span_plan(4, lo, hi, &ndw, &staged) == RT_OK, "span plan, float rows");
+            expect((int64_t)ndw == 256 + spread && staged == (spread <= 264), "span plan table, float rows");
+        }
+    size_t ndw = 0;
+    int staged = -1;
+    expect(rt_dedisperse_span_plan(1, 0, 800, &ndw, &staged) == RT_OK && ndw == 264 && staged == 1,
+           "span plan: the last staged 8-bit span is 264 dwords");
+    expect(rt_dedisperse_span_plan(1, 3, 800, &ndw, &staged) == RT_OK && ndw == 264 && staged == 1,
+           "span plan: lo % 4 == 3 stages a spread of 797");
+    expect(rt_dedisperse_span_plan(1, 3, 801, &ndw, &staged) == RT_OK && ndw == 265 && staged == 0,
+           "span plan: lo % 4 == 3 reads a spread of 798 directly");
+    expect(rt_dedisperse_span_plan(4, 5, 269, &ndw, &staged) == RT_OK && ndw == 520 && staged == 1,
+           "span plan: the last staged float span is 520 dwords");
+    expect(rt_dedisperse_span_plan(4, 5, 270, &ndw, &staged) == RT_OK && ndw == 521 && staged == 0,
+           "span plan: a float spread of 265 is read directly");
+    expect(rt_dedisperse_span_plan(1, 0, 0, nullptr, nullptr) == RT_OK, "span plan: null outputs");
+    expect(rt_dedisperse_span_plan(1, 0, 2147483647ll, &ndw, &staged) == RT_OK && staged == 0,
+           "span plan: the largest delay");
+    expect(rt_dedisperse_span_plan(0, 0, 1, &ndw, &staged) == RT_EINVAL, "span plan: esize 0");
+    expect(rt_dedisperse_span_plan(2, 0, 1, &ndw, &staged) == RT_EINVAL, "span plan: esize 2");
+    expect(rt_dedisperse_span_plan(8, 0, 1, &ndw, &staged) == RT_EINVAL, "span plan: esize 8");
+    expect(rt_dedisperse_span_plan(1, 5, 4, &ndw, &staged) == RT_EINVAL, "span plan: lo > hi");
+    expect(rt_dedisperse_span_plan(1, -1, 4, &ndw, &staged) == RT_EINVAL, "span plan: negative lo");
+    expect(rt_dedisperse_span_plan(4, -3, -2, &ndw, &staged) == RT_EINVAL, "span plan: negative delays");
+    expect(rt_dedisperse_span_plan(4, 0, 2147483648ll, &ndw, &staged) == RT_EINVAL, "span plan: hi of 2^31");
+}
+
 }  // namespace
 
 int main()
@@ -462,6 +506,7 @@ int main()
     run_errors();
     run_rfi_errors();
     run_packed_errors();
+    run_span_plan();
     if (fails)
         std::printf("dedisp_check: %d failures\n", fails);
     else

@@ -307,6 +307,20 @@ int rt_dedisperse_bands_host(const void* x, int dtype, size_t nsamp, size_t ncha
     });
 }
 
+int rt_dedisperse_span_plan(size_t esize, int64_t lo, int64_t hi, size_t* ndw, int* staged)
+{
+    return guarded([&] {
+        if (esize != 1 && esize != 4)
+            throw std::invalid_argument("span_plan: esize must be 1 (8-bit rows) or 4 (float rows)");
+        if (lo < 0 || hi < lo || hi >= 2147483648ll)
+            throw std::invalid_argument("span_plan: the delays must be 0 <= lo <= hi < 2^31");
+        const DedispSpan sp = dedisp_span((uint32_t)esize, (uint32_t)lo, (uint32_t)hi);
+        if (ndw) *ndw = sp.ndw;
+        if (staged) *staged = sp.direct ? 0 : 1;
+        return RT_OK;
+    });
+}
+
 int rt_zero_dm_mean_host(const void* x, int dtype, size_t nsamp, size_t nchans, const uint8_t* mask, float* m)
 {
     return guarded([&] {

@@ -65,7 +65,7 @@ namespace {
 
 constexpr uint32_t kDdThreads = 256;
 constexpr uint32_t kDdWaves = 4;
-constexpr uint32_t kDdTile = 256;       // outputs of a time tile: 4 per lane
+constexpr uint32_t kDdTile = kDedispTile;   // outputs of a time tile (256): 4 per lane
 constexpr uint32_t kDdPerWave = 4;      // DMs a wave sums
 constexpr uint32_t kDdDms = kDdWaves * kDdPerWave;
 constexpr uint32_t kDdChans = 16;       // channels staged per step
@@ -73,11 +73,14 @@ constexpr uint32_t kDdSkip = 0xFFFFFFFFu;     // channel masked or past nchans
 constexpr uint32_t kDdDirect = 0xFFFFFFFEu;   // span too long to stage: read from the workspace row
 
 // dwords of one channel's staged span: the time tile plus the spread of the
-// tile's delays (up to 794 samples of 8-bit data, 264 of float data; a wider
-// spread takes the direct path)
+// tile's delays.  The numbers and the rule are dedisp_types.hpp's (dedisp_span,
+// which rt_dedisperse_span_plan restates for the tests): 8-bit data is staged
+// up to a spread hi - (lo & ~3) of 800 samples, that is hi - lo of 800, 799,
+// 798 or 797 for lo % 4 = 0 .. 3, float data up to hi - lo of 264; a wider
+// spread takes the direct path
 template <class T>
 struct DdSpan {
-    static constexpr uint32_t dwords = sizeof(T) == 1 ? 264 : 520;
+    static constexpr uint32_t dwords = dedisp_span_dwords(sizeof(T));
 };
 
 // ---- the block mask (rt_block_mask, riptide_amd.h)
@@ -677,10 +680,10 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_sum_kernel(
                 lo = min(lo, sdel[dd][cc]);
                 hi = max(hi, sdel[dd][cc]);
             }
-            const uint32_t e0 = (t0 + (uint32_t)lo) & ~(kE - 1);   // first element staged
-            const uint32_t e1 = t0 + kDdTile + (uint32_t)hi;        // one past the last element read
-            const uint32_t ndw = (e1 - e0 + kE - 1) / kE;
-            if (ndw > kSpan) {
+            // first element staged, dwords up to one past the last element read, and whether they fit
+            const DedispSpan sp = dedisp_span(sizeof(T), t0 + (uint32_t)lo, t0 + (uint32_t)hi);
+            const uint32_t e0 = sp.first, ndw = sp.ndw;
+            if (sp.direct) {
                 if (lane == 0) sbase[cc] = kDdDirect;
                 continue;
             }

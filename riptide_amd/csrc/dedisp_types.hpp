@@ -68,6 +68,43 @@ inline void dedisp_check_dtype(int dtype, size_t nchans, bool cap, const char* w
     if (dedisp_packed_bits(dtype)) dedisp_row_bytes(dtype, nchans);
 }
 
+// ---- the staging rule of dedisp_sum_kernel (dedisp_kernels.hip), which takes
+// these numbers and dedisp_span from here; rt_dedisperse_span_plan
+// (dedisp_host.cpp) is the same function, for tests to name the path they run.
+// A workgroup sums kDedispTile outputs from t0, a multiple of kDedispTile, of
+// 16 DMs.  Per channel, with lo and hi the smallest and largest clamped delay
+// of those DMs, it reads the elements [t0 + lo, t0 + kDedispTile + hi) of the
+// channel's row.  That span, from the dword holding its first element, is
+// staged in LDS when it fits the dwords below, and read from the workspace row
+// directly otherwise:
+//   8-bit rows  staged iff hi - (lo & ~3) <= 800: a spread hi - lo of up to
+//               800, 799, 798, 797 samples for lo % 4 = 0, 1, 2, 3
+//   float rows  staged iff hi - lo <= 264
+constexpr uint32_t kDedispTile = 256;            // outputs of a time tile
+constexpr uint32_t kDedispSpanDwords8 = 264;     // staged dwords of a channel, 8-bit rows
+constexpr uint32_t kDedispSpanDwords32 = 520;    // the same, float rows
+
+constexpr uint32_t dedisp_span_dwords(uint32_t esize) { return esize == 1 ? kDedispSpanDwords8 : kDedispSpanDwords32; }
+
+struct DedispSpan {
+    uint32_t first;   // first element staged: the span's first element rounded down to a dword
+    uint32_t ndw;     // dwords from there to the span's end
+    bool direct;      // ndw is more than the LDS span holds: the channel is read from its row
+};
+
+// esize: bytes of a row's element, 1 or 4.  e_lo = t0 + lo and e_hi = t0 + hi
+// in the kernel; t0 is a multiple of 256, so the plan of (lo, hi) alone has
+// the same ndw and path (first is then relative to t0).  e_hi + 256 must not
+// overflow 32 bits: blocks and delays are below 2^31.
+constexpr DedispSpan dedisp_span(uint32_t esize, uint32_t e_lo, uint32_t e_hi)
+{
+    const uint32_t per = 4 / esize;                  // elements per dword
+    const uint32_t e0 = e_lo & ~(per - 1);           // first element staged
+    const uint32_t e1 = e_hi + kDedispTile;          // one past the last element read
+    const uint32_t ndw = (e1 - e0 + per - 1) / per;
+    return DedispSpan{e0, ndw, ndw > dedisp_span_dwords(esize)};
+}
+
 // a band table in host memory: every band a channel range lo <= hi <= nchans
 inline void dedisp_check_band_table(const uint32_t* bands, size_t nbands, size_t nchans)
 {

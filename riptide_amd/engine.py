@@ -530,6 +530,21 @@ def dedisperse_workspace_bytes(dtype, nsamp_blk, nchans, zero_dm=False, nbits=No
     return b.value
 
 
+def dedisperse_span_plan(esize, lo, hi):
+    """(ndw, staged) of the dedispersion sum kernel for one channel of one
+    tile of 16 DMs x 256 outputs (rt_dedisperse_span_plan; no device call):
+    esize is 1 for 8-bit rows (uint8, int8, 1/2/4-bit data) and 4 for float
+    rows (float32, 16-bit data, everything under zero_dm); lo and hi are the
+    smallest and largest delay, clamped to [0, max_delay], of the tile's DMs
+    in that channel.  ndw is the dwords the channel's span takes; staged says
+    whether they go through LDS (8-bit rows: hi - (lo & ~3) <= 800; float
+    rows: hi - lo <= 264) or the channel is read from its workspace row
+    directly.  ValueError for another esize, lo < 0, lo > hi or hi >= 2^31."""
+    ndw, staged = ctypes.c_size_t(), ctypes.c_int()
+    _check(_L.rt_dedisperse_span_plan(int(esize), int(lo), int(hi), ctypes.byref(ndw), ctypes.byref(staged)))
+    return ndw.value, bool(staged.value)
+
+
 def _dedisp_block(block, nbits=None):
     """(dtype name, nsamp_blk, nchans) of a block argument, validated.  With
     nbits the block is packed rows, uint8 [nsamp_blk, row_bytes] (any byte

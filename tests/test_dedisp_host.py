@@ -200,3 +200,129 @@ def test_sanitizer_program():
     r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "runtime error" not in r.stderr, (r.stdout[-3000:], r.stderr[-3000:])
     assert r.stdout.strip().endswith("dedisp_check OK")
+
+
+# ------------------------------------------- the sum kernel's staging rule
+def test_span_plan_table():
+    """engine.dedisperse_span_plan (rt_dedisperse_span_plan: dedisp_span of
+    dedisp_types.hpp, the rule dedisp_sum_kernel itself calls) against the
+    closed forms, for both element sizes, every lo % 4 and every spread from 0
+    to past both thresholds: 8-bit rows are staged iff hi - (lo & ~3) <= 800,
+    float rows iff hi - lo <= 264, and the full spans of 264 and 520 dwords are
+    reached exactly."""
+    from riptide_amd import engine
+    seen = {1: set(), 4: set()}
+    for lo in (0, 1, 2, 3, 4, 5, 6, 7, 1000, 1001, 1002, 1003, 2 ** 31 - 1300):
+        for spread in list(range(0, 12)) + list(range(255, 275)) + list(range(790, 810)):
+            hi = lo + spread
+            ndw, staged = engine.dedisperse_span_plan(1, lo, hi)
+            w8 = hi - (lo & ~3)
+            assert ndw == (256 + w8 + 3) // 4 and staged == (w8 <= 800), (lo, hi, ndw, staged)
+            assert staged == (ndw <= dc.SPAN_DWORDS[1])
+            seen[1].add((ndw, staged))
+            ndw, staged = engine.dedisperse_span_plan(4, lo, hi)
+            assert ndw == 256 + spread and staged == (spread <= 264), (lo, hi, ndw, staged)
+            assert staged == (ndw <= dc.SPAN_DWORDS[4])
+            seen[4].add((ndw, staged))
+    assert {(264, True), (265, False)} <= seen[1] and {(520, True), (521, False)} <= seen[4]
+    # the last staged spread hi - lo of 8-bit rows: 800, 799, 798, 797 by lo % 4
+    for r in range(4):
+        assert engine.dedisperse_span_plan(1, 8 + r, 8 + r + 800 - r) == (264, True)
+        assert engine.dedisperse_span_plan(1, 8 + r, 8 + r + 801 - r) == (265, False)
+    assert dc.LAST_STAGED == {1: 4 * dc.SPAN_DWORDS[1] - dc.TIME_TILE, 4: dc.SPAN_DWORDS[4] - dc.TIME_TILE}
+    assert engine.dedisperse_span_plan(1, 0, 2 ** 31 - 1) == ((256 + 2 ** 31 - 1 + 3) // 4, False)
+    for bad in ((0, 0, 1), (2, 0, 1), (8, 0, 1), (-1, 0, 1), (1, 5, 4), (4, 5, 4), (1, -1, 4), (4, -3, -2),
+                (1, 0, 2 ** 31), (4, -2 ** 31, 0)):
+        with pytest.raises(ValueError, match="span_plan"):
+            engine.dedisperse_span_plan(*bad)
+
+
+def test_path_tables():
+    """The preconditions of dedisp_common's hand-made delay tables, on numpy
+    and the span plan alone: what the GPU path tests rely on is a property of
+    their inputs."""
+    tables = dc.path_tables()
+    assert {"mixed", "residues", "clamp"} <= set().union(*(t[4] for t in tables.values()))
+    for name, (delays, mask, max_delay, esize, claims) in tables.items():
+        assert delays.dtype == np.int64 and delays.ndim == 2, name
+        assert delays.shape[1] <= 40 and delays.shape[0] <= 33 and max_delay + 300 <= 1500, name
+        inside = (delays >= 0) & (delays <= max_delay)
+        if "clamp" in claims:
+            wild = delays[~inside]
+            assert {-1, -2 ** 31, max_delay + 1, 2 ** 31 - 1} == set(int(v) for v in wild), name
+            assert np.abs(delays).max() < 2 ** 31 + 1 and delays.min() >= -2 ** 31      # the table fits int32
+            paths = dc.tile_paths(delays, max_delay, esize)
+            hit = (~inside).any(axis=0)
+            assert "S" in paths[0, hit] and "D" in paths[0, hit], name
+        else:
+            assert inside.all(), name
+        paths = dc.tile_paths(delays, max_delay, esize, mask)
+        if name.startswith("threshold"):
+            # class S channels sit exactly at the last staged span, D one sample past it
+            from riptide_amd import engine
+            clipped = delays[:dc.DM_TILE]
+            for c in range(delays.shape[1]):
+                ndw, staged = engine.dedisperse_span_plan(esize, clipped[:, c].min(), clipped[:, c].max())
+                cls = dc.THRESHOLD_CLASSES[c % len(dc.THRESHOLD_CLASSES)]
+                assert (ndw, staged) == ((dc.SPAN_DWORDS[esize], True) if cls == "S" else
+                                         (dc.SPAN_DWORDS[esize] + 1, False)), (name, c)
+                assert clipped[0, c] == clipped[:, c].min() and clipped[-1, c] == clipped[:, c].max()
+            assert len(set(int(v) % 4 for v in clipped.min(axis=0))) == 1
+            # the partial step of four channels holds both paths
+            assert {"S", "D"} <= set(paths[0, dc.CHAN_STEP:dc.CHAN_STEP + 4]), name
+            if delays.shape[0] > dc.DM_TILE:
+                assert set(paths[1]) <= {"S", "M"}, name
+        if "mixed" in claims:
+            assert mask is not None and {"S", "D", "M"} <= set(paths[0, :dc.CHAN_STEP]), name
+        if "residues" in claims:
+            assert esize == 1 and set(paths.ravel()) == {"S"}, name
+            first = delays[:dc.DM_TILE]
+            lo = first.min(axis=0)
+            pairs = {(int(l) & 3, int(v - l) & 3) for row in first for v, l in zip(row, lo)}
+            assert len(pairs) == 16, name
+            # a full step of 16 channels alone holds them all, and reads at every byte residue p & 3
+            step = {(int(l) & 3, int(v - (l & ~3)) & 3) for row in first for v, l in zip(row[:16], lo[:16])}
+            assert len(step) == 16, name
+
+
+BAND_TABLE = np.array([[0, 20], [3, 19], [16, 20], [15, 17], [9, 9], [11, 13]], dtype=np.uint32)
+
+
+@pytest.mark.parametrize("kind", ["float32", "u16", "uint8-zero_dm", "int8-zero_dm", "u4-zero_dm"])
+def test_float32_restatement_equals_the_host_specification(kind):
+    """dc.numpy_dedisperse_f32 -- a float32 accumulator from +0.0, one float32
+    addition per unmasked channel in ascending order, under the zero-DM filter
+    of float32(x) - m -- has the bits of dedisperse_host and
+    dedisperse_bands_host on the hand-made tables: the GPU tests' float
+    reference does not rest on the project's C++."""
+    from riptide_amd.dedispersion import dedisperse_bands_host, dedisperse_host
+    kind, _, zero_dm = kind.partition("-")
+    for name in ("threshold-e4-r1-ndm17", "threshold-e4-r2-ndm5", "residues-20ch"):
+        delays, mask, max_delay, _, _ = dc.path_tables()[name]
+        nout = 70
+        x, vals, nbits = dc.kind_samples(np.random.RandomState(len(name)), max_delay + nout, delays.shape[1], kind)
+        for m in (None, mask) if mask is not None else (None,):
+            mean = dc.numpy_zero_dm_mean(vals, m) if zero_dm else None
+            if zero_dm:
+                from riptide_amd.dedispersion import zero_dm_mean_host
+                assert np.array_equal(mean.view(np.uint32), zero_dm_mean_host(x, mask=m, nbits=nbits).view(np.uint32))
+            host = dedisperse_host(x, delays, max_delay, mask=m, nout=nout, zero_dm=bool(zero_dm), nbits=nbits)
+            dc.assert_same_bits(host, dc.numpy_dedisperse_f32(vals, delays, nout, m, mean=mean), f"{name}, plain")
+            host = dedisperse_bands_host(x, delays, max_delay, BAND_TABLE, mask=m, nout=nout, zero_dm=bool(zero_dm),
+                                         nbits=nbits)
+            dc.assert_same_bits(host, dc.numpy_dedisperse_f32(vals, delays, nout, m, bands=BAND_TABLE, mean=mean),
+                                f"{name}, bands")
+            assert not host[:, 4].any() and not np.signbit(host[:, 4]).any()      # the empty band: +0.0
+
+
+def test_host_refuses_the_unclipped_table():
+    """The device call clamps delays outside [0, max_delay] as it reads them
+    (test_gpu_dedisp_paths.py::test_delay_clamp); the host specification
+    refuses such a table and takes the clipped one."""
+    from riptide_amd.dedispersion import dedisperse_host
+    for esize, dtype in ((1, np.uint8), (4, np.float32)):
+        wild, max_delay = dc.clamp_table(esize)
+        x = dc.samples(np.random.RandomState(esize), max_delay + 10, wild.shape[1], dtype)
+        with pytest.raises(ValueError, match="outside \\[0, max_delay\\]"):
+            dedisperse_host(x, wild, max_delay)
+        assert dedisperse_host(x, np.clip(wild, 0, max_delay), max_delay).shape == (wild.shape[0], 10)

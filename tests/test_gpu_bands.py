@@ -46,12 +46,17 @@ def run_plain(torch, x, delays, max_delay, mask=None, **kw):
 
 def check(out, x, delays, max_delay, nout, bands, mask=None):
     """Integer data: the host specification's bits.  float32: the bound against
-    the float64 sums (and the host specification is inside it too)."""
+    the float64 sums (and the host specification is inside it too), and the
+    bits of dc.numpy_dedisperse_f32 -- the float32 additions in ascending
+    channel order within each band -- which are the host specification's."""
     from riptide_amd.dedispersion import dedisperse_bands_host
     host = dedisperse_bands_host(x, delays, max_delay, bands, mask=mask, nout=nout)
     if x.dtype == np.float32:
         assert_band_rows(out, x, delays, nout, bands, mask)
         assert_band_rows(host, x, delays, nout, bands, mask)
+        ref = dc.numpy_dedisperse_f32(x, delays, nout, mask, bands=bands)
+        dc.assert_same_bits(host, ref, "host specification, float32 sums in channel order")
+        dc.assert_same_bits(out, ref, "float32 sums in channel order")
     else:
         assert out.dtype == np.float32 and np.array_equal(out, host), \
             f"{int((out != host).sum())} of {out.size} sums differ"

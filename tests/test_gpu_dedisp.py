@@ -1,7 +1,8 @@
 """GPU tests of the dedispersion kernels (csrc/dedisp_kernels.hip) and the
 filterbank search path built on them.  The device result is compared with the
-numpy restatement of dedisp_common: bit for bit for 8-bit data, within
-nchans * 2^-24 * sum |x| for float32.  The delays come from
+numpy restatement of dedisp_common: bit for bit for 8-bit data; for float32
+within nchans * 2^-24 * sum |x| of the float64 sums and bit for bit with the
+float32 additions in channel order.  The delays come from
 dispersion_delays, which test_dedisp_host.py pins to its formula."""
 import os
 import socket
