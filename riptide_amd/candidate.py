@@ -222,7 +222,7 @@ def build_candidates_filterbank(clusters, fb_or_fname, range_confs, deredden_par
     carries the result as `refined`."""
     import torch
     from . import engine
-    from .dedispersion import DEFAULT_BUDGET_BYTES, KDM, band_edges, band_series, dispersion_delays
+    from .dedispersion import DEFAULT_BUDGET_BYTES, KDM, band_edges, band_series, check_max_delay, dispersion_delays
     from .reading import Filterbank, open_filterbank
     fb = fb_or_fname if isinstance(fb_or_fname, Filterbank) else open_filterbank(fb_or_fname)
     kdm = KDM if kdm is None else float(kdm)
@@ -237,8 +237,7 @@ def build_candidates_filterbank(clusters, fb_or_fname, range_confs, deredden_par
     dms = list(by_dm)
     log.debug(f"{len(ordered)} candidates to build from {len(dms)} DMs of {fb.header.fname}")
     _, max_delay = dispersion_delays(fb.freqs, dms, fb.tsamp, kdm)
-    if max_delay >= fb.nsamp:
-        raise ValueError(f"the largest delay ({max_delay} samples) is not below the {fb.nsamp} samples of the file")
+    check_max_delay(max_delay, fb.nsamp)
     nout = fb.nsamp - max_delay if nout is None else int(nout)
     bands = np.concatenate([band_edges(fb.nchans, nsub), np.array([[0, fb.nchans]], dtype=np.uint32)])
     nbands = bands.shape[0]

@@ -100,6 +100,13 @@ def _host_block(data, nbits):
     return data, DEDISP_DTYPES[data.dtype.name], data.shape[0], data.shape[1]
 
 
+def check_max_delay(max_delay, nsamp, what="file"):
+    """ValueError unless the `nsamp` samples of the file (or `what`) outlast
+    the largest delay of a DM list."""
+    if max_delay >= nsamp:
+        raise ValueError(f"the largest delay ({max_delay} samples) is not below the {nsamp} samples of the {what}")
+
+
 def _checked_data(data):
     data = np.asarray(data)
     if data.ndim != 2 or data.dtype.name not in DEDISP_DTYPES:
@@ -164,8 +171,7 @@ def _dedisperse(data, freqs, tsamp, dms, bands, mask, kdm, zero_dm, nbits):
     mask = _checked_mask(mask, nchans)
     if bands is not None:
         bands = _checked_bands(bands, nchans)
-    if max_delay >= nsamp:
-        raise ValueError(f"the largest delay ({max_delay} samples) is not below the {nsamp} samples of the data")
+    check_max_delay(max_delay, nsamp, "data")
     ndm, nout = delays.shape[0], nsamp - max_delay
     out = np.empty((ndm, nout) if bands is None else (ndm, bands.shape[0], nout), dtype=np.float32)
     head = (_lib.ptr(data), code, nsamp, nchans, _lib.ptr(delays), None if mask is None else _lib.ptr(mask), ndm)
@@ -363,8 +369,8 @@ def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, n
     per call."""
     import torch
     from . import engine
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else
-                       (device.index if isinstance(device, torch.device) else int(device)))
+    from ._args import resolve_device
+    dev = resolve_device(device)
     nsamp, nchans = fb.nsamp, fb.nchans
     nbits = _checked_sample_type(fb)
     row_elems, dtype = _gulp_layout(fb)
@@ -373,8 +379,7 @@ def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, n
                          "(255 * nchans must be below 2^24)")
     delays, max_delay = dispersion_delays(fb.freqs, dms, fb.tsamp, kdm)
     mask = _checked_mask(mask, nchans)
-    if max_delay >= nsamp:
-        raise ValueError(f"the largest delay ({max_delay} samples) is not below the {nsamp} samples of the file")
+    check_max_delay(max_delay, nsamp)
     full = nsamp - max_delay
     nout = full if nout is None else int(nout)
     if not 0 < nout <= full:

@@ -13,6 +13,8 @@ as WorkerPool.process_fname does) and device peak detection, and the
 per-rank peak lists -- tagged with their trial index -- are gathered once at
 the end (KB-scale, latency-bound) and put back in trial order.
 """
+import contextlib
+import itertools
 import logging
 import os
 import typing
@@ -44,6 +46,37 @@ def _group_by_shape(samples, tsamps):
     for i, (x, ts) in enumerate(zip(samples, tsamps)):
         groups.setdefault((int(np.asarray(x).size), float(ts)), []).append(i)
     return groups
+
+
+def _pipelined(steps, detect):
+    """The slice pipeline of every search below: `steps` yields (tag, pending),
+    each made by queuing one slice's device work, and item k + 1 is pulled --
+    queued -- before detect runs on item k's pending: enqueue 0, enqueue 1,
+    detect 0, enqueue 2, detect 1, ..., detect n - 1, the device busy through
+    every detection's host stages.  Yields (tag, detected) in order."""
+    steps = iter(steps)
+    cur = next(steps, None)
+    while cur is not None:
+        nxt = next(steps, None)
+        yield cur[0], detect(cur[1])
+        cur = nxt
+
+
+@contextlib.contextmanager
+def _dedispersed(fb, dms, device, batch, **kwargs):
+    """Inside the scope `device` (None, an int or a torch.device) is the
+    current one and the file is dedispersed there at the trial DMs
+    (dedispersion.dedisperse_filterbank, which takes kwargs): yields (series
+    [ndm, nout] on the device, every trial's metadata, the [b0, b1) slices of
+    `batch` DMs)."""
+    import torch
+    from ._args import resolve_device
+    from .dedispersion import dedisperse_filterbank
+    dev = resolve_device(device)
+    with torch.cuda.device(dev):
+        series = dedisperse_filterbank(fb, dms, device=dev, **kwargs)
+        yield (series, [fb.metadata(dm) for dm in dms],
+               [(b0, min(b0 + batch, len(dms))) for b0 in range(0, len(dms), batch)])
 
 
 class EngineSearcher:
@@ -190,29 +223,26 @@ class EngineSearcher:
             for b0 in range(0, len(idx), self.batch):
                 batches.append((tsamp, idx[b0:b0 + self.batch]))
         per = [None] * len(samples)
-        state = {"next": 0, "pending": []}
 
-        def enqueue_one():
-            k = state["next"]
-            if k < len(batches):
-                tsamp, chunk = batches[k]
+        def steps():
+            for k, (tsamp, chunk) in enumerate(batches):
                 x = upload_samples([samples[i] for i in chunk], device=self.device)
                 if k + 1 == len(batches) and uploaded is not None:
                     uploaded()
-                state["pending"].append((chunk, self._enqueue(x, tsamp, [metadatas[i] for i in chunk])))
-                state["next"] = k + 1
+                yield chunk, self._enqueue(x, tsamp, [metadatas[i] for i in chunk])
 
-        def collect():
-            while state["pending"]:
-                enqueue_one()           # batch j + 1 queued before batch j's detection
-                chunk, pend = state["pending"].pop(0)
-                for i, peaks in zip(chunk, self._detect(pend)):
-                    per[i] = peaks
-            return per
-
-        enqueue_one()
+        queued = steps()
+        first = list(itertools.islice(queued, 1))       # the first batch is queued now, the rest by collect()
         if not batches and uploaded is not None:
             uploaded()
+        pipe = _pipelined(itertools.chain(first, queued), self._detect)
+
+        def collect():
+            for chunk, peaks in pipe:
+                for i, p in zip(chunk, peaks):
+                    per[i] = p
+            return per
+
         return collect
 
     def search_samples(self, samples, tsamps, metadatas):
@@ -246,29 +276,46 @@ class EngineSearcher:
         pulses), the SinglePulse list of single_pulse.cluster_events over all
         DMs; the events behind them (series = index into dms) are kept in
         self.pulse_events."""
-        import torch
-        from .dedispersion import KDM, dedisperse_filterbank
+        from . import engine, single_pulse
+        from .dedispersion import KDM
         kdm = KDM if kdm is None else float(kdm)
         dms = [float(d) for d in dms]
-        if pulses is not None:
-            return self._search_filterbank_pulses(fb, dms, mask, nout, kdm, zero_dm, dict(pulses), block_mask)
+        kw = None if pulses is None else dict(pulses)
+        if kw is not None:
+            unknown = set(kw) - {"widths", "threshold", "radius", "time_radius", "dm_gap", "max_events"}
+            if unknown:
+                raise ValueError(f"unknown single-pulse parameters: {sorted(unknown)}")
+            self.pulse_events = np.empty(0, dtype=single_pulse.EVENT_DTYPE)
         if not dms:
-            return []
-        dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else
-                           (self.device.index if isinstance(self.device, torch.device) else int(self.device)))
-        with torch.cuda.device(dev):
-            series = dedisperse_filterbank(fb, dms, mask=mask, device=dev, nout=nout, kdm=kdm, zero_dm=zero_dm,
-                                           block_mask=block_mask)
-            metas = [fb.metadata(dm) for dm in dms]
-            slices = [(b0, min(b0 + self.batch, len(dms))) for b0 in range(0, len(dms), self.batch)]
-            per, pending = [], None
-            for b0, b1 in slices:
-                pend = self._enqueue(series[b0:b1], fb.tsamp, metas[b0:b1])
-                if pending is not None:
-                    per.extend(self._detect(pending))
-                pending = pend
-            per.extend(self._detect(pending))
-        return per
+            return [] if kw is None else ([], [])
+        per, parts = [], []
+        with _dedispersed(fb, dms, self.device, self.batch, mask=mask, nout=nout, kdm=kdm, zero_dm=zero_dm,
+                          block_mask=block_mask) as (series, metas, slices):
+            each = None
+            if kw is not None:
+                widths = single_pulse._default_widths(kw.get("widths"), series.shape[1])
+
+                def each(b0, pend):
+                    # the single-pulse search of a slice's normalised series, right behind its periodograms
+                    ev = engine.single_pulse_device(pend["x"], widths, kw.get("threshold", 8.0),
+                                                    radius=kw.get("radius"), max_events=kw.get("max_events", 1 << 20))
+                    parts.append(single_pulse.events_to_host(ev, b0))
+
+            def steps():
+                for b0, b1 in slices:
+                    pend = self._enqueue(series[b0:b1], fb.tsamp, metas[b0:b1])
+                    if each is not None:
+                        each(b0, pend)
+                    yield b0, pend
+
+            for _, peaks in _pipelined(steps(), self._detect):
+                per.extend(peaks)
+        if kw is None:
+            return per
+        self.pulse_events = np.concatenate(parts)
+        found = single_pulse.cluster_events(self.pulse_events, dms, fb.tsamp, time_radius=kw.get("time_radius"),
+                                            dm_gap=kw.get("dm_gap", 1), widths=widths)
+        return per, found
 
     def search_device_accel(self, raw, tsamp, metadatas, accels):
         """The acceleration search of a device batch raw [D, N] (float32), one
@@ -289,22 +336,18 @@ class EngineSearcher:
         factors = np.array([accel_factor(a, tsamp) for a in accels], dtype=np.float64)
         dms = [m.get("dm") for m in metadatas]
 
-        def collect(rows, pend):
-            for r, peaks in zip(rows, self._detect(pend)):
-                out[r // A].extend(AccelPeak(*p, accels[r % A]) for p in peaks)
+        def steps():
+            for d0 in range(0, D, self.batch):
+                d1 = min(d0 + self.batch, D)
+                x = self._normalise(raw[d0:d1], tsamp)
+                for r0 in range(d0 * A, d1 * A, self.batch):
+                    rows = np.arange(r0, min(r0 + self.batch, d1 * A))
+                    y = engine.resample_device(x, factors[rows % A], src=rows // A - d0)
+                    yield rows, self._enqueue_series(y, tsamp, [dms[r // A] for r in rows])
 
-        pending = None
-        for d0 in range(0, D, self.batch):
-            d1 = min(d0 + self.batch, D)
-            x = self._normalise(raw[d0:d1], tsamp)
-            for r0 in range(d0 * A, d1 * A, self.batch):
-                rows = np.arange(r0, min(r0 + self.batch, d1 * A))
-                y = engine.resample_device(x, factors[rows % A], src=rows // A - d0)
-                pend = self._enqueue_series(y, tsamp, [dms[r // A] for r in rows])
-                if pending is not None:
-                    collect(*pending)
-                pending = (rows, pend)
-        collect(*pending)
+        for rows, per in _pipelined(steps(), self._detect):
+            for r, peaks in zip(rows, per):
+                out[r // A].extend(AccelPeak(*p, accels[r % A]) for p in peaks)
         return out
 
     def search_filterbank_accel(self, fb, dms, accels, mask=None, nout=None, kdm=None, zero_dm=False,
@@ -315,54 +358,14 @@ class EngineSearcher:
         nout, kdm, zero_dm and block_mask as for search_filterbank.  With
         accels = [0.0] the peaks are search_filterbank's.  The single-pulse
         search (pulses=) is not combined with it."""
-        import torch
-        from .dedispersion import KDM, dedisperse_filterbank
+        from .dedispersion import KDM
         kdm = KDM if kdm is None else float(kdm)
         dms = [float(d) for d in dms]
         if not dms:
             return []
-        dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else
-                           (self.device.index if isinstance(self.device, torch.device) else int(self.device)))
-        with torch.cuda.device(dev):
-            series = dedisperse_filterbank(fb, dms, mask=mask, device=dev, nout=nout, kdm=kdm, zero_dm=zero_dm,
-                                           block_mask=block_mask)
-            return self.search_device_accel(series, fb.tsamp, [fb.metadata(dm) for dm in dms], accels)
-
-    def _search_filterbank_pulses(self, fb, dms, mask, nout, kdm, zero_dm, kw, block_mask=None):
-        """search_filterbank with the single-pulse search beside the
-        periodicity search: the same calls in the same order, and each slice's
-        normalised series handed to engine.single_pulse_device as well."""
-        import torch
-        from . import engine, single_pulse
-        from .dedispersion import dedisperse_filterbank
-        unknown = set(kw) - {"widths", "threshold", "radius", "time_radius", "dm_gap", "max_events"}
-        if unknown:
-            raise ValueError(f"unknown single-pulse parameters: {sorted(unknown)}")
-        self.pulse_events = np.empty(0, dtype=single_pulse.EVENT_DTYPE)
-        if not dms:
-            return [], []
-        dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else
-                           (self.device.index if isinstance(self.device, torch.device) else int(self.device)))
-        with torch.cuda.device(dev):
-            series = dedisperse_filterbank(fb, dms, mask=mask, device=dev, nout=nout, kdm=kdm, zero_dm=zero_dm,
-                                           block_mask=block_mask)
-            widths = single_pulse._default_widths(kw.get("widths"), series.shape[1])
-            metas = [fb.metadata(dm) for dm in dms]
-            slices = [(b0, min(b0 + self.batch, len(dms))) for b0 in range(0, len(dms), self.batch)]
-            per, parts, pending = [], [], None
-            for b0, b1 in slices:
-                pend = self._enqueue(series[b0:b1], fb.tsamp, metas[b0:b1])
-                ev = engine.single_pulse_device(pend["x"], widths, kw.get("threshold", 8.0), radius=kw.get("radius"),
-                                                max_events=kw.get("max_events", 1 << 20))
-                parts.append(single_pulse.events_to_host(ev, b0))
-                if pending is not None:
-                    per.extend(self._detect(pending))
-                pending = pend
-            per.extend(self._detect(pending))
-        self.pulse_events = np.concatenate(parts)
-        found = single_pulse.cluster_events(self.pulse_events, dms, fb.tsamp, time_radius=kw.get("time_radius"),
-                                            dm_gap=kw.get("dm_gap", 1), widths=widths)
-        return per, found
+        with _dedispersed(fb, dms, self.device, self.batch, mask=mask, nout=nout, kdm=kdm, zero_dm=zero_dm,
+                          block_mask=block_mask) as (series, metas, _):
+            return self.search_device_accel(series, fb.tsamp, metas, accels)
 
     def __call__(self, trials):
         return self.search_samples([t.data for t in trials], [t.tsamp for t in trials],
@@ -387,6 +390,31 @@ def _gather_tagged(tagged, group, world, make=Peak):
         tagged = [t for part in gathered for t in part]
     tagged.sort(key=lambda t: t[0])
     return [make(*p) for _, plist in tagged for p in plist]
+
+
+def _filterbank_shard(fb_or_fname, dms, kdm, group):
+    """What the filterbank searches below do first: the file opened, kdm and
+    dms normalised, this rank's round-robin share `mine` of the DMs and the
+    length `nout` the whole DM list leaves, nsamp minus its largest delay ([]
+    and 0 without DMs).  Returns (fb, dms, kdm, world, mine, nout)."""
+    from .dedispersion import KDM, check_max_delay, dispersion_delays
+    from .reading import Filterbank, open_filterbank
+    kdm = KDM if kdm is None else float(kdm)
+    fb = fb_or_fname if isinstance(fb_or_fname, Filterbank) else open_filterbank(fb_or_fname)
+    dms = [float(d) for d in dms]
+    rank, world = _rank_world(group)
+    if not dms:
+        return fb, dms, kdm, world, [], 0
+    _, max_delay = dispersion_delays(fb.freqs, dms, fb.tsamp, kdm)
+    check_max_delay(max_delay, fb.nsamp)
+    return fb, dms, kdm, world, shard(len(dms), rank, world), fb.nsamp - max_delay
+
+
+def _gather_per_dm(mine, local, group, world, make=Peak):
+    """And last: this rank's one peak list per DM of `mine`, tagged and gathered."""
+    if len(local) != len(mine):
+        raise RuntimeError("searcher must return one peak list per DM")
+    return _gather_tagged([(i, [tuple(p) for p in plist]) for i, plist in zip(mine, local)], group, world, make)
 
 
 def search_trials(trials, searcher, group=None, loader=None, chunksize=None):
@@ -455,38 +483,24 @@ def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=Non
     (EngineSearcher.search_filterbank), the events are gathered as the peak
     lists are, and the return is (peak list, pulses): the SinglePulse list of
     single_pulse.cluster_events over the events of every DM, on every rank."""
-    from .dedispersion import KDM, dispersion_delays
-    kdm = KDM if kdm is None else float(kdm)
-    from .reading import Filterbank, open_filterbank
-    fb = fb_or_fname if isinstance(fb_or_fname, Filterbank) else open_filterbank(fb_or_fname)
-    dms = [float(d) for d in dms]
-    rank, world = _rank_world(group)
-    tagged = []
+    fb, dms, kdm, world, mine, nout = _filterbank_shard(fb_or_fname, dms, kdm, group)
+    local = []
     if dms:
-        _, max_delay = dispersion_delays(fb.freqs, dms, fb.tsamp, kdm)
-        if max_delay >= fb.nsamp:
-            raise ValueError(f"the largest delay ({max_delay} samples) is not below the {fb.nsamp} samples of the "
-                             "file")
-        mine = shard(len(dms), rank, world)
         # zero_dm is passed only when set: a searcher without the argument keeps working
         extra = {"zero_dm": True} if zero_dm else {}
         if pulses is not None:
             extra["pulses"] = pulses
         if block_mask is not None:    # as zero_dm: only when set
             extra["block_mask"] = block_mask
-        local = searcher.search_filterbank(fb, [dms[i] for i in mine], mask=mask, nout=fb.nsamp - max_delay,
-                                          kdm=kdm, **extra)
+        local = searcher.search_filterbank(fb, [dms[i] for i in mine], mask=mask, nout=nout, kdm=kdm, **extra)
         if pulses is not None:
             local = local[0]
-        if len(local) != len(mine):
-            raise RuntimeError("searcher must return one peak list per DM")
-        tagged = [(i, [tuple(p) for p in plist]) for i, plist in zip(mine, local)]
-    peaks = _gather_tagged(tagged, group, world)
+    peaks = _gather_per_dm(mine, local, group, world)
     if pulses is None:
         return peaks
     from . import single_pulse
     events = np.empty(0, dtype=single_pulse.EVENT_DTYPE)
-    if dms and mine:
+    if mine:
         events = searcher.pulse_events.copy()
         events["series"] = np.asarray(mine, dtype=np.int32)[events["series"]]
     if world > 1:
@@ -495,8 +509,7 @@ def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=Non
         dist.all_gather_object(gathered, events, group=group)
         events = np.concatenate(gathered)
     events = events[np.lexsort((events["sample"], events["series"]))]
-    nsamp = fb.nsamp - max_delay if dms else 0
-    widths = single_pulse._default_widths(pulses.get("widths"), nsamp) if dms else None
+    widths = single_pulse._default_widths(pulses.get("widths"), nout) if dms else None
     return peaks, single_pulse.cluster_events(events, dms, fb.tsamp, time_radius=pulses.get("time_radius"),
                                               dm_gap=pulses.get("dm_gap", 1), widths=widths)
 
@@ -514,24 +527,10 @@ def search_filterbank_accel(fb_or_fname, dms, accels, searcher, group=None, mask
     common length.  fb_or_fname, mask, kdm, zero_dm and block_mask as for
     search_filterbank; the single-pulse search is not combined with it."""
     from .acceleration import AccelPeak
-    from .dedispersion import KDM, dispersion_delays
-    from .reading import Filterbank, open_filterbank
-    kdm = KDM if kdm is None else float(kdm)
-    fb = fb_or_fname if isinstance(fb_or_fname, Filterbank) else open_filterbank(fb_or_fname)
-    dms = [float(d) for d in dms]
+    fb, dms, kdm, world, mine, nout = _filterbank_shard(fb_or_fname, dms, kdm, group)
     accels = [float(a) for a in accels]
-    rank, world = _rank_world(group)
-    tagged = []
+    local = []
     if dms:
-        _, max_delay = dispersion_delays(fb.freqs, dms, fb.tsamp, kdm)
-        if max_delay >= fb.nsamp:
-            raise ValueError(f"the largest delay ({max_delay} samples) is not below the {fb.nsamp} samples of the "
-                             "file")
-        mine = shard(len(dms), rank, world)
-        local = searcher.search_filterbank_accel(fb, [dms[i] for i in mine], accels, mask=mask,
-                                                 nout=fb.nsamp - max_delay, kdm=kdm, zero_dm=zero_dm,
-                                                 block_mask=block_mask)
-        if len(local) != len(mine):
-            raise RuntimeError("searcher must return one peak list per DM")
-        tagged = [(i, [tuple(p) for p in plist]) for i, plist in zip(mine, local)]
-    return _gather_tagged(tagged, group, world, make=AccelPeak)
+        local = searcher.search_filterbank_accel(fb, [dms[i] for i in mine], accels, mask=mask, nout=nout, kdm=kdm,
+                                                 zero_dm=zero_dm, block_mask=block_mask)
+    return _gather_per_dm(mine, local, group, world, make=AccelPeak)

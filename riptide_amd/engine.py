@@ -9,10 +9,19 @@ import typing
 import numpy as np
 
 from . import _lib
+from ._args import (batch_rows, check_workspace, checked_out, checked_workspace, resolve_device, stream_on,
+                    stream_scope)
 from .ffautils import generate_width_trials
 
 _L = _lib.load()
 _check = _lib.check
+
+
+def _size(fn, *args):
+    """The value a size query of the C API writes to its size_t out-parameter."""
+    b = ctypes.c_size_t()
+    _check(fn(*args, ctypes.byref(b)))
+    return b.value
 
 
 def _stream_handle(stream=None):
@@ -74,7 +83,7 @@ class PeriodogramPlan:
 
     def __init__(self, size, tsamp, widths, period_min, period_max, bins_min, bins_max, device=None):
         import torch
-        dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        dev = resolve_device(device)
         _check(_L.rt_set_device(dev.index))
         self.device = dev
         self.size, self.tsamp = int(size), float(tsamp)
@@ -108,9 +117,7 @@ class PeriodogramPlan:
         return self._grid
 
     def workspace_bytes(self, batch):
-        b = ctypes.c_size_t()
-        _check(_L.rt_plan_workspace_bytes(self._h, int(batch), ctypes.byref(b)))
-        return b.value
+        return _size(_L.rt_plan_workspace_bytes, self._h, int(batch))
 
     def ladder_layout(self):
         """ladder_layout() of this plan's own search parameters."""
@@ -133,38 +140,27 @@ class PeriodogramPlan:
         squeeze = data.dim() == 1
         if squeeze:
             data = data.unsqueeze(0)
-        if data.dim() != 2 or data.dtype != torch.float32 or data.device != self.device or data.shape[1] != self.size:
-            raise ValueError("data must be float32 [B, size] on the plan's device")
-        if data.stride(1) != 1:
-            raise ValueError("data rows must be contiguous")
-        B = data.shape[0]
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        with torch.cuda.stream(s):
-            if out is None:
-                out = torch.empty((B, self.length, self.num_widths), dtype=torch.float32, device=self.device)
-            elif (out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous()
-                  or tuple(out.shape) != (B, self.length, self.num_widths)):
-                raise ValueError(f"out must be a contiguous float32 [{B}, {self.length}, {self.num_widths}] "
-                                 "tensor on the plan's device")
-            need = self.workspace_bytes(B)
-            if workspace is None:
-                workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-            elif (workspace.dtype != torch.uint8 or workspace.device != self.device or not workspace.is_contiguous()
-                  or workspace.numel() < need):
-                raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on the plan's device")
+        B = self._rows(data)
+        with stream_scope(self.device, stream) as (s, handle):
+            out = checked_out(out, (B, self.length, self.num_widths), torch.float32, self.device,
+                              f"out must be a contiguous float32 [{B}, {self.length}, {self.num_widths}] "
+                              "tensor on the plan's device")
+            workspace = checked_workspace(workspace, self.workspace_bytes(B), self.device, "plan")
             _check(_L.rt_periodogram_device(self._h, _lib.ptr(data), B, data.stride(0), _lib.ptr(out),
                                             self.length * self.num_widths, _lib.ptr(workspace), workspace.numel(),
-                                            _stream_handle(s)))
+                                            handle))
         if check:
             self.check(s)
         return out[0] if squeeze else out
 
-    def _ws_ok(self, workspace, B):
+    def _rows(self, data):
+        """B of a batch argument of run() or ladder(), checked."""
         import torch
-        need = self.workspace_bytes(B)
-        if (workspace is None or workspace.dtype != torch.uint8 or workspace.device != self.device
-                or not workspace.is_contiguous() or workspace.numel() < need):
-            raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on the plan's device")
+        if data.dim() != 2 or data.dtype != torch.float32 or data.device != self.device or data.shape[1] != self.size:
+            raise ValueError("data must be float32 [B, size] on the plan's device")
+        if data.stride(1) != 1:
+            raise ValueError("data rows must be contiguous")
+        return data.shape[0]
 
     def ladder(self, data, workspace, stream=None):
         """First half of run(): the downsampling ladder of data float32 [B, size]
@@ -172,30 +168,22 @@ class PeriodogramPlan:
         passes() on another stream, batch k + 1's ladder overlaps batch k's
         FFA passes; the caller orders the two halves of one batch (an event)
         and keeps a workspace per batch in flight."""
-        import torch
-        if data.dim() != 2 or data.dtype != torch.float32 or data.device != self.device or data.shape[1] != self.size:
-            raise ValueError("data must be float32 [B, size] on the plan's device")
-        if data.stride(1) != 1:
-            raise ValueError("data rows must be contiguous")
-        B = data.shape[0]
-        self._ws_ok(workspace, B)
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        B = self._rows(data)
+        check_workspace(workspace, self.workspace_bytes(B), self.device, "plan")
         _check(_L.rt_periodogram_ladder_device(self._h, _lib.ptr(data), B, data.stride(0), _lib.ptr(workspace),
-                                               workspace.numel(), _stream_handle(s)))
+                                               workspace.numel(), _stream_handle(stream_on(self.device, stream))))
 
     def passes(self, out, workspace, stream=None):
         """Second half of run(): FFA passes + fused S/N of the batch whose
         ladder filled `workspace`, into out float32 [B, L, W]."""
         import torch
-        B = out.shape[0]
-        if (out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous()
-                or tuple(out.shape) != (B, self.length, self.num_widths)):
-            raise ValueError(f"out must be a contiguous float32 [B, {self.length}, {self.num_widths}] "
-                             "tensor on the plan's device")
-        self._ws_ok(workspace, B)
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        B, L, W = out.shape[0], self.length, self.num_widths
+        checked_out(out, (B, L, W), torch.float32, self.device,
+                    f"out must be a contiguous float32 [B, {L}, {W}] tensor on the plan's device")
+        check_workspace(workspace, self.workspace_bytes(B), self.device, "plan")
         _check(_L.rt_periodogram_passes_device(self._h, B, _lib.ptr(out), self.length * self.num_widths,
-                                               _lib.ptr(workspace), workspace.numel(), _stream_handle(s)))
+                                               _lib.ptr(workspace), workspace.numel(),
+                                               _stream_handle(stream_on(self.device, stream))))
         return out
 
     def check(self, stream=None):
@@ -214,10 +202,7 @@ class PeriodogramPlan:
 
 
 def deredden_workspace_bytes(size, width_samples, min_points, batch):
-    b = ctypes.c_size_t()
-    _check(_L.rt_deredden_workspace_bytes(int(size), int(width_samples), int(min_points), int(batch),
-                                          ctypes.byref(b)))
-    return b.value
+    return _size(_L.rt_deredden_workspace_bytes, int(size), int(width_samples), int(min_points), int(batch))
 
 
 # rt_dered_forms and its RT_* values (include/riptide_amd.h)
@@ -251,29 +236,18 @@ def deredden_normalise(data, width_samples, min_points=101, deredden=True, norma
                        workspace=None, stream=None):
     """TimeSeries.deredden(...).normalise() for a batch [B, N] of device series."""
     import torch
-    squeeze = data.dim() == 1
-    if squeeze:
-        data = data.unsqueeze(0)
-    if data.dim() != 2 or data.dtype != torch.float32 or data.device.type != "cuda" or data.stride(1) != 1:
-        raise ValueError("data must be float32 [B, N] device rows with unit stride")
-    B, N = data.shape
-    s = stream if stream is not None else torch.cuda.current_stream(data.device)
-    with torch.cuda.stream(s):
-        if out is None:
-            out = torch.empty((B, N), dtype=torch.float32, device=data.device)
-        elif (out.dim() != 2 or tuple(out.shape) != (B, N) or out.dtype != torch.float32
-              or out.device != data.device or out.stride(1) != 1):
-            raise ValueError("out must be float32 [B, N] rows with unit stride on the data's device")
-        need = deredden_workspace_bytes(N, width_samples, min_points, B)
-        if workspace is None:
-            workspace = torch.empty(need, dtype=torch.uint8, device=data.device)
-        elif (workspace.dtype != torch.uint8 or workspace.device != data.device or not workspace.is_contiguous()
-              or workspace.numel() < need):
-            raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on the data's device")
+    data, B, N, squeeze = batch_rows(data)
+    dev = data.device
+    with stream_scope(dev, stream) as (_, handle):
+        out = checked_out(out, (B, N), torch.float32, dev,
+                          "out must be float32 [B, N] rows with unit stride on the data's device",
+                          lambda o: (o.dim() != 2 or tuple(o.shape) != (B, N) or o.dtype != torch.float32
+                                     or o.device != dev or o.stride(1) != 1))
+        workspace = checked_workspace(workspace, deredden_workspace_bytes(N, width_samples, min_points, B), dev, "data")
         _check(_L.rt_deredden_normalise_device(_lib.ptr(data), N, B, data.stride(0), int(width_samples),
                                                int(min_points), int(bool(deredden)), int(bool(normalise)),
                                                _lib.ptr(out), out.stride(0), _lib.ptr(workspace), workspace.numel(),
-                                               _stream_handle(s)))
+                                               handle))
     return out[0] if squeeze else out
 
 
@@ -286,28 +260,22 @@ def fold_device(data, tsamp, specs, stream=None):
     synchronisation.  Raises folding.fold's ValueErrors."""
     import torch
     from .folding import pack_fold_specs
-    if data.dim() == 1:
-        data = data.unsqueeze(0)
-    if data.dim() != 2 or data.dtype != torch.float32 or data.device.type != "cuda" or data.stride(1) != 1:
-        raise ValueError("data must be float32 [B, N] device rows with unit stride")
+    data, B, N, _ = batch_rows(data)
     specs = list(specs)
     if not specs:
         return []
-    B, N = data.shape
     for series, _, bins, _ in specs:
         if not 0 <= int(series) < B:
             raise ValueError(f"series index {series} outside the {B} rows of data")
         if int(bins) < 2:
             raise ValueError("the device fold needs bins >= 2")
     table, shapes, total = pack_fold_specs(N, N * float(tsamp), float(tsamp), specs)
-    need = ctypes.c_size_t()
-    _check(_L.rt_fold_workspace_bytes(N, _lib.ptr(table), len(specs), ctypes.byref(need)))
-    s = stream if stream is not None else torch.cuda.current_stream(data.device)
-    with torch.cuda.device(data.device), torch.cuda.stream(s):
+    need = _size(_L.rt_fold_workspace_bytes, N, _lib.ptr(table), len(specs))
+    with stream_scope(data.device, stream) as (_, handle):
         out = torch.empty(total, dtype=torch.float32, device=data.device)
-        workspace = torch.empty(max(need.value, 1), dtype=torch.uint8, device=data.device)
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=data.device)
         _check(_L.rt_fold_device(_lib.ptr(data), N, data.stride(0), B, _lib.ptr(table), len(specs), _lib.ptr(out),
-                                 total, _lib.ptr(workspace), workspace.numel(), _stream_handle(s)))
+                                 total, _lib.ptr(workspace), workspace.numel(), handle))
     results = []
     for k, shape in enumerate(shapes):
         o = int(table["out_off"][k])
@@ -343,16 +311,14 @@ def refine_device(cubes, shifts, widths, table, profiles=False, stream=None):
         raise ValueError("refine: a spec's arrays exceed the device tensors")
     nsnr = int((u["snr_off"] + u["ndm"] * u["nper"] * u["nw"]).max())
     nprof = int((u["prof_off"] + u["ndm"] * u["nper"] * u["bins"]).max())
-    need = ctypes.c_size_t()
-    _check(_L.rt_refine_workspace_bytes(_lib.ptr(table), table.size, ctypes.byref(need)))
-    s = stream if stream is not None else torch.cuda.current_stream(cubes.device)
-    with torch.cuda.device(cubes.device), torch.cuda.stream(s):
+    need = _size(_L.rt_refine_workspace_bytes, _lib.ptr(table), table.size)
+    with stream_scope(cubes.device, stream) as (_, handle):
         snr = torch.empty(nsnr, dtype=torch.float32, device=cubes.device)
         prof = torch.empty(nprof, dtype=torch.float32, device=cubes.device) if profiles else None
-        workspace = torch.empty(max(need.value, 1), dtype=torch.uint8, device=cubes.device)
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=cubes.device)
         _check(_L.rt_refine_device(_lib.ptr(cubes), _lib.ptr(shifts), _lib.ptr(widths), _lib.ptr(table), table.size,
                                    _lib.ptr(snr), _lib.ptr(prof) if profiles else None, _lib.ptr(workspace),
-                                   workspace.numel(), _stream_handle(s)))
+                                   workspace.numel(), handle))
     return snr, prof
 
 
@@ -405,11 +371,7 @@ def single_pulse_device(data, widths, threshold, radius=None, dense=False, max_e
     there are more than max_events.  The count is read back, so the call
     waits for the stream; rt_single_pulse_device itself does not."""
     import torch
-    if data.dim() == 1:
-        data = data.unsqueeze(0)
-    if data.dim() != 2 or data.dtype != torch.float32 or data.device.type != "cuda" or data.stride(1) != 1:
-        raise ValueError("data must be float32 [B, N] device rows with unit stride")
-    B, N = data.shape
+    data, B, N, _ = batch_rows(data)
     if B > 1 and data.stride(0) < N:
         raise ValueError("data rows must not overlap")
     w = np.ascontiguousarray(widths, dtype=np.int32).ravel()
@@ -425,21 +387,19 @@ def single_pulse_device(data, widths, threshold, radius=None, dense=False, max_e
     if cap < 0:
         raise ValueError("capacity must be >= 0")
     ldx = data.stride(0) if B > 1 else max(N, 1)
-    s = stream if stream is not None else torch.cuda.current_stream(data.device)
     dev = data.device
-    with torch.cuda.device(dev), torch.cuda.stream(s):
+    with stream_scope(dev, stream) as (_, handle):
         best = torch.empty((B, N), dtype=torch.float32, device=dev) if dense else None
         kbest = torch.empty((B, N), dtype=torch.int32, device=dev) if dense else None
         count = torch.zeros(1, dtype=torch.int64, device=dev)
         while True:
-            need = ctypes.c_size_t()
-            _check(_L.rt_single_pulse_workspace_bytes(B, N, w.size, cap, ctypes.byref(need)))
             ev = torch.empty((cap, 4), dtype=torch.int32, device=dev)
-            workspace = torch.empty(max(need.value, 1), dtype=torch.uint8, device=dev)
+            need = _size(_L.rt_single_pulse_workspace_bytes, B, N, w.size, cap)
+            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
             _check(_L.rt_single_pulse_device(_lib.ptr(data), B, N, ldx, _lib.ptr(w), w.size, float(threshold), radius,
                                              _lib.ptr(ev) if cap else None, cap, _lib.ptr(count),
                                              _lib.ptr(best) if dense else None, _lib.ptr(kbest) if dense else None,
-                                             _lib.ptr(workspace), workspace.numel(), _stream_handle(s)))
+                                             _lib.ptr(workspace), workspace.numel(), handle))
             found = int(count.item())
             if found <= cap:
                 break
@@ -466,27 +426,21 @@ def resample_device(data, factors, src=None, out=None, stream=None):
     a src outside [0, B), a factor that is not finite or has |f| * N >= 1."""
     import torch
     from .acceleration import resample_rows
-    if data.dim() == 1:
-        data = data.unsqueeze(0)
-    if data.dim() != 2 or data.dtype != torch.float32 or data.device.type != "cuda" or data.stride(1) != 1:
-        raise ValueError("data must be float32 [B, N] device rows with unit stride")
-    B, N = data.shape
+    data, B, N, _ = batch_rows(data)
     if B > 1 and data.stride(0) < N:
         raise ValueError("resample: input row stride below the series length")
     rows, f = resample_rows(B, factors, src)
     R = rows.size
-    s = stream if stream is not None else torch.cuda.current_stream(data.device)
-    with torch.cuda.device(data.device), torch.cuda.stream(s):
-        if out is None:
-            out = torch.empty((R, N), dtype=torch.float32, device=data.device)
-        elif (out.dim() != 2 or tuple(out.shape) != (R, N) or out.dtype != torch.float32
-              or out.device != data.device or out.stride(1) != 1):
-            raise ValueError(f"out must be float32 [{R}, {N}] rows with unit stride on the data's device")
-        elif R > 1 and out.stride(0) < N:
+    dev = data.device
+    with stream_scope(dev, stream) as (_, handle):
+        out = checked_out(out, (R, N), torch.float32, dev,
+                          f"out must be float32 [{R}, {N}] rows with unit stride on the data's device",
+                          lambda o: (o.dim() != 2 or tuple(o.shape) != (R, N) or o.dtype != torch.float32
+                                     or o.device != dev or o.stride(1) != 1))
+        if R > 1 and out.stride(0) < N:
             raise ValueError("resample: output row stride below the series length")
         _check(_L.rt_resample_device(_lib.ptr(data), B, N, data.stride(0) if B > 1 else max(N, 1), _lib.ptr(rows),
-                                     _lib.ptr(f), R, _lib.ptr(out), out.stride(0) if R > 1 else max(N, 1),
-                                     _stream_handle(s)))
+                                     _lib.ptr(f), R, _lib.ptr(out), out.stride(0) if R > 1 else max(N, 1), handle))
     return out
 
 
@@ -524,10 +478,8 @@ def dedisperse_workspace_bytes(dtype, nsamp_blk, nchans, zero_dm=False, nbits=No
     'u4', 'u16'; or pass nbits, dtype is then ignored).  1/2/4-bit data takes
     the 8-bit size and 16-bit data the float32 size.  With zero_dm every dtype
     takes float32 rows, plus nsamp_blk floats for the mean series."""
-    b = ctypes.c_size_t()
-    _check(_L.rt_dedisperse_workspace_bytes_opt(DEDISP_DTYPES[_dedisp_name(dtype, nbits)], int(nsamp_blk), int(nchans),
-                                                DEDISP_ZERO_DM if zero_dm else 0, ctypes.byref(b)))
-    return b.value
+    return _size(_L.rt_dedisperse_workspace_bytes_opt, DEDISP_DTYPES[_dedisp_name(dtype, nbits)], int(nsamp_blk),
+                 int(nchans), DEDISP_ZERO_DM if zero_dm else 0)
 
 
 def dedisperse_span_plan(esize, lo, hi):
@@ -631,16 +583,12 @@ def zero_dm_mean_device(block, mask=None, out=None, stream=None, nbits=None, blo
     name, nsamp_blk, nchans = _dedisp_block(block, nbits)
     _check_device_mask(mask, block, nchans)
     bm = _block_mask_struct(block_mask, t_origin, block, name, nchans)
-    s = stream if stream is not None else torch.cuda.current_stream(block.device)
-    with torch.cuda.device(block.device), torch.cuda.stream(s):
-        if out is None:
-            out = torch.empty(nsamp_blk, dtype=torch.float32, device=block.device)
-        elif (out.dtype != torch.float32 or out.device != block.device or not out.is_contiguous()
-              or tuple(out.shape) != (nsamp_blk,)):
-            raise ValueError(f"out must be a contiguous float32 [{nsamp_blk}] tensor on the block's device")
+    with stream_scope(block.device, stream) as (_, handle):
+        out = checked_out(out, (nsamp_blk,), torch.float32, block.device,
+                          f"out must be a contiguous float32 [{nsamp_blk}] tensor on the block's device")
         if nsamp_blk:
             args = (_lib.ptr(block), DEDISP_DTYPES[name], nsamp_blk, nchans, None if mask is None else _lib.ptr(mask),
-                    _lib.ptr(out), _stream_handle(s))
+                    _lib.ptr(out), handle)
             if bm is None:
                 _check(_L.rt_zero_dm_mean_device(*args))
             else:
@@ -651,9 +599,7 @@ def zero_dm_mean_device(block, mask=None, out=None, stream=None, nbits=None, blo
 def block_stats_workspace_bytes(nsamp_blk, nchans, block_len):
     """Device workspace bytes of block_stats_device for a block of this shape
     (none for block_len <= 2048)."""
-    b = ctypes.c_size_t()
-    _check(_L.rt_block_stats_workspace_bytes(int(nsamp_blk), int(nchans), int(block_len), ctypes.byref(b)))
-    return b.value
+    return _size(_L.rt_block_stats_workspace_bytes, int(nsamp_blk), int(nchans), int(block_len))
 
 
 def block_stats_device(block, block_len, out=None, workspace=None, stream=None, nbits=None):
@@ -671,31 +617,21 @@ def block_stats_device(block, block_len, out=None, workspace=None, stream=None, 
     if block_len < 1:
         raise ValueError("block_stats: block_len must be at least 1")
     nblk = -(-nsamp_blk // block_len)
-    s = stream if stream is not None else torch.cuda.current_stream(block.device)
-    with torch.cuda.device(block.device), torch.cuda.stream(s):
-        if out is None:
-            out = torch.empty((nblk, 2, nchans), dtype=torch.float64, device=block.device)
-        elif (out.dtype != torch.float64 or out.device != block.device or not out.is_contiguous()
-              or tuple(out.shape) != (nblk, 2, nchans)):
-            raise ValueError(f"out must be a contiguous float64 [{nblk}, 2, {nchans}] tensor on the block's device")
+    with stream_scope(block.device, stream) as (_, handle):
+        out = checked_out(out, (nblk, 2, nchans), torch.float64, block.device,
+                          f"out must be a contiguous float64 [{nblk}, 2, {nchans}] tensor on the block's device")
         if not nsamp_blk:
             return out
-        need = block_stats_workspace_bytes(nsamp_blk, nchans, block_len)
-        if workspace is None:
-            workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=block.device)
-        elif (workspace.dtype != torch.uint8 or workspace.device != block.device or not workspace.is_contiguous()
-              or workspace.numel() < need):
-            raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on the block's device")
+        workspace = checked_workspace(workspace, block_stats_workspace_bytes(nsamp_blk, nchans, block_len),
+                                      block.device, "block", floor=16)
         _check(_L.rt_block_stats_device(_lib.ptr(block), DEDISP_DTYPES[name], nsamp_blk, nchans, block_len,
-                                        _lib.ptr(out), _lib.ptr(workspace), workspace.numel(), _stream_handle(s)))
+                                        _lib.ptr(out), _lib.ptr(workspace), workspace.numel(), handle))
     return out
 
 
 def channel_stats_workspace_bytes(nsamp_blk, nchans):
     """Device workspace bytes of channel_stats_device for a block of this shape."""
-    b = ctypes.c_size_t()
-    _check(_L.rt_channel_stats_workspace_bytes(int(nsamp_blk), int(nchans), ctypes.byref(b)))
-    return b.value
+    return _size(_L.rt_channel_stats_workspace_bytes, int(nsamp_blk), int(nchans))
 
 
 def channel_stats_device(block, acc, workspace=None, stream=None, nbits=None):
@@ -712,18 +648,13 @@ def channel_stats_device(block, acc, workspace=None, stream=None, nbits=None):
     if (acc.dtype != torch.float64 or acc.device != block.device or not acc.is_contiguous()
             or tuple(acc.shape) != (2, nchans)):
         raise ValueError(f"acc must be a contiguous float64 [2, {nchans}] tensor on the block's device")
-    s = stream if stream is not None else torch.cuda.current_stream(block.device)
-    with torch.cuda.device(block.device), torch.cuda.stream(s):
+    with stream_scope(block.device, stream) as (_, handle):
         if not nsamp_blk:
             return acc
-        need = channel_stats_workspace_bytes(nsamp_blk, nchans)
-        if workspace is None:
-            workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=block.device)
-        elif (workspace.dtype != torch.uint8 or workspace.device != block.device or not workspace.is_contiguous()
-              or workspace.numel() < need):
-            raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on the block's device")
+        workspace = checked_workspace(workspace, channel_stats_workspace_bytes(nsamp_blk, nchans), block.device,
+                                      "block", floor=16)
         _check(_L.rt_channel_stats_device(_lib.ptr(block), DEDISP_DTYPES[name], nsamp_blk, nchans, _lib.ptr(acc),
-                                          _lib.ptr(workspace), workspace.numel(), _stream_handle(s)))
+                                          _lib.ptr(workspace), workspace.numel(), handle))
     return acc
 
 
@@ -744,8 +675,7 @@ def _dedisperse_device(block, delays, max_delay, bands, mask, out, out_offset, w
     _check_device_mask(mask, block, nchans)
     max_delay, out_offset = int(max_delay), int(out_offset)
     nout = nsamp_blk - max_delay
-    s = stream if stream is not None else torch.cuda.current_stream(block.device)
-    with torch.cuda.device(block.device), torch.cuda.stream(s):
+    with stream_scope(block.device, stream) as (_, handle):
         if bands is not None:
             if not torch.is_tensor(bands):
                 bands = torch.from_numpy(checked_bands(bands, nchans).view(np.int32)).to(block.device)
@@ -759,28 +689,24 @@ def _dedisperse_device(block, delays, max_delay, bands, mask, out, out_offset, w
         if not 0 <= max_delay < nsamp_blk:
             raise ValueError(f"max_delay {max_delay} must be in [0, {nsamp_blk}): the block is no longer than the "
                              "largest delay")
-        if out is None:
-            out = torch.empty((ndm, nout) if bands is None else (ndm, nbands, nout), dtype=torch.float32,
-                              device=block.device)
-        elif bands is None:
-            if (out.dim() != 2 or out.dtype != torch.float32 or out.device != block.device or out.shape[0] != ndm
-                    or out.stride(1) != 1 or out.shape[1] < out_offset + nout
-                    or (ndm > 1 and out.stride(0) < out.shape[1])):
-                raise ValueError(f"out must be float32 [{ndm}, >= {out_offset + nout}] rows with unit stride on "
-                                 "the block's device")
-        elif (out.dim() != 3 or out.dtype != torch.float32 or out.device != block.device
-              or tuple(out.shape[:2]) != (ndm, nbands) or not out.is_contiguous() or out.shape[2] < out_offset + nout):
-            raise ValueError(f"out must be a contiguous float32 [{ndm}, {nbands}, >= {out_offset + nout}] "
-                             "tensor on the block's device")
-        if workspace is None:
-            workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=block.device)
-        elif (workspace.dtype != torch.uint8 or workspace.device != block.device or not workspace.is_contiguous()
-              or workspace.numel() < need):
-            raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on the block's device")
+        if bands is None:
+            out = checked_out(out, (ndm, nout), torch.float32, block.device,
+                              f"out must be float32 [{ndm}, >= {out_offset + nout}] rows with unit stride on "
+                              "the block's device",
+                              lambda o: (o.dim() != 2 or o.dtype != torch.float32 or o.device != block.device
+                                         or o.shape[0] != ndm or o.stride(1) != 1 or o.shape[1] < out_offset + nout
+                                         or (ndm > 1 and o.stride(0) < o.shape[1])))
+        else:
+            out = checked_out(out, (ndm, nbands, nout), torch.float32, block.device,
+                              f"out must be a contiguous float32 [{ndm}, {nbands}, >= {out_offset + nout}] "
+                              "tensor on the block's device",
+                              lambda o: (o.dim() != 3 or o.dtype != torch.float32 or o.device != block.device
+                                         or tuple(o.shape[:2]) != (ndm, nbands) or not o.is_contiguous()
+                                         or o.shape[2] < out_offset + nout))
+        workspace = checked_workspace(workspace, need, block.device, "block", floor=16)
         head = (_lib.ptr(block), DEDISP_DTYPES[name], nsamp_blk, nchans, _lib.ptr(delays),
                 None if mask is None else _lib.ptr(mask), ndm)
-        tail = (out_offset, _lib.ptr(workspace), workspace.numel(), _stream_handle(s),
-                DEDISP_ZERO_DM if zero_dm else 0)
+        tail = (out_offset, _lib.ptr(workspace), workspace.numel(), handle, DEDISP_ZERO_DM if zero_dm else 0)
         if bm is not None:
             # the entry point reads "no table, nbands 0" as the plain call: an empty table is refused here,
             # as rt_dedisperse_bands_device refuses it

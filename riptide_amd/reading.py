@@ -517,15 +517,14 @@ def upload_samples(raws, device=None, stream=None):
     with numpy's astype(float32)."""
     import torch
     from . import _lib
-    from .engine import _stream_handle
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    from ._args import resolve_device, stream_scope
+    dev = resolve_device(device)
     n = int(raws[0].size)
     if any(int(r.size) != n for r in raws):
         raise ValueError("upload_samples needs series of equal length")
     L = _lib.load()
     kinds = {np.dtype(np.uint8): 0, np.dtype(np.int8): 1}
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
-    with torch.cuda.stream(s):
+    with stream_scope(dev, stream) as (_, handle):
         out = torch.empty((len(raws), n), dtype=torch.float32, device=dev)
         for b, raw in enumerate(raws):
             raw = np.asarray(raw)
@@ -542,8 +541,7 @@ def upload_samples(raws, device=None, stream=None):
                 out[b].copy_(src, non_blocking=pinned)
                 continue
             staged = src.to(dev, non_blocking=pinned)
-            _lib.check(L.rt_convert_samples_device(_lib.ptr(staged), n, kinds[raw.dtype], _lib.ptr(out[b]),
-                                                   _stream_handle(s)))
+            _lib.check(L.rt_convert_samples_device(_lib.ptr(staged), n, kinds[raw.dtype], _lib.ptr(out[b]), handle))
     return out
 
 

@@ -52,9 +52,8 @@ class ChannelStats:
 
 
 def _device_and_rows(fb, nsamp, gulp, device):
-    import torch
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else
-                       (device.index if isinstance(device, torch.device) else int(device)))
+    from ._args import resolve_device
+    dev = resolve_device(device)
     _checked_sample_type(fb)
     row_elems, dtype = _gulp_layout(fb)
     nrows = fb.nsamp if nsamp is None else int(nsamp)

@@ -192,26 +192,22 @@ def search_filterbank_pulses(fb_or_fname, dms, deredden_params, widths=None, thr
     events and cluster_events.  mask, zero_dm, kdm, nout, block_mask: as for
     dispatch.search_filterbank.  Returns (pulses, events); `series` of an
     event is its index into dms."""
-    import torch
     from . import engine
-    from .dedispersion import KDM, dedisperse_filterbank
+    from .dedispersion import KDM
+    from .dispatch import _dedispersed
     from .reading import Filterbank, open_filterbank
     fb = fb_or_fname if isinstance(fb_or_fname, Filterbank) else open_filterbank(fb_or_fname)
     kdm = KDM if kdm is None else float(kdm)
     dms = [float(d) for d in dms]
     if not dms:
         return [], np.empty(0, dtype=EVENT_DTYPE)
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else
-                       (device.index if isinstance(device, torch.device) else int(device)))
-    batch = max(1, int(batch))
     parts = []
-    with torch.cuda.device(dev):
-        series = dedisperse_filterbank(fb, dms, mask=mask, device=dev, nout=nout, kdm=kdm, zero_dm=zero_dm,
-                                       block_mask=block_mask)
+    with _dedispersed(fb, dms, device, max(1, int(batch)), mask=mask, nout=nout, kdm=kdm, zero_dm=zero_dm,
+                      block_mask=block_mask) as (series, _, slices):
         w = _default_widths(widths, series.shape[1])
         ws = int(round(deredden_params["rmed_width"] / fb.tsamp))
-        for b0 in range(0, len(dms), batch):
-            x = engine.deredden_normalise(series[b0:b0 + batch], ws, deredden_params["rmed_minpts"])
+        for b0, b1 in slices:
+            x = engine.deredden_normalise(series[b0:b1], ws, deredden_params["rmed_minpts"])
             ev = engine.single_pulse_device(x, w, threshold, radius=radius, max_events=max_events)
             parts.append((b0, ev))
         events = np.concatenate([events_to_host(ev, b0) for b0, ev in parts])

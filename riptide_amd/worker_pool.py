@@ -23,6 +23,7 @@ the device work.
 import logging
 import threading
 
+from ._args import resolve_device
 from .dispatch import EngineSearcher
 from .reading import _raw_samples
 
@@ -98,9 +99,8 @@ class GpuWorkerPool:
         import torch
         if not torch.cuda.is_available():
             return
-        dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else self.device)
         ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(dev))
+        ev.record(torch.cuda.current_stream(resolve_device(self.device)))
         self._part_done[part] = ev
 
     def _read(self, fnames, part):
