@@ -894,6 +894,70 @@ int rt_dedisperse_device_cells(const void* d_block, int dtype, size_t nsamp_blk,
 int rt_zero_dm_mean_device_cells(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans,
                                  const uint8_t* d_mask, float* d_m, void* stream, const rt_block_mask* bm);
 
+/* ------------------------------ pulse cutouts ------------------------------ */
+/* Dedispersed, time-decimated windows of one block, one per job: the
+ * frequency-time and DM-time cutouts of single-pulse candidates.  Let x' be
+ * the block [nsamp, nchans] of any sample type above after the block mask (bm
+ * with its t_origin; NULL: none), and under RT_DEDISP_ZERO_DM y = x' - m with
+ * m the mean series over the unmasked channels (rt_zero_dm_mean_host of x').
+ * delays is int32 [ndelay_rows, nchans]; an entry is clamped to [0, max_delay]
+ * as it is read.  Job (start, factor f, nbins T, delay_row, [band_lo,
+ * band_hi), out_off) writes
+ *   out[out_off + n] = sum over unmasked c in [band_lo, band_hi), ascending,
+ *                      sum over j = 0 .. f - 1, ascending, of
+ *                      x'[start + n * f + j + delays[delay_row][c], c]
+ * for n = 0 .. T - 1.  start is relative to row 0 of the block and may be
+ * negative.  A sample whose row is outside [0, nsamp) is skipped: not added
+ * and not counted.  An empty band, or one whose channels are all masked,
+ * gives zeros.  The ranges [out_off, out_off + nbins) of the jobs of a call
+ * must not overlap.
+ * Exactness: the 8-bit types (U8, I8, U1, U2, U4) without the zero-DM filter
+ * are summed as integers (an int8 sample as its signed value) and converted
+ * to float32 once; F32, U16 and everything under RT_DEDISP_ZERO_DM use one
+ * float32 accumulator from 0.0f, a round-to-nearest addition per sample in
+ * exactly the order above.  The device call returns the host call's bits for
+ * every type.
+ * RT_EINVAL (device: nothing is launched) for an unknown type or flag, nchans,
+ * nsamp or ndelay_rows of 0, nsamp >= 2^31, max_delay outside [0, 2^31), more
+ * than RT_DEDISP_MAX_CHANS_8BIT channels of an 8-bit type, a mask refused as
+ * above, and a job with factor or nbins of 0, nbins * factor >= 2^31, start
+ * outside [-2^40, 2^40], delay_row >= ndelay_rows, a band that is not lo <=
+ * hi <= nchans, (band_hi - band_lo) * factor * 255 >= 2^31 where the sum is
+ * an integer one, or out_off + nbins > out_floats. */
+typedef struct rt_cutout_spec {
+    int64_t  start;      /* first sample of bin 0 at delay 0, relative to the block */
+    uint64_t out_off;    /* float offset of bin 0 in out */
+    uint32_t factor;     /* samples summed per bin, >= 1 */
+    uint32_t nbins;      /* >= 1 */
+    uint32_t delay_row;  /* row of the delay table */
+    uint32_t band_lo;    /* channels [band_lo, band_hi) */
+    uint32_t band_hi;
+    uint32_t reserved;   /* 0 */
+} rt_cutout_spec;
+/* Host only, no device: the specification.  Every array is in host memory. */
+int rt_pulse_cutouts_host(const void* x, int dtype, size_t nsamp, size_t nchans, const int32_t* delays,
+                          size_t ndelay_rows, int64_t max_delay, const uint8_t* mask, const rt_cutout_spec* jobs,
+                          size_t njobs, float* out, size_t out_floats, uint32_t flags, const rt_block_mask* bm);
+/* One resident block, stream-ordered, no synchronisation: the block goes to
+ * the channel-major rows of the dedispersion workspace (d_workspace of
+ * rt_dedisperse_workspace_bytes_opt(dtype, nsamp_blk, nchans, flags) bytes,
+ * 16-byte aligned), as the first step of rt_dedisperse_device_cells, then one
+ * launch for all jobs.  jobs is in host memory and is checked there; d_jobs is
+ * device memory for njobs rt_cutout_spec, 8-byte aligned, which the call
+ * fills.  d_delays, d_mask, d_out (out_floats floats, 4-byte aligned) and the
+ * mask's cells and fill are device memory.  njobs == 0 launches nothing. */
+int rt_pulse_cutouts_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans,
+                            const int32_t* d_delays, size_t ndelay_rows, int64_t max_delay, const uint8_t* d_mask,
+                            const rt_cutout_spec* jobs, size_t njobs, rt_cutout_spec* d_jobs, float* d_out,
+                            size_t out_floats, void* d_workspace, size_t workspace_bytes, void* stream,
+                            uint32_t flags, const rt_block_mask* bm);
+/* The kernel's shape, for tests to name the path they run (no device call):
+ * the bins of a tile, and for a channel whose clamped span of a tile is the
+ * elements [lo, hi) of its row (esize 1: 8-bit rows, 4: float rows) the dwords
+ * it takes and whether they go through LDS (staged) or the row is read
+ * directly.  Both paths give the same bits. */
+int rt_pulse_cutouts_plan(size_t esize, int64_t lo, int64_t hi, size_t* tile, size_t* ndw, int* staged);
+
 /* --------------------------- file input (device) --------------------------- */
 /* 8-bit SIGPROC samples (riptide/time_series.py:352-357) to float32 in device
  * memory: d_raw holds n bytes, int8 when is_signed else uint8; exact as

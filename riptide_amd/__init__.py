@@ -25,7 +25,8 @@ from .reading import Filterbank, PackedFilterbank, open_filterbank
 from .dispatch import search_filterbank, search_filterbank_accel
 from .refine import Refinement, refine_candidates, refine_cube
 from .single_pulse import SinglePulse, search_filterbank_pulses
-from . import acceleration, dedispersion, rfi, single_pulse
+from .pulse_candidates import PulseCandidate, build_pulse_candidates
+from . import acceleration, dedispersion, pulse_candidates, rfi, single_pulse
 
 __all__ = [
     "Candidate", "PeakCluster", "build_candidates", "build_candidates_filterbank", "flag_harmonics",
@@ -36,5 +37,6 @@ __all__ = [
     "PackedFilterbank", "open_filterbank",
     "dedispersion", "rfi", "Refinement", "refine_cube", "refine_candidates",
     "SinglePulse", "search_filterbank_pulses", "single_pulse",
+    "PulseCandidate", "build_pulse_candidates", "pulse_candidates",
     "acceleration", "search_filterbank_accel",
 ]

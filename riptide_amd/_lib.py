@@ -170,6 +170,16 @@ _SIGNATURES = {
                                           _c_sz, _c_sz, _vp, _c_sz, _vp, ctypes.c_uint32, _vp]),
     # rt_zero_dm_mean_device's arguments, then bm
     "rt_zero_dm_mean_device_cells": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _vp, _vp]),
+    # x, dtype, nsamp, nchans, delays (int32 [rows, nchans]), rows, max_delay, mask, jobs (rt_cutout_spec[njobs]),
+    # njobs, out, out floats, flags, bm
+    "rt_pulse_cutouts_host": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _c_sz, ctypes.c_int64, _vp, _vp, _c_sz, _vp, _c_sz,
+                                     ctypes.c_uint32, _vp]),
+    # the same with a device block, delays, mask and out, and behind njobs the device table the call fills;
+    # then workspace, workspace bytes, stream, flags, bm
+    "rt_pulse_cutouts_device": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _c_sz, ctypes.c_int64, _vp, _vp, _c_sz, _vp, _vp,
+                                       _c_sz, _vp, _c_sz, _vp, ctypes.c_uint32, _vp]),
+    # esize, lo, hi, tile, ndw, staged
+    "rt_pulse_cutouts_plan": (_c_i, [_c_sz, ctypes.c_int64, ctypes.c_int64, _psz, _psz, ctypes.POINTER(_c_i)]),
 }
 
 

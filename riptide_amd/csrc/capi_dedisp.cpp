@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "capi_dedisp.hpp"
 #include "capi_device.hpp"
 #include "dedisp_types.hpp"
 #include "kernels.hpp"
@@ -55,24 +56,6 @@ void dedisp_check_bands(size_t ndm, size_t nbands)
     if (ndm * nbands > 0xFFFFFFFFull)   // ndm < 2^20, nbands < 2^16: no overflow here
         throw std::invalid_argument("dedisperse: ndm * nbands rows overflow 32 bits");
 }
-
-// A block mask of a device call over nsamp_blk rows (the shape is checked):
-// the shared check, the fill aligned to its type, then the kernels' form of
-// it.  No mask (a null pointer) is no DedispCells: the plain kernels.
-struct DeviceCells {
-    DedispCells cells{};
-    bool set = false;
-    DeviceCells(const rt_block_mask* bm, int dtype, size_t nsamp_blk)
-    {
-        dedisp_check_block_mask(bm, nsamp_blk);
-        if (!bm) return;
-        if ((uintptr_t)bm->fill % dedisp_fill_bytes(dtype))
-            throw std::invalid_argument("block_mask: misaligned fill");
-        cells = DedispCells{bm->cells, bm->fill, bm->t_origin, (uint64_t)bm->block_len};
-        set = true;
-    }
-    const DedispCells* get() const { return set ? &cells : nullptr; }
-};
 
 // rt_dedisperse_device, _device_opt, rt_dedisperse_bands_device (bt->table in
 // device memory) and rt_dedisperse_device_cells (bm: cells and fill in device

@@ -51,8 +51,9 @@
 //
 // The launchers at the end choose by sample type in one place, dd_dispatch:
 // launch_zero_dm_mean, launch_channel_stats and the zero-DM transpose are one
-// call of it each.  launch_dedisperse fills the workspace with 8-bit or
-// float32 rows, then makes the one launch_sum call of those rows.
+// call of it each.  launch_dedisp_rows fills the workspace with 8-bit or
+// float32 rows; launch_dedisperse calls it, then makes the one launch_sum call
+// of those rows.
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
@@ -883,24 +884,20 @@ hipError_t launch_block_stats(const void* block, int dtype, uint32_t nsamp_blk, 
     return hipGetLastError();
 }
 
-// Two steps.  The block goes to channel-major rows in the workspace: float32
-// rows for float and 16-bit data and for every type under the zero-DM filter
-// (x - m, m behind the rows), 8-bit rows otherwise (signed samples biased by
-// 128, 1/2/4-bit samples unpacked).  Then one sum over whichever rows they are.
-// With a block mask the first step's kernels are the DdCells instantiations:
-// the workspace then holds x' (or x' - m), and the sum is the same launch.
-hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
-                             const int32_t* d_delays, const uint8_t* d_mask, uint32_t ndm, uint32_t max_delay,
-                             float* out, uint64_t out_stride, void* ws, uint32_t flags, hipStream_t s,
-                             const uint32_t* d_bands, uint32_t nbands, const DedispCells* bm)
+// The first step of launch_dedisperse, alone (launch_pulse_cutouts of
+// cutout_kernels.hip reads the same rows): the block to channel-major rows in
+// the workspace -- float32 rows for float and 16-bit data and for every type
+// under the zero-DM filter (x - m, m behind the rows), 8-bit rows otherwise
+// (signed samples biased by 128, 1/2/4-bit samples unpacked).  With a block
+// mask the kernels are the DdCells instantiations: the workspace then holds x'
+// (or x' - m).
+hipError_t launch_dedisp_rows(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
+                              const uint8_t* d_mask, void* ws, uint32_t flags, hipStream_t s, const DedispCells* bm)
 {
-    const uint32_t nout = nsamp_blk - max_delay;
     const int nbits = dedisp_packed_bits(dtype);
     const bool zero_dm = flags & RT_DEDISP_ZERO_DM;
-    const bool float_rows = zero_dm || nbits == 16 || dtype == RT_DEDISP_F32;
-    const uint64_t pitch_bytes = dedisp_pitch_bytes(float_rows ? RT_DEDISP_F32 : dtype, nsamp_blk);
-    const dim3 sum_grid((nout + kDdTile - 1) / kDdTile, (ndm + kDdDms - 1) / kDdDms);
-    if (float_rows) {
+    const uint64_t pitch_bytes = dedisp_pitch_bytes(dedisp_float_rows(dtype, flags) ? RT_DEDISP_F32 : dtype, nsamp_blk);
+    if (dedisp_float_rows(dtype, flags)) {
         const uint64_t pitch = pitch_bytes / 4;
         const dim3 grid((uint32_t)((pitch + 63) / 64), (nchans + 63) / 64);
         if (zero_dm) {
@@ -927,34 +924,50 @@ hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, u
                                    (const float*)block, nsamp_blk, nchans, (float*)ws, pitch, cells);
             });
         }
-        launch_sum(sum_grid, s, (const float*)ws, pitch, nchans, d_delays, d_mask, ndm, max_delay, nout, out, out_stride,
-                   0, d_bands, nbands);
-    } else {
-        if (nbits) {   // the values themselves: no bias
-            const uint32_t row_bytes = (uint32_t)((uint64_t)nchans * nbits / 8);
-            const uint32_t dwords = row_bytes % 4 == 0 && (uintptr_t)block % 4 == 0;
-            const dim3 grid((uint32_t)((pitch_bytes + 255) / 256), (row_bytes + 63) / 64);
-            const auto unpack = [&](auto tag) {
-                dd_cells(bm, [&](auto cells) {
-                    hipLaunchKernelGGL((dedisp_unpack_transpose_kernel<decltype(tag)::kBits, decltype(cells)>), grid,
-                                       dim3(kDdThreads), 0, s, (const uint8_t*)block, nsamp_blk, nchans, row_bytes,
-                                       (uint8_t*)ws, pitch_bytes, dwords, cells);
-                });
-            };
-            if (nbits == 1) unpack(DdBits<1>{});
-            else if (nbits == 2) unpack(DdBits<2>{});
-            else unpack(DdBits<4>{});
-        } else {
-            const dim3 grid((uint32_t)((pitch_bytes + 255) / 256), (nchans + 63) / 64);
+    } else if (nbits) {   // the values themselves: no bias
+        const uint32_t row_bytes = (uint32_t)((uint64_t)nchans * nbits / 8);
+        const uint32_t dwords = row_bytes % 4 == 0 && (uintptr_t)block % 4 == 0;
+        const dim3 grid((uint32_t)((pitch_bytes + 255) / 256), (row_bytes + 63) / 64);
+        const auto unpack = [&](auto tag) {
             dd_cells(bm, [&](auto cells) {
-                hipLaunchKernelGGL(dedisp_transpose8_kernel<decltype(cells)>, grid, dim3(kDdThreads), 0, s,
-                                   (const uint8_t*)block, nsamp_blk, nchans, (uint8_t*)ws, pitch_bytes,
-                                   dtype == RT_DEDISP_I8 ? 0x80u : 0u, cells);
+                hipLaunchKernelGGL((dedisp_unpack_transpose_kernel<decltype(tag)::kBits, decltype(cells)>), grid,
+                                   dim3(kDdThreads), 0, s, (const uint8_t*)block, nsamp_blk, nchans, row_bytes,
+                                   (uint8_t*)ws, pitch_bytes, dwords, cells);
             });
-        }
+        };
+        if (nbits == 1) unpack(DdBits<1>{});
+        else if (nbits == 2) unpack(DdBits<2>{});
+        else unpack(DdBits<4>{});
+    } else {
+        const dim3 grid((uint32_t)((pitch_bytes + 255) / 256), (nchans + 63) / 64);
+        dd_cells(bm, [&](auto cells) {
+            hipLaunchKernelGGL(dedisp_transpose8_kernel<decltype(cells)>, grid, dim3(kDdThreads), 0, s,
+                               (const uint8_t*)block, nsamp_blk, nchans, (uint8_t*)ws, pitch_bytes,
+                               dtype == RT_DEDISP_I8 ? 0x80u : 0u, cells);
+        });
+    }
+    return hipGetLastError();
+}
+
+// Two steps.  The block goes to channel-major rows in the workspace
+// (launch_dedisp_rows).  Then one sum over whichever rows they are.
+hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
+                             const int32_t* d_delays, const uint8_t* d_mask, uint32_t ndm, uint32_t max_delay,
+                             float* out, uint64_t out_stride, void* ws, uint32_t flags, hipStream_t s,
+                             const uint32_t* d_bands, uint32_t nbands, const DedispCells* bm)
+{
+    const uint32_t nout = nsamp_blk - max_delay;
+    const bool float_rows = dedisp_float_rows(dtype, flags);
+    const uint64_t pitch_bytes = dedisp_pitch_bytes(float_rows ? RT_DEDISP_F32 : dtype, nsamp_blk);
+    const dim3 sum_grid((nout + kDdTile - 1) / kDdTile, (ndm + kDdDms - 1) / kDdDms);
+    const hipError_t e = launch_dedisp_rows(block, dtype, nsamp_blk, nchans, d_mask, ws, flags, s, bm);
+    if (e != hipSuccess) return e;
+    if (float_rows)
+        launch_sum(sum_grid, s, (const float*)ws, pitch_bytes / 4, nchans, d_delays, d_mask, ndm, max_delay, nout, out,
+                   out_stride, 0, d_bands, nbands);
+    else
         launch_sum(sum_grid, s, (const uint8_t*)ws, pitch_bytes, nchans, d_delays, d_mask, ndm, max_delay, nout, out,
                    out_stride, dtype == RT_DEDISP_I8 ? 128 : 0, d_bands, nbands);
-    }
     return hipGetLastError();
 }
 

@@ -30,6 +30,13 @@ constexpr bool dedisp_known_dtype(int dtype)
 // exact in float32 up to RT_DEDISP_MAX_CHANS_8BIT channels
 constexpr bool dedisp_integer_sum(int dtype) { return dtype != RT_DEDISP_F32 && dtype != RT_DEDISP_U16; }
 
+// whether the transposed rows of the workspace are float32 (float and 16-bit
+// data, and every type under the zero-DM filter) or 8-bit
+constexpr bool dedisp_float_rows(int dtype, uint32_t flags)
+{
+    return (flags & RT_DEDISP_ZERO_DM) || !dedisp_integer_sum(dtype);
+}
+
 // bytes of a row of the block of a known type (rt_dedisp_row_bytes); packed
 // rows must be whole bytes
 inline size_t dedisp_row_bytes(int dtype, size_t nchans)

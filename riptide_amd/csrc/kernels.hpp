@@ -8,6 +8,7 @@
 #include "harmonic.hpp"
 #include "refine_host.hpp"
 #include "resample_host.hpp"
+#include "riptide_amd.h"
 
 namespace rt {
 
@@ -122,6 +123,14 @@ hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, u
                              float* out, uint64_t out_stride, void* ws, uint32_t flags, hipStream_t s,
                              const uint32_t* d_bands = nullptr, uint32_t nbands = 0,
                              const DedispCells* bm = nullptr);
+// launch_dedisperse's first step alone: the block (with bm: x') to the
+// channel-major rows of ws -- float32 rows when dedisp_float_rows(dtype, flags)
+// (under RT_DEDISP_ZERO_DM x - m, m behind the rows), 8-bit rows otherwise
+// (int8 biased by 128, 1/2/4-bit unpacked); the padding of a row, elements
+// [nsamp_blk, pitch), is written as zero
+hipError_t launch_dedisp_rows(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
+                              const uint8_t* d_mask, void* ws, uint32_t flags, hipStream_t s,
+                              const DedispCells* bm = nullptr);
 // m[t] = (float32)(sum over unmasked c of block[t, c] / their number), t < nsamp_blk
 hipError_t launch_zero_dm_mean(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
                                const uint8_t* d_mask, float* m, hipStream_t s, const DedispCells* bm = nullptr);
@@ -137,6 +146,16 @@ uint64_t blockstats_chunks(uint64_t nsamp_blk, uint64_t block_len);
 uint64_t blockstats_workspace_bytes(uint64_t nsamp_blk, uint64_t nchans, uint64_t block_len);
 hipError_t launch_block_stats(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans, uint32_t block_len,
                               double* stats, void* ws, hipStream_t s);
+
+// cutout_kernels.hip (the tile, the staging rule and the checks: cutout_host.hpp)
+// ws: the rows launch_dedisp_rows left for this dtype and these flags.  Job i
+// of d_jobs (device memory, checked by the caller: cutout_check_jobs) writes
+// its nbins floats from out + out_off; max_tiles = ceil(the largest nbins /
+// kCutoutTile) <= kCutoutMaxTiles, njobs >= 1.
+hipError_t launch_pulse_cutouts(const void* ws, int dtype, uint32_t flags, uint32_t nsamp_blk, uint32_t nchans,
+                                const int32_t* d_delays, uint32_t ndelay_rows, uint32_t max_delay,
+                                const uint8_t* d_mask, const rt_cutout_spec* d_jobs, uint32_t njobs,
+                                uint32_t max_tiles, float* out, hipStream_t s);
 
 // resample_kernels.hip
 // out[r, j] = x[T.src[r], resample_index(T.factor[r], j, N)] for r < rows <=

@@ -783,6 +783,82 @@ def dedisperse_bands_device(block, delays, max_delay, bands, mask=None, out=None
                               block_mask, t_origin)
 
 
+# rt_cutout_spec (include/riptide_amd.h)
+CUTOUT_JOB_DTYPE = np.dtype([("start", np.int64), ("out_off", np.uint64), ("factor", np.uint32),
+                             ("nbins", np.uint32), ("delay_row", np.uint32), ("band_lo", np.uint32),
+                             ("band_hi", np.uint32), ("reserved", np.uint32)])
+
+
+def checked_cutout_jobs(jobs):
+    """jobs as a contiguous one-dimensional CUTOUT_JOB_DTYPE array; ValueError
+    for anything else."""
+    jobs = np.asarray(jobs)
+    if jobs.dtype != CUTOUT_JOB_DTYPE or jobs.ndim != 1:
+        raise ValueError("jobs must be a one-dimensional array of engine.CUTOUT_JOB_DTYPE records")
+    return np.ascontiguousarray(jobs)
+
+
+def pulse_cutouts_plan(esize, lo, hi):
+    """(tile, ndw, staged) of the cutout kernel (rt_pulse_cutouts_plan; no
+    device call): the bins of a tile, and for a channel whose clamped span of
+    a tile is the elements [lo, hi) of its row -- esize 1 for 8-bit rows, 4
+    for float rows -- the dwords it takes and whether they go through LDS or
+    the row is read directly (8-bit rows: staged iff (lo & 3) + hi - lo <=
+    4096; float rows: iff hi - lo <= 1024)."""
+    tile, ndw, staged = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_int()
+    _check(_L.rt_pulse_cutouts_plan(int(esize), int(lo), int(hi), ctypes.byref(tile), ctypes.byref(ndw),
+                                    ctypes.byref(staged)))
+    return tile.value, ndw.value, bool(staged.value)
+
+
+def pulse_cutouts_device(block, jobs, delays, max_delay, mask=None, out=None, workspace=None, stream=None,
+                         zero_dm=False, nbits=None, block_mask=None, t_origin=0):
+    """Dedispersed, time-decimated windows of one resident block, one per job
+    (rt_pulse_cutouts_device): jobs is a host array of CUTOUT_JOB_DTYPE, delays
+    int32 [R, nchans] on the block's device (entries clamped to [0, max_delay]
+    as they are read), and job (start, factor f, nbins T, delay_row, [band_lo,
+    band_hi), out_off) writes
+
+      out[out_off + n] = sum over unmasked c in [band_lo, band_hi) and j < f of
+                         block[start + n * f + j + delays[delay_row, c], c]
+
+    for n < T; start is relative to the block's row 0 and may be negative, and
+    a sample outside the block's rows is skipped.  Returns out, a contiguous
+    float32 [>= every out_off + nbins] tensor (allocated to exactly that when
+    None).  8-bit sums are exact integers; float sums (float32, 16-bit, and
+    everything under zero_dm) are added in channel order, then sample order, and
+    equal pulse_candidates.pulse_cutouts_host bit for bit.  block, mask,
+    workspace (dedisperse_workspace_bytes), nbits, zero_dm, block_mask and
+    t_origin as for dedisperse_device.  Stream-ordered, no host
+    synchronisation; no jobs: an empty tensor (or out), nothing launched."""
+    import torch
+    name, nsamp_blk, nchans = _dedisp_block(block, nbits)
+    bm = _block_mask_struct(block_mask, t_origin, block, name, nchans)
+    jobs = checked_cutout_jobs(jobs)
+    if (delays.dim() != 2 or delays.dtype != torch.int32 or delays.device != block.device
+            or not delays.is_contiguous() or delays.shape[1] != nchans):
+        raise ValueError("delays must be a contiguous int32 [R, nchans] tensor on the block's device")
+    _check_device_mask(mask, block, nchans)
+    need_out = int((jobs["out_off"] + jobs["nbins"]).max()) if jobs.size else 0
+    with stream_scope(block.device, stream) as (_, handle):
+        out = checked_out(out, (need_out,), torch.float32, block.device,
+                          f"out must be a contiguous float32 [>= {need_out}] tensor on the block's device",
+                          lambda o: (o.dim() != 1 or o.dtype != torch.float32 or o.device != block.device
+                                     or not o.is_contiguous() or o.numel() < need_out))
+        if not jobs.size:
+            return out
+        need = dedisperse_workspace_bytes(name, nsamp_blk, nchans, zero_dm)
+        workspace = checked_workspace(workspace, need, block.device, "block", floor=16)
+        d_jobs = torch.empty(jobs.size * CUTOUT_JOB_DTYPE.itemsize, dtype=torch.uint8, device=block.device)
+        _check(_L.rt_pulse_cutouts_device(_lib.ptr(block), DEDISP_DTYPES[name], nsamp_blk, nchans, _lib.ptr(delays),
+                                          delays.shape[0], int(max_delay), None if mask is None else _lib.ptr(mask),
+                                          _lib.ptr(jobs), jobs.size, _lib.ptr(d_jobs), _lib.ptr(out), out.numel(),
+                                          _lib.ptr(workspace), workspace.numel(), handle,
+                                          DEDISP_ZERO_DM if zero_dm else 0,
+                                          None if bm is None else ctypes.byref(bm)))
+    return out
+
+
 def profile_enable(on=True):
     _check(_L.rt_profile_enable(int(bool(on))))
 

@@ -183,7 +183,7 @@ def search_pulses(series, tsamp, dms, widths=None, threshold=8.0, radius=None, t
 
 def search_filterbank_pulses(fb_or_fname, dms, deredden_params, widths=None, threshold=8.0, mask=None, zero_dm=False,
                              kdm=None, nout=None, batch=8, device=None, radius=None, time_radius=None, dm_gap=1,
-                             max_events=1 << 20, block_mask=None):
+                             max_events=1 << 20, block_mask=None, cutouts=None):
     """Single-pulse search of a channelised SIGPROC file (a file name, a
     reading.Filterbank or PackedFilterbank) at the trial DMs without leaving
     the device: dedispersion.dedisperse_filterbank, then slices of `batch` DMs
@@ -191,7 +191,14 @@ def search_filterbank_pulses(fb_or_fname, dms, deredden_params, widths=None, thr
     seconds, rmed_minpts) and engine.single_pulse_device, one download of the
     events and cluster_events.  mask, zero_dm, kdm, nout, block_mask: as for
     dispatch.search_filterbank.  Returns (pulses, events); `series` of an
-    event is its index into dms."""
+    event is its index into dms.
+
+    cutouts: None, or a dict of keyword arguments of
+    pulse_candidates.build_pulse_candidates (an empty one for its defaults;
+    mask, zero_dm, block_mask, kdm and device default to this call's).  The
+    function then returns (pulses, events, candidates): one PulseCandidate per
+    pulse, in the order of pulses, with the frequency-time and DM-time cutouts
+    read back from the file."""
     from . import engine
     from .dedispersion import KDM
     from .dispatch import _dedispersed
@@ -200,7 +207,8 @@ def search_filterbank_pulses(fb_or_fname, dms, deredden_params, widths=None, thr
     kdm = KDM if kdm is None else float(kdm)
     dms = [float(d) for d in dms]
     if not dms:
-        return [], np.empty(0, dtype=EVENT_DTYPE)
+        none = [], np.empty(0, dtype=EVENT_DTYPE)
+        return none if cutouts is None else none + ([],)
     parts = []
     with _dedispersed(fb, dms, device, max(1, int(batch)), mask=mask, nout=nout, kdm=kdm, zero_dm=zero_dm,
                       block_mask=block_mask) as (series, _, slices):
@@ -211,4 +219,10 @@ def search_filterbank_pulses(fb_or_fname, dms, deredden_params, widths=None, thr
             ev = engine.single_pulse_device(x, w, threshold, radius=radius, max_events=max_events)
             parts.append((b0, ev))
         events = np.concatenate([events_to_host(ev, b0) for b0, ev in parts])
-    return cluster_events(events, dms, fb.tsamp, time_radius=time_radius, dm_gap=dm_gap, widths=w), events
+    pulses = cluster_events(events, dms, fb.tsamp, time_radius=time_radius, dm_gap=dm_gap, widths=w)
+    if cutouts is None:
+        return pulses, events
+    from .pulse_candidates import build_pulse_candidates
+    kwargs = dict(mask=mask, zero_dm=zero_dm, block_mask=block_mask, kdm=kdm, device=device)
+    kwargs.update(cutouts)
+    return pulses, events, build_pulse_candidates(fb, pulses, **kwargs)
