@@ -894,6 +894,106 @@ int rt_dedisperse_device_cells(const void* d_block, int dtype, size_t nsamp_blk,
 int rt_zero_dm_mean_device_cells(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans,
                                  const uint8_t* d_mask, float* d_m, void* stream, const rt_block_mask* bm);
 
+/* ---- DM plan: which trials to search, and each one's time decimation */
+/* Host only, no device, float64.  freqs_mhz are channel centres, ascending or
+ * descending, nchans >= 2.  With
+ *   cw     = (max f - min f) / (nchans - 1)          the channel width
+ *   flo    = min f - cw / 2,  fhi = max f + cw / 2   the band edges
+ *   fmid   = (flo + fhi) / 2
+ *   kdisp  = kdm * (1 / flo^2 - 1 / fhi^2)
+ *   ksmear = kdm * (1 / (fmid - cw/2)^2 - 1 / (fmid + cw/2)^2)
+ *   s(DM)  = max(wmin, ksmear * DM)                  the smearing at that DM
+ *   r(DM)  = s(DM) / kdisp                           the coverage radius
+ * the trials are DM_0 = dm_min and DM_{i+1} the DM whose radius touches the
+ * previous one's, DM_{i+1} - r(DM_{i+1}) = DM_i + r(DM_i): with e = DM_i +
+ * r(DM_i), e + wmin / kdisp, or when ksmear times that exceeds wmin,
+ * e / (1 - ksmear / kdisp).  The last trial is the first with DM + r(DM) >=
+ * dm_max.  downsamp[i] is the largest power of two f <= max_downsamp with
+ * f * tsamp * oversample <= s(DM_i), at least 1; it never decreases with i.
+ * *ntrials is the number of trials; dms and downsamp (both or neither NULL:
+ * a count alone) take them when capacity >= *ntrials.  RT_EINVAL for nchans <
+ * 2, a frequency, tsamp, wmin, oversample or kdm that is not positive and
+ * finite, a dm_min that is negative or not finite, dm_max < dm_min or not
+ * finite, max_downsamp outside [1, RT_DEDISP_MAX_DOWNSAMP], more than
+ * RT_DM_PLAN_MAX_TRIALS trials, or a capacity below the count. */
+#define RT_DEDISP_MAX_DOWNSAMP 256
+#define RT_DM_PLAN_MAX_TRIALS (1u << 20)
+int rt_dm_plan(const double* freqs_mhz, size_t nchans, double tsamp, double dm_min, double dm_max, double wmin,
+               double oversample, uint32_t max_downsamp, double kdm, double* dms, uint32_t* downsamp,
+               size_t capacity, size_t* ntrials);
+
+/* ---- dedispersion decimated in time: a step of factor f */
+/* Decimation first, the sum second.  With x' the block after the block mask
+ * (under RT_DEDISP_ZERO_DM: x' - m, as above), f = downsamp and delays the
+ * table of rt_dedisperse_delays at tsamp * f:
+ *   z[u, c]   = sum over i = 0 .. f - 1 of x'[f * u + i, c]     u < nsamp / f
+ *   out[d, u] = sum over unmasked c, ascending, of z[u + delay[d, c], c]
+ * Both sums are float32 additions from 0.0f in index order.  For 8-bit and
+ * 1/2/4-bit samples without the zero-DM filter every partial sum is an
+ * integer: a call with vmax * f * nchans >= 2^24 (vmax = 255, or 2^nbits - 1)
+ * is RT_EINVAL, so those outputs are exact.  The trailing nsamp % f samples
+ * are dropped.  f = 1 is rt_dedisperse_host_opt, bit for bit. */
+/* Host only, no device: the specification.  delays int64 [ndm, nchans] in
+ * decimated samples, every entry in [0, max_delay]; out [ndm, nout] with nout
+ * + max_delay <= nsamp / f; bm NULL or a block mask in host memory whose
+ * t_origin is a multiple of f.  RT_EINVAL for downsamp outside [1,
+ * RT_DEDISP_MAX_DOWNSAMP], the exactness cap, and everything
+ * rt_dedisperse_host_opt and rt_block_replace_host refuse. */
+int rt_dedisperse_ds_host(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
+                          const uint8_t* mask, size_t ndm, int64_t max_delay, size_t downsamp, size_t nout,
+                          float* out, uint32_t flags, const rt_block_mask* bm);
+/* One step of a step table: ndm DMs of one factor.  The step's delay table is
+ * int32 [ndm, nchans] from element delays_off of the call's delay array, its
+ * output rows start at float out_off of the call's output array:
+ *   out[out_off + d * out_stride + out_offset + u]
+ * for u in [0, nsamp_blk / downsamp - max_delay). */
+typedef struct rt_dedisp_step {
+    uint64_t delays_off;   /* int32 elements into d_delays */
+    uint64_t out_off;      /* floats into d_out */
+    uint64_t out_stride;   /* floats between DM rows */
+    uint64_t out_offset;   /* first column written */
+    uint32_t ndm;          /* >= 1 */
+    uint32_t max_delay;    /* decimated samples */
+    uint32_t downsamp;     /* f, in [1, RT_DEDISP_MAX_DOWNSAMP] */
+    uint32_t reserved;     /* 0 */
+} rt_dedisp_step;
+/* Host only, no device: the checks of rt_dedisperse_steps_device on a step
+ * table in host memory.  RT_EINVAL for nsteps == 0 or a NULL table, a
+ * downsamp outside [1, RT_DEDISP_MAX_DOWNSAMP], ndm == 0 or too many DMs,
+ * max_delay >= nsamp_blk / downsamp, a non-zero reserved, the exactness cap
+ * above, a delay table that leaves the delays_len elements, output rows that
+ * leave the out_floats floats or an out_stride below out_offset plus the
+ * step's outputs, a block mask whose t_origin is not a multiple of every
+ * downsamp, and the shapes rt_dedisperse_device_cells refuses. */
+int rt_dedisperse_steps_check(int dtype, size_t nsamp_blk, size_t nchans, const rt_dedisp_step* steps,
+                              size_t nsteps, size_t delays_len, size_t out_floats, uint32_t flags,
+                              const rt_block_mask* bm);
+/* Device workspace bytes of rt_dedisperse_steps_device: the rows of
+ * rt_dedisperse_workspace_bytes_opt, then one float32 area of nchans rows of
+ * nsamp_blk / f samples (the pitch padded to 16 bytes) for the smallest f > 1
+ * of factors[nfactors], which every decimated step reuses in stream order. */
+int rt_dedisperse_steps_workspace_bytes(int dtype, size_t nsamp_blk, size_t nchans, const uint32_t* factors,
+                                        size_t nfactors, uint32_t flags, size_t* bytes);
+/* Every step of a table from one resident block, stream-ordered, no
+ * synchronisation: the block goes to the channel-major rows once, as in
+ * rt_dedisperse_device_cells; a step with downsamp == 1 is that call's sum
+ * (its bits), any other first decimates the rows into the float32 area and
+ * sums those with the float32 sum.  steps is in host memory.  RT_EINVAL
+ * (nothing is launched) for everything rt_dedisperse_steps_check refuses, a
+ * NULL or misaligned pointer and a workspace below
+ * rt_dedisperse_steps_workspace_bytes. */
+int rt_dedisperse_steps_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans,
+                               const int32_t* d_delays, size_t delays_len, const uint8_t* d_mask,
+                               const rt_dedisp_step* steps, size_t nsteps, float* d_out, size_t out_floats,
+                               void* d_workspace, size_t workspace_bytes, void* stream, uint32_t flags,
+                               const rt_block_mask* bm);
+/* Host-buffer form, as rt_dedisperse_opt: x, the delays (int64 [delays_len],
+ * every step's entries in [0, its max_delay]) and the mask are uploaded, out
+ * [out_floats] copied back.  Synchronous; no block mask. */
+int rt_dedisperse_steps(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
+                        size_t delays_len, const uint8_t* mask, const rt_dedisp_step* steps, size_t nsteps,
+                        float* out, size_t out_floats, uint32_t flags);
+
 /* ------------------------------ pulse cutouts ------------------------------ */
 /* Dedispersed, time-decimated windows of one block, one per job: the
  * frequency-time and DM-time cutouts of single-pulse candidates.  Let x' be

@@ -22,7 +22,8 @@ from .peak_cluster import PeakCluster
 from .candidate import Candidate, build_candidates, build_candidates_filterbank
 from .harmonic_testing import apply_candidate_filters, flag_harmonics, hdiag, htest
 from .reading import Filterbank, PackedFilterbank, open_filterbank
-from .dispatch import search_filterbank, search_filterbank_accel
+from .dispatch import search_filterbank, search_filterbank_accel, search_filterbank_plan
+from .dedispersion import DMPlan, dm_plan
 from .refine import Refinement, refine_candidates, refine_cube
 from .single_pulse import SinglePulse, search_filterbank_pulses
 from .pulse_candidates import PulseCandidate, build_pulse_candidates
@@ -39,4 +40,5 @@ __all__ = [
     "SinglePulse", "search_filterbank_pulses", "single_pulse",
     "PulseCandidate", "build_pulse_candidates", "pulse_candidates",
     "acceleration", "search_filterbank_accel",
+    "dm_plan", "DMPlan", "search_filterbank_plan",
 ]

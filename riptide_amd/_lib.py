@@ -170,6 +170,24 @@ _SIGNATURES = {
                                           _c_sz, _c_sz, _vp, _c_sz, _vp, ctypes.c_uint32, _vp]),
     # rt_zero_dm_mean_device's arguments, then bm
     "rt_zero_dm_mean_device_cells": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _vp, _vp]),
+    # freqs, nchans, tsamp, dm_min, dm_max, wmin, oversample, max_downsamp, kdm, dms, downsamp (uint32), capacity,
+    # ntrials
+    "rt_dm_plan": (_c_i, [_vp, _c_sz, _c_d, _c_d, _c_d, _c_d, _c_d, ctypes.c_uint32, _c_d, _vp, _vp, _c_sz, _psz]),
+    # x, dtype, nsamp, nchans, delays (int64), mask, ndm, max_delay, downsamp, nout, out, flags, bm
+    "rt_dedisperse_ds_host": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _vp, _c_sz, ctypes.c_int64, _c_sz, _c_sz, _vp,
+                                     ctypes.c_uint32, _vp]),
+    # the step table: `steps` is a numpy array of engine.DEDISP_STEP_DTYPE (rt_dedisp_step) in host memory
+    # dtype, nsamp_blk, nchans, steps, nsteps, delays_len, out_floats, flags, bm
+    "rt_dedisperse_steps_check": (_c_i, [_c_i, _c_sz, _c_sz, _vp, _c_sz, _c_sz, _c_sz, ctypes.c_uint32, _vp]),
+    # dtype, nsamp_blk, nchans, factors (uint32), nfactors, flags, bytes
+    "rt_dedisperse_steps_workspace_bytes": (_c_i, [_c_i, _c_sz, _c_sz, _vp, _c_sz, ctypes.c_uint32, _psz]),
+    # block, dtype, nsamp_blk, nchans, delays (int32), delays_len, mask, steps, nsteps, out, out_floats, workspace,
+    # workspace bytes, stream, flags, bm
+    "rt_dedisperse_steps_device": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _c_sz, _vp, _vp, _c_sz, _vp, _c_sz, _vp,
+                                          _c_sz, _vp, ctypes.c_uint32, _vp]),
+    # x, dtype, nsamp, nchans, delays (int64), delays_len, mask, steps, nsteps, out, out_floats, flags
+    "rt_dedisperse_steps": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _c_sz, _vp, _vp, _c_sz, _vp, _c_sz,
+                                   ctypes.c_uint32]),
     # x, dtype, nsamp, nchans, delays (int32 [rows, nchans]), rows, max_delay, mask, jobs (rt_cutout_spec[njobs]),
     # njobs, out, out floats, flags, bm
     "rt_pulse_cutouts_host": (_c_i, [_vp, _c_i, _c_sz, _c_sz, _vp, _c_sz, ctypes.c_int64, _vp, _vp, _c_sz, _vp, _c_sz,

@@ -4,7 +4,9 @@
 // one and the host-buffer one, each with an optional band table; the
 // resident-block core also takes an optional block mask (rt_block_mask), as
 // the zero-DM mean does, and the block statistics stand beside the channel
-// statistics.
+// statistics.  The step-table calls (rt_dedisperse_steps*: the steps of a DM
+// plan, each decimated in time) check their table with dedisp_check_steps of
+// dedisp_types.hpp, which the host-only rt_dedisperse_steps_check shares.
 #include "riptide_amd.h"
 
 #include <mutex>
@@ -21,22 +23,7 @@ using namespace rt;
 
 namespace {
 
-void dedisp_check_shape(int dtype, size_t nsamp_blk, size_t nchans, size_t ndm, int64_t max_delay)
-{
-    if (!dedisp_known_dtype(dtype)) throw std::invalid_argument("dedisperse: unknown sample type code");
-    if (!nchans || !ndm) throw std::invalid_argument("dedisperse: nchans and ndm must be at least 1");
-    dedisp_check_chan_cap(dtype, nchans);
-    if (nchans > 65535ull * 64) throw std::invalid_argument("dedisperse: too many channels");
-    if (ndm > 65535ull * 16) throw std::invalid_argument("dedisperse: too many DMs for one call");
-    if (nsamp_blk >= (1ull << 31)) throw std::invalid_argument("dedisperse: a block must be below 2^31 samples");
-    // packed rows: whole bytes, and nsamp_blk * row_bytes inside the kernels' 64-bit byte offsets
-    // (row_bytes < 2^23 by the channel limit above)
-    if (dedisp_packed_bits(dtype) && dedisp_row_bytes(dtype, nchans) > (~0ull >> 1) / (nsamp_blk ? nsamp_blk : 1))
-        throw std::invalid_argument("dedisperse: the block's bytes overflow a 64-bit offset");
-    if (max_delay < 0 || (uint64_t)max_delay >= nsamp_blk)
-        throw std::invalid_argument("dedisperse: max_delay must be in [0, nsamp): the block is no longer than the "
-                                    "largest delay");
-}
+// (the shape limits of a call, dedisp_check_shape, and the step table's checks: dedisp_types.hpp)
 
 // The band table of the band forms, in device memory for the resident-block
 // call and in host memory for the host-buffer one; no BandTable (a null
@@ -130,6 +117,25 @@ int dedisperse_buffers(const void* x, int dtype, size_t nsamp, size_t nchans, co
         sync(c.stream);
         return RT_OK;
     });
+}
+
+// the smallest downsamp > 1 of a list of factors (0: none): what sizes the decimated area
+uint32_t steps_min_factor(const uint32_t* factors, size_t n)
+{
+    uint32_t fmin = 0;
+    for (size_t i = 0; i < n; ++i) {
+        dedisp_check_downsamp(factors[i]);
+        if (factors[i] > 1 && (!fmin || factors[i] < fmin)) fmin = factors[i];
+    }
+    return fmin;
+}
+
+uint64_t steps_workspace_bytes(int dtype, size_t nsamp_blk, size_t nchans, const rt_dedisp_step* steps,
+                               size_t nsteps, uint32_t flags)
+{
+    std::vector<uint32_t> factors(nsteps);
+    for (size_t k = 0; k < nsteps; ++k) factors[k] = steps[k].downsamp;
+    return dedisp_steps_workspace_bytes(dtype, nsamp_blk, nchans, flags, steps_min_factor(factors.data(), nsteps));
 }
 
 // the statistics have no exactness limit on the channel count of 8-bit data
@@ -226,6 +232,79 @@ int rt_dedisperse_device_cells(const void* d_block, int dtype, size_t nsamp_blk,
     return dedisperse_device(d_block, dtype, nsamp_blk, nchans, d_delays, d_mask, ndm,
                              d_bands || nbands ? &bt : nullptr, max_delay, d_out, out_stride, out_offset, d_ws,
                              ws_bytes, stream, flags, bm);
+}
+
+int rt_dedisperse_steps_workspace_bytes(int dtype, size_t nsamp_blk, size_t nchans, const uint32_t* factors,
+                                        size_t nfactors, uint32_t flags, size_t* bytes)
+{
+    return guarded([&] {
+        if (!bytes) throw std::invalid_argument("dedisperse: bytes is NULL");
+        if (nfactors && !factors) throw std::invalid_argument("dedisperse: factors is NULL");
+        dedisp_check_flags(flags);
+        dedisp_check_shape(dtype, nsamp_blk, nchans, 1, 0);
+        *bytes = (size_t)dedisp_steps_workspace_bytes(dtype, nsamp_blk, nchans, flags,
+                                                      steps_min_factor(factors, nfactors));
+        return RT_OK;
+    });
+}
+
+int rt_dedisperse_steps_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans,
+                               const int32_t* d_delays, size_t delays_len, const uint8_t* d_mask,
+                               const rt_dedisp_step* steps, size_t nsteps, float* d_out, size_t out_floats,
+                               void* d_ws, size_t ws_bytes, void* stream, uint32_t flags, const rt_block_mask* bm)
+{
+    return guarded([&] {
+        dedisp_check_steps(dtype, nsamp_blk, nchans, steps, nsteps, delays_len, out_floats, flags, bm);
+        const DeviceCells dc(bm, dtype, nsamp_blk);
+        if (!d_block || !d_delays || !d_out || !d_ws) throw std::invalid_argument("dedisperse: null device pointer");
+        if ((uintptr_t)d_ws % 16 || (uintptr_t)d_delays % 4 || (uintptr_t)d_out % 4 ||
+            (dtype == RT_DEDISP_F32 && (uintptr_t)d_block % 4))
+            throw std::invalid_argument("dedisperse: misaligned device pointer");
+        if (ws_bytes < steps_workspace_bytes(dtype, nsamp_blk, nchans, steps, nsteps, flags))
+            throw std::invalid_argument("workspace too small");
+        ck(launch_dedisperse_steps(d_block, dtype, (uint32_t)nsamp_blk, (uint32_t)nchans, d_delays, d_mask, steps,
+                                   nsteps, d_out, d_ws, flags, (hipStream_t)stream, dc.get()),
+           "dedisperse");
+        return RT_OK;
+    });
+}
+
+int rt_dedisperse_steps(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
+                        size_t delays_len, const uint8_t* mask, const rt_dedisp_step* steps, size_t nsteps,
+                        float* out, size_t out_floats, uint32_t flags)
+{
+    return guarded([&] {
+        dedisp_check_steps(dtype, nsamp, nchans, steps, nsteps, delays_len, out_floats, flags, nullptr);
+        if (!x || !delays || !out) throw std::invalid_argument("dedisperse: null buffer");
+        std::vector<int32_t> del(delays_len);
+        for (size_t k = 0; k < nsteps; ++k) {   // tables that overlap are checked once per step
+            const rt_dedisp_step& st = steps[k];
+            for (size_t i = st.delays_off; i < st.delays_off + (size_t)st.ndm * nchans; ++i) {
+                if (delays[i] < 0 || delays[i] > (int64_t)st.max_delay)
+                    throw std::invalid_argument("dedisperse: a delay is outside [0, max_delay]");
+                del[i] = (int32_t)delays[i];
+            }
+        }
+        const size_t in_bytes = nsamp * dedisp_row_bytes(dtype, nchans);
+        const size_t ws_bytes = (size_t)steps_workspace_bytes(dtype, nsamp, nchans, steps, nsteps, flags);
+        std::lock_guard<std::mutex> lk(g_mu);
+        Context& c = context();
+        void* dx = c.buf[0].get(in_bytes);
+        float* dz = dev<float>(c, 1, out_floats);
+        void* dw = c.buf[2].get(ws_bytes);
+        int32_t* dd = dev<int32_t>(c, 3, del.size());
+        uint8_t* dm = mask ? dev<uint8_t>(c, 4, nchans) : nullptr;
+        h2d(dx, x, in_bytes, c.stream);
+        h2d(dz, out, out_floats * 4, c.stream);   // what no step writes comes back as it was
+        h2d(dd, del.data(), del.size() * 4, c.stream);
+        if (mask) h2d(dm, mask, nchans, c.stream);
+        ck(launch_dedisperse_steps(dx, dtype, (uint32_t)nsamp, (uint32_t)nchans, dd, dm, steps, nsteps, dz, dw, flags,
+                                   c.stream),
+           "dedisperse");
+        d2h(out, dz, out_floats * 4, c.stream);
+        sync(c.stream);
+        return RT_OK;
+    });
 }
 
 int rt_zero_dm_mean_device(const void* d_block, int dtype, size_t nsamp_blk, size_t nchans, const uint8_t* d_mask,

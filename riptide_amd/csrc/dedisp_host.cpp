@@ -4,6 +4,7 @@
 // for theirs).  No HIP header (`make asan` builds this file as is).
 #include "riptide_amd.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -146,9 +147,197 @@ void dedisperse_host(const void* x, int dtype, size_t nsamp, size_t nchans, cons
     });
 }
 
+// ---- a step of factor f (riptide_amd.h, rt_dedisperse_ds_host): decimation
+// first, z [nz, nchans], then the sum of z along the sweep
+// integer samples without the zero-DM filter: exact int32 sums (the cap keeps
+// them below 2^24), converted once
+template <class T>
+void decimate_rows_int(const T* x, size_t nchans, size_t f, size_t nz, float* z)
+{
+    for (size_t u = 0; u < nz; ++u)
+        for (size_t c = 0; c < nchans; ++c) {
+            int32_t acc = 0;
+            for (size_t i = 0; i < f; ++i) acc += (int32_t)x[(u * f + i) * nchans + c];
+            z[u * nchans + c] = (float)acc;
+        }
+}
+
+// everything else: float32 additions from 0.0f in index order; m (NULL: none)
+// is the zero-DM mean series
+template <class T>
+void decimate_rows_f32(const T* x, size_t nchans, size_t f, size_t nz, const float* m, float* z)
+{
+    for (size_t u = 0; u < nz; ++u)
+        for (size_t c = 0; c < nchans; ++c) {
+            float acc = 0.0f;
+            for (size_t i = 0; i < f; ++i) {
+                const size_t t = u * f + i;
+                const float v = (float)x[t * nchans + c];
+                acc += m ? v - m[t] : v;
+            }
+            z[u * nchans + c] = acc;
+        }
+}
+
+void dedisperse_ds_host(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
+                        const uint8_t* mask, size_t ndm, int64_t max_delay, size_t f, size_t nout, float* out,
+                        uint32_t flags, const rt_block_mask* bm)
+{
+    dedisp_check_flags(flags);
+    if (!nchans || !ndm) throw std::invalid_argument("dedisperse: nchans and ndm must be at least 1");
+    dedisp_check_dtype(dtype, nchans, false);
+    dedisp_check_downsamp(f);
+    dedisp_check_block_mask(bm, nsamp);
+    dedisp_check_mask_origin(bm, f);
+    std::vector<uint8_t> replaced;
+    if (bm && nsamp) {
+        if (!x) throw std::invalid_argument("dedisperse: null buffer");
+        replaced.resize(nsamp * dedisp_row_bytes(dtype, nchans));
+        block_replace(x, dtype, nsamp, nchans, bm, replaced.data());
+        x = replaced.data();
+    }
+    if (f == 1) {   // today's path, today's bits
+        dedisperse_host(x, dtype, nsamp, nchans, delays, mask, ndm, max_delay, nout, out, flags, Bands{});
+        return;
+    }
+    const size_t nz = nsamp / f;
+    if (max_delay < 0 || max_delay >= 2147483648ll)
+        throw std::invalid_argument("dedisperse: max_delay is outside [0, 2^31)");
+    if (nout > nz || (uint64_t)max_delay > nz - nout)
+        throw std::invalid_argument("dedisperse: nout + max_delay exceeds the " + std::to_string(nz) +
+                                    " decimated samples of the input");
+    dedisp_check_chan_cap(dtype, nchans);
+    dedisp_check_ds_cap(dtype, nchans, f, flags);
+    for (size_t i = 0; i < ndm * nchans; ++i)
+        if (delays[i] < 0 || delays[i] > max_delay)
+            throw std::invalid_argument("dedisperse: a delay is outside [0, max_delay]");
+    if (!nout) return;
+    std::vector<float> z(nz * nchans);
+    with_samples(x, dtype, nsamp, nchans, [&](const auto* v) {
+        using T = typename std::remove_cv<typename std::remove_pointer<decltype(v)>::type>::type;
+        if (flags & RT_DEDISP_ZERO_DM) {
+            std::vector<float> m(nsamp);
+            zero_dm_mean(v, nsamp, nchans, mask, m.data());
+            decimate_rows_f32(v, nchans, f, nz, m.data(), z.data());
+        } else if constexpr (sizeof(T) == 1) {
+            decimate_rows_int(v, nchans, f, nz, z.data());
+        } else {
+            decimate_rows_f32(v, nchans, f, nz, (const float*)nullptr, z.data());
+        }
+    });
+    dedisperse_rows(z.data(), nchans, delays, mask, ndm, nout, out, Bands{});   // float32, in channel order
+}
+
+// ---- the DM plan (riptide_amd.h, rt_dm_plan)
+bool positive(double v) { return v > 0.0 && std::isfinite(v); }
+
+struct DmPlanner {
+    double kdisp, ksmear, wmin, step;   // step: tsamp * oversample
+    uint32_t max_downsamp;
+    double smear(double dm) const { return std::max(wmin, ksmear * dm); }
+    double radius(double dm) const { return smear(dm) / kdisp; }
+    double next(double dm) const
+    {
+        const double e = dm + radius(dm);
+        const double flat = e + wmin / kdisp;
+        return ksmear * flat > wmin ? e / (1.0 - ksmear / kdisp) : flat;
+    }
+    uint32_t downsamp(double dm) const
+    {
+        uint32_t f = 1;
+        while (2 * f <= max_downsamp && (double)(2 * f) * step <= smear(dm)) f *= 2;
+        return f;
+    }
+};
+
+DmPlanner dm_planner(const double* freqs, size_t nchans, double tsamp, double dm_min, double dm_max, double wmin,
+                     double oversample, uint32_t max_downsamp, double kdm)
+{
+    if (nchans < 2) throw std::invalid_argument("dm_plan: at least 2 channels are needed");
+    if (!freqs) throw std::invalid_argument("dm_plan: freqs is NULL");
+    double fmin = freqs[0], fmax = freqs[0];
+    for (size_t c = 0; c < nchans; ++c) {
+        if (!positive(freqs[c]))
+            throw std::invalid_argument("dm_plan: channel frequencies must be positive and finite");
+        fmin = std::min(fmin, freqs[c]);
+        fmax = std::max(fmax, freqs[c]);
+    }
+    if (!positive(tsamp)) throw std::invalid_argument("dm_plan: tsamp must be positive and finite");
+    if (!positive(wmin)) throw std::invalid_argument("dm_plan: wmin must be positive and finite");
+    if (!positive(oversample)) throw std::invalid_argument("dm_plan: oversample must be positive and finite");
+    if (!positive(kdm)) throw std::invalid_argument("dm_plan: kdm must be positive and finite");
+    if (!(dm_min >= 0.0) || !std::isfinite(dm_min))
+        throw std::invalid_argument("dm_plan: dm_min must be non-negative and finite");
+    if (!(dm_max >= dm_min) || !std::isfinite(dm_max))
+        throw std::invalid_argument("dm_plan: dm_max must be finite and at least dm_min");
+    if (max_downsamp < 1 || max_downsamp > RT_DEDISP_MAX_DOWNSAMP)
+        throw std::invalid_argument("dm_plan: max_downsamp must be in [1, " +
+                                    std::to_string(RT_DEDISP_MAX_DOWNSAMP) + "]");
+    const double cw = (fmax - fmin) / (double)(nchans - 1);
+    const double flo = fmin - cw / 2.0, fhi = fmax + cw / 2.0;
+    if (!positive(cw) || !positive(flo))
+        throw std::invalid_argument("dm_plan: the channels must span a band above 0 MHz");
+    const double fmid = (flo + fhi) / 2.0;
+    const double a = fmid - cw / 2.0, b = fmid + cw / 2.0;
+    DmPlanner p;
+    p.kdisp = kdm * (1.0 / (flo * flo) - 1.0 / (fhi * fhi));
+    p.ksmear = kdm * (1.0 / (a * a) - 1.0 / (b * b));
+    p.wmin = wmin;
+    p.step = tsamp * oversample;
+    p.max_downsamp = max_downsamp;
+    if (!positive(p.kdisp) || !positive(p.ksmear) || !(p.ksmear < p.kdisp))
+        throw std::invalid_argument("dm_plan: the band gives no usable dispersion sweep");
+    return p;
+}
+
 }  // namespace
 
 extern "C" {
+
+int rt_dm_plan(const double* freqs_mhz, size_t nchans, double tsamp, double dm_min, double dm_max, double wmin,
+               double oversample, uint32_t max_downsamp, double kdm, double* dms, uint32_t* downsamp,
+               size_t capacity, size_t* ntrials)
+{
+    return guarded([&] {
+        if (!ntrials) throw std::invalid_argument("dm_plan: ntrials is NULL");
+        if (!dms != !downsamp) throw std::invalid_argument("dm_plan: dms and downsamp go together");
+        const DmPlanner p = dm_planner(freqs_mhz, nchans, tsamp, dm_min, dm_max, wmin, oversample, max_downsamp, kdm);
+        size_t n = 0;
+        for (double dm = dm_min;; dm = p.next(dm)) {
+            if (n >= RT_DM_PLAN_MAX_TRIALS)
+                throw std::invalid_argument("dm_plan: more than 2^20 trials: raise wmin or lower dm_max");
+            if (dms) {
+                if (n >= capacity) throw std::invalid_argument("dm_plan: capacity is below the number of trials");
+                dms[n] = dm;
+                downsamp[n] = p.downsamp(dm);
+            }
+            ++n;
+            if (dm + p.radius(dm) >= dm_max) break;
+        }
+        *ntrials = n;
+        return RT_OK;
+    });
+}
+
+int rt_dedisperse_ds_host(const void* x, int dtype, size_t nsamp, size_t nchans, const int64_t* delays,
+                          const uint8_t* mask, size_t ndm, int64_t max_delay, size_t downsamp, size_t nout,
+                          float* out, uint32_t flags, const rt_block_mask* bm)
+{
+    return guarded([&] {
+        dedisperse_ds_host(x, dtype, nsamp, nchans, delays, mask, ndm, max_delay, downsamp, nout, out, flags, bm);
+        return RT_OK;
+    });
+}
+
+int rt_dedisperse_steps_check(int dtype, size_t nsamp_blk, size_t nchans, const rt_dedisp_step* steps,
+                              size_t nsteps, size_t delays_len, size_t out_floats, uint32_t flags,
+                              const rt_block_mask* bm)
+{
+    return guarded([&] {
+        dedisp_check_steps(dtype, nsamp_blk, nchans, steps, nsteps, delays_len, out_floats, flags, bm);
+        return RT_OK;
+    });
+}
 
 int rt_dedisp_row_bytes(int dtype, size_t nchans, size_t* bytes)
 {

@@ -23,6 +23,10 @@
 //                             of one band of a table, a grid layer per band:
 //                             out[d, b, t], every band of a batch of DMs from
 //                             one pass over the transposed block
+//   dedisp_decimate_kernel    a step of a DM plan (launch_dedisperse_steps): the
+//                             transposed rows summed f samples at a time into
+//                             float32 rows, which dedisp_sum_kernel<float> then
+//                             sums with the step's delays
 //   dedisp_rowmean_kernel     zero-DM filter (RT_DEDISP_ZERO_DM): m[t], the mean
 //                             of time sample t over the unmasked channels, one
 //                             wave per sample
@@ -759,6 +763,109 @@ __global__ __launch_bounds__(kDdThreads) void dedisp_sum_kernel(
     }
 }
 
+// ---- time decimation of the transposed rows (launch_dedisperse_steps)
+// z[c, u] = sum over i < f of row_c[f u + i] for u < nz = floor(nsamp_blk / f),
+// float32 rows of pitch zpitch (a multiple of 4 floats); [nz, zpitch) is
+// written as zero.  T = uint8_t: 8-bit rows, summed in int32, the bias removed
+// (bias * f) and converted once.  T = float: float32 additions from 0.0f in
+// index order.  Reading the transposed rows, it needs no form per packed type,
+// block mask or zero-DM filter: those stay in the transposes.
+// A workgroup takes 256 outputs of one channel, a wave 64 of them: the 64 f
+// contiguous elements from element 64 f (u0 / 64) of the row, a stretch that
+// starts on a 64-byte boundary.  When an output's f elements are 4, 8 or a
+// multiple of 16 bytes, lane l loads its own chunk with dword, 2-dword or
+// 4-dword loads (aligned: the row pitch is a multiple of 16 bytes) -- at 4, 8
+// and 16 bytes one instruction of the wave covers the whole stretch.  Any
+// other f goes through LDS: the wave loads the stretch with coalesced dword
+// loads, kDcStageDw dwords at a time, and every lane adds the elements of its
+// chunk that lie in the piece, so no lane issues f byte loads.
+// No load leaves the row's padded pitch: a chunk is loaded only for u < nz
+// (f u + f <= nsamp_blk <= pitch) and the staged dwords are clamped to the
+// pitch; no store goes past zpitch.
+// kStaged is the launcher's choice by f (dc_staged): the staged form alone
+// holds the 16 KiB of LDS, the vector-load form none.
+constexpr uint32_t kDcTile = 256;        // outputs of a workgroup
+constexpr uint32_t kDcStageDw = 1024;    // dwords of a wave's staged piece
+
+template <class T, class Acc>
+__device__ inline void dc_add_dword(Acc& acc, uint32_t v)
+{
+    if constexpr (sizeof(T) == 1) acc += (Acc)((v & 0xFFu) + ((v >> 8) & 0xFFu) + ((v >> 16) & 0xFFu) + (v >> 24));
+    else acc += __uint_as_float(v);
+}
+
+// whether a chunk of cb bytes goes through LDS: not 4, 8 or a multiple of 16 bytes
+constexpr bool dc_staged(uint32_t cb) { return cb % 16 != 0 && cb != 8 && cb != 4; }
+
+template <class T, bool kStaged>
+__global__ __launch_bounds__(kDdThreads) void dedisp_decimate_kernel(
+    const T* __restrict__ ws, uint64_t pitch, uint32_t nchans, uint32_t f, uint32_t nz, float* __restrict__ z,
+    uint64_t zpitch, int32_t bias)
+{
+    constexpr bool kBytes = sizeof(T) == 1;
+    constexpr uint32_t kE = 4 / sizeof(T);   // elements per dword
+    using Acc = typename std::conditional<kBytes, int32_t, float>::type;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t u0 = blockIdx.x * kDcTile + wave * 64;   // the wave's first output
+    const uint32_t u = u0 + lane;
+    const uint32_t cb = f * (uint32_t)sizeof(T);            // bytes of an output's chunk
+    [[maybe_unused]] const uint64_t row_dw = pitch / kE;
+    for (uint32_t c = blockIdx.y; c < nchans; c += gridDim.y) {
+        const T* row = ws + (uint64_t)c * pitch;
+        Acc acc = 0;
+        if constexpr (kStaged) {
+            __shared__ __attribute__((aligned(16))) uint32_t stage[kDdWaves][kDcStageDw];
+            const uint32_t* rdw = reinterpret_cast<const uint32_t*>(row);
+            const uint64_t w0 = (uint64_t)u0 * cb / 4;    // u0 is a multiple of 64: a whole dword
+            const uint32_t ndw = 16 * cb;                 // dwords of the wave's stretch, 64 cb / 4
+            const uint32_t e_lo = lane * f, e_hi = e_lo + f;   // the lane's elements of the stretch
+            for (uint32_t p0 = 0; p0 < ndw; p0 += kDcStageDw) {
+                __syncthreads();   // the previous piece is consumed
+                const uint32_t n = min(kDcStageDw, ndw - p0);
+                for (uint32_t i = lane; i < n; i += 64) {
+                    const uint64_t w = w0 + p0 + i;
+                    stage[wave][i] = w < row_dw ? rdw[w] : 0u;
+                }
+                __syncthreads();
+                const uint32_t s0 = p0 * kE;   // first element of the piece
+                const uint32_t lo = max(e_lo, s0), hi = min(e_hi, s0 + n * kE);
+                for (uint32_t e = lo; e < hi; ++e) {
+                    if constexpr (kBytes) acc += (Acc) reinterpret_cast<const uint8_t*>(stage[wave])[e - s0];
+                    else acc += __uint_as_float(stage[wave][e - s0]);
+                }
+            }
+        } else if (cb % 16 == 0) {   // the same in every workgroup
+            if (u < nz) {
+                const uint4* p = reinterpret_cast<const uint4*>(row + (uint64_t)u * f);
+                for (uint32_t k = 0; k < cb / 16; ++k) {
+                    const uint4 v = p[k];
+                    dc_add_dword<T>(acc, v.x);
+                    dc_add_dword<T>(acc, v.y);
+                    dc_add_dword<T>(acc, v.z);
+                    dc_add_dword<T>(acc, v.w);
+                }
+            }
+        } else if (cb == 8) {
+            if (u < nz) {
+                const uint2 v = *reinterpret_cast<const uint2*>(row + (uint64_t)u * f);
+                dc_add_dword<T>(acc, v.x);
+                dc_add_dword<T>(acc, v.y);
+            }
+        } else {   // cb == 4
+            if (u < nz) dc_add_dword<T>(acc, *reinterpret_cast<const uint32_t*>(row + (uint64_t)u * f));
+        }
+        if (u < zpitch) {
+            float v = 0.0f;
+            if (u < nz) {
+                if constexpr (kBytes) v = (float)(acc - bias * (int32_t)f);
+                else v = acc;
+            }
+            z[(uint64_t)c * zpitch + u] = v;
+        }
+    }
+}
+
 // the sum over the transposed rows: the plain instantiation, or with a band
 // table the band one on a grid with a z layer per band
 template <class T>
@@ -968,6 +1075,63 @@ hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, u
     else
         launch_sum(sum_grid, s, (const uint8_t*)ws, pitch_bytes, nchans, d_delays, d_mask, ndm, max_delay, nout, out,
                    out_stride, dtype == RT_DEDISP_I8 ? 128 : 0, d_bands, nbands);
+    return hipGetLastError();
+}
+
+uint64_t dedisp_steps_workspace_bytes(int dtype, uint64_t nsamp_blk, uint64_t nchans, uint32_t flags,
+                                      uint32_t min_factor)
+{
+    const uint64_t rows = dedisp_workspace_bytes(dtype, nsamp_blk, nchans, flags);   // a multiple of 16
+    if (!min_factor) return rows;
+    return rows + dedisp_pitch_bytes(RT_DEDISP_F32, nsamp_blk / min_factor) * nchans;
+}
+
+// The rows once, then step after step in stream order: a step of downsamp 1
+// is launch_dedisperse's sum of those rows; any other decimates them into the
+// float32 area behind them, which the step before has finished reading, and
+// runs the float32 sum over that area with the step's own pitch.
+hipError_t launch_dedisperse_steps(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
+                                   const int32_t* d_delays, const uint8_t* d_mask, const rt_dedisp_step* steps,
+                                   size_t nsteps, float* out, void* ws, uint32_t flags, hipStream_t s,
+                                   const DedispCells* bm)
+{
+    const bool float_rows = dedisp_float_rows(dtype, flags);
+    const uint64_t pitch_bytes = dedisp_pitch_bytes(float_rows ? RT_DEDISP_F32 : dtype, nsamp_blk);
+    const int32_t bias = !float_rows && dtype == RT_DEDISP_I8 ? 128 : 0;
+    float* z = reinterpret_cast<float*>(static_cast<uint8_t*>(ws) + dedisp_workspace_bytes(dtype, nsamp_blk, nchans, flags));
+    const hipError_t e = launch_dedisp_rows(block, dtype, nsamp_blk, nchans, d_mask, ws, flags, s, bm);
+    if (e != hipSuccess) return e;
+    for (size_t k = 0; k < nsteps; ++k) {
+        const rt_dedisp_step& st = steps[k];
+        const int32_t* delays = d_delays + st.delays_off;
+        float* o = out + st.out_off + st.out_offset;
+        const uint32_t f = st.downsamp, nz = nsamp_blk / f, nout = nz - st.max_delay;
+        const dim3 sum_grid((nout + kDdTile - 1) / kDdTile, (st.ndm + kDdDms - 1) / kDdDms);
+        if (f == 1) {
+            if (float_rows)
+                launch_sum(sum_grid, s, (const float*)ws, pitch_bytes / 4, nchans, delays, d_mask, st.ndm,
+                           st.max_delay, nout, o, st.out_stride, 0, nullptr, 0);
+            else
+                launch_sum(sum_grid, s, (const uint8_t*)ws, pitch_bytes, nchans, delays, d_mask, st.ndm, st.max_delay,
+                           nout, o, st.out_stride, bias, nullptr, 0);
+            continue;
+        }
+        const uint64_t zpitch = dedisp_pitch_bytes(RT_DEDISP_F32, nz) / 4;
+        const dim3 grid((uint32_t)((zpitch + kDcTile - 1) / kDcTile), nchans < 65535u ? nchans : 65535u);
+        const auto decimate = [&](auto staged) {
+            constexpr bool kStaged = decltype(staged)::value;
+            if (float_rows)
+                hipLaunchKernelGGL((dedisp_decimate_kernel<float, kStaged>), grid, dim3(kDdThreads), 0, s,
+                                   (const float*)ws, pitch_bytes / 4, nchans, f, nz, z, zpitch, 0);
+            else
+                hipLaunchKernelGGL((dedisp_decimate_kernel<uint8_t, kStaged>), grid, dim3(kDdThreads), 0, s,
+                                   (const uint8_t*)ws, pitch_bytes, nchans, f, nz, z, zpitch, bias);
+        };
+        if (dc_staged(f * (float_rows ? 4u : 1u))) decimate(std::true_type{});
+        else decimate(std::false_type{});
+        launch_sum(sum_grid, s, (const float*)z, zpitch, nchans, delays, d_mask, st.ndm, st.max_delay, nout, o,
+                   st.out_stride, 0, nullptr, 0);
+    }
     return hipGetLastError();
 }
 

@@ -148,4 +148,84 @@ inline void dedisp_check_block_mask(const rt_block_mask* bm, size_t nsamp)
                                     std::to_string(bm->block_len) + " samples");
 }
 
+// the shape limits of a resident-block call: the kernels' 32-bit indices and grids
+inline void dedisp_check_shape(int dtype, size_t nsamp_blk, size_t nchans, size_t ndm, int64_t max_delay)
+{
+    if (!dedisp_known_dtype(dtype)) throw std::invalid_argument("dedisperse: unknown sample type code");
+    if (!nchans || !ndm) throw std::invalid_argument("dedisperse: nchans and ndm must be at least 1");
+    dedisp_check_chan_cap(dtype, nchans);
+    if (nchans > 65535ull * 64) throw std::invalid_argument("dedisperse: too many channels");
+    if (ndm > 65535ull * 16) throw std::invalid_argument("dedisperse: too many DMs for one call");
+    if (nsamp_blk >= (1ull << 31)) throw std::invalid_argument("dedisperse: a block must be below 2^31 samples");
+    // packed rows: whole bytes, and nsamp_blk * row_bytes inside the kernels' 64-bit byte offsets
+    // (row_bytes < 2^23 by the channel limit above)
+    if (dedisp_packed_bits(dtype) && dedisp_row_bytes(dtype, nchans) > (~0ull >> 1) / (nsamp_blk ? nsamp_blk : 1))
+        throw std::invalid_argument("dedisperse: the block's bytes overflow a 64-bit offset");
+    if (max_delay < 0 || (uint64_t)max_delay >= nsamp_blk)
+        throw std::invalid_argument("dedisperse: max_delay must be in [0, nsamp): the block is no longer than the "
+                                    "largest delay");
+}
+
+// ---- decimated steps (riptide_amd.h: rt_dedisperse_ds_host, rt_dedisp_step)
+inline void dedisp_check_downsamp(uint64_t f)
+{
+    if (f < 1 || f > RT_DEDISP_MAX_DOWNSAMP)
+        throw std::invalid_argument("dedisperse: downsamp " + std::to_string(f) + " is outside [1, " +
+                                    std::to_string(RT_DEDISP_MAX_DOWNSAMP) + "]");
+}
+
+// the exactness cap of a step of factor f: integer sums stay below 2^24
+inline void dedisp_check_ds_cap(int dtype, size_t nchans, uint64_t f, uint32_t flags)
+{
+    if (!dedisp_integer_sum(dtype) || (flags & RT_DEDISP_ZERO_DM)) return;
+    const int nbits = dedisp_packed_bits(dtype);
+    const uint64_t vmax = nbits ? (1ull << nbits) - 1 : 255;
+    if (vmax * f * nchans >= (1ull << 24))   // f <= 256, nchans < 2^23: no overflow
+        throw std::invalid_argument("dedisperse: " + std::to_string(nchans) + " channels at downsamp " +
+                                    std::to_string(f) + " are too many for an exact sum (" + std::to_string(vmax) +
+                                    " * downsamp * nchans must be below 2^24)");
+}
+
+// a block mask in front of decimated steps: every gulp starts on a decimated sample
+inline void dedisp_check_mask_origin(const rt_block_mask* bm, uint64_t f)
+{
+    if (bm && bm->t_origin % f)
+        throw std::invalid_argument("block_mask: t_origin " + std::to_string(bm->t_origin) +
+                                    " is not a multiple of downsamp " + std::to_string(f));
+}
+
+// a step table in host memory over a block of nsamp_blk rows (rt_dedisperse_steps_check)
+inline void dedisp_check_steps(int dtype, size_t nsamp_blk, size_t nchans, const rt_dedisp_step* steps,
+                               size_t nsteps, size_t delays_len, size_t out_floats, uint32_t flags,
+                               const rt_block_mask* bm)
+{
+    dedisp_check_flags(flags);
+    dedisp_check_shape(dtype, nsamp_blk, nchans, 1, 0);
+    dedisp_check_block_mask(bm, nsamp_blk);
+    if (!steps || !nsteps) throw std::invalid_argument("dedisperse: a step table needs at least one step");
+    for (size_t k = 0; k < nsteps; ++k) {
+        const rt_dedisp_step& st = steps[k];
+        const std::string who = "dedisperse: step " + std::to_string(k) + ": ";
+        dedisp_check_downsamp(st.downsamp);
+        if (st.reserved) throw std::invalid_argument(who + "reserved must be 0");
+        if (!st.ndm) throw std::invalid_argument(who + "ndm must be at least 1");
+        if (st.ndm > 65535ull * 16) throw std::invalid_argument("dedisperse: too many DMs for one call");
+        const uint64_t nz = nsamp_blk / st.downsamp;
+        if (st.max_delay >= nz)
+            throw std::invalid_argument(who + "max_delay " + std::to_string(st.max_delay) + " is not below the " +
+                                        std::to_string(nz) + " decimated samples of the block");
+        dedisp_check_mask_origin(bm, st.downsamp);
+        dedisp_check_ds_cap(dtype, nchans, st.downsamp, flags);
+        const uint64_t nout = nz - st.max_delay;
+        if (st.delays_off > delays_len || (uint64_t)st.ndm * nchans > delays_len - st.delays_off)
+            throw std::invalid_argument(who + "its delay table leaves the delay array");
+        if (st.out_offset > st.out_stride || nout > st.out_stride - st.out_offset)
+            throw std::invalid_argument(who + "out_stride is shorter than out_offset plus the step's outputs");
+        // the last float written: out_off + (ndm - 1) * out_stride + out_offset + nout - 1
+        const unsigned __int128 end = (unsigned __int128)st.out_off +
+                                      (unsigned __int128)(st.ndm - 1) * st.out_stride + st.out_offset + nout;
+        if (end > out_floats) throw std::invalid_argument(who + "its output rows leave the output array");
+    }
+}
+
 }  // namespace rt

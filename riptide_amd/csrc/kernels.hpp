@@ -131,6 +131,22 @@ hipError_t launch_dedisperse(const void* block, int dtype, uint32_t nsamp_blk, u
 hipError_t launch_dedisp_rows(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
                               const uint8_t* d_mask, void* ws, uint32_t flags, hipStream_t s,
                               const DedispCells* bm = nullptr);
+// dedisp_workspace_bytes for a step table: those rows, then for min_factor, the
+// smallest downsamp > 1 of the call (0: none), one float32 area of nchans rows
+// of nsamp_blk / min_factor samples at dedisp_pitch_bytes(RT_DEDISP_F32, .),
+// which every decimated step reuses in stream order
+uint64_t dedisp_steps_workspace_bytes(int dtype, uint64_t nsamp_blk, uint64_t nchans, uint32_t flags,
+                                      uint32_t min_factor);
+// Every step of a table (host memory, checked by the caller: dedisp_check_steps)
+// from one launch_dedisp_rows: a step of downsamp 1 is launch_dedisperse's sum;
+// any other decimates the rows into the float32 area (dedisp_decimate_kernel,
+// the padding of its pitch written as zero) and runs the float32 sum over it.
+// Step k writes out[out_off + d * out_stride + out_offset + u], u < nsamp_blk /
+// downsamp - max_delay, with the delays from d_delays + delays_off.
+hipError_t launch_dedisperse_steps(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
+                                   const int32_t* d_delays, const uint8_t* d_mask, const rt_dedisp_step* steps,
+                                   size_t nsteps, float* out, void* ws, uint32_t flags, hipStream_t s,
+                                   const DedispCells* bm = nullptr);
 // m[t] = (float32)(sum over unmasked c of block[t, c] / their number), t < nsamp_blk
 hipError_t launch_zero_dm_mean(const void* block, int dtype, uint32_t nsamp_blk, uint32_t nchans,
                                const uint8_t* d_mask, float* m, hipStream_t s, const DedispCells* bm = nullptr);

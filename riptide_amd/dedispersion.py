@@ -24,6 +24,7 @@ and y is summed in float32 for every sample type (RT_DEDISP_ZERO_DM in
 include/riptide_amd.h; rfi.py for the mean series and channel statistics).
 """
 import ctypes
+import typing
 
 import numpy as np
 
@@ -451,3 +452,359 @@ def band_series(fb, dms, bands, deredden_params, nout, mask=None, zero_dm=False,
             idx = torch.from_numpy(keep).to(raw.device)
             out[idx] = engine.deredden_normalise(rows[idx], width, minpts)
     return out.view(ndm, nbands, nout), empty
+
+
+# ---------------------------------------------------------------- the DM plan
+MAX_DOWNSAMP = 256    # RT_DEDISP_MAX_DOWNSAMP: the largest factor of a step
+
+
+class DMStep(typing.NamedTuple):
+    """Consecutive trials of a plan that share one decimation factor."""
+    dms: np.ndarray       # float64, ascending as planned
+    downsamp: int         # f: samples summed per output sample
+    tsamp: float          # f * the file's sampling time, seconds (None when built by hand without one)
+
+
+class DMPlan:
+    """Which DMs to search and at what time resolution: `steps` (DMStep), the
+    flat `dms` in plan order, the per-trial `downsamp` array, len() = the
+    number of trials.  `dm_cover`, the largest DM of the plan this one was cut
+    from (shard keeps it), fixes the stretch of the observation every step
+    covers, so a sharded plan gives the series of the whole plan.
+
+    dm_plan makes one from a band; DMPlan.from_steps([(dms, downsamp), ...])
+    builds one by hand, with any integer downsamp in [1, 256] (dm_plan itself
+    only gives powers of two)."""
+
+    def __init__(self, steps, tsamp=None, dm_cover=None):
+        self.tsamp = None if tsamp is None else float(tsamp)
+        self.steps = []
+        for dms, f in steps:
+            dms = np.ascontiguousarray(np.atleast_1d(dms), dtype=np.float64)
+            if int(f) != f or not 1 <= int(f) <= MAX_DOWNSAMP:
+                raise ValueError(f"downsamp {f} must be an integer in [1, {MAX_DOWNSAMP}]")
+            if dms.ndim != 1 or not np.all(np.isfinite(dms)) or np.any(dms < 0):
+                raise ValueError("the DMs of a step must be a one-dimensional list of non-negative finite numbers")
+            if dms.size:
+                self.steps.append(DMStep(dms, int(f), None if tsamp is None else int(f) * self.tsamp))
+        largest = max((float(s.dms.max()) for s in self.steps), default=0.0)
+        self.dm_cover = largest if dm_cover is None else float(dm_cover)
+        if self.dm_cover < largest:
+            raise ValueError("dm_cover is below the plan's largest DM")
+
+    @classmethod
+    def from_steps(cls, steps, tsamp=None):
+        return cls(steps, tsamp)
+
+    @property
+    def dms(self):
+        return np.concatenate([s.dms for s in self.steps]) if self.steps else np.empty(0, dtype=np.float64)
+
+    @property
+    def downsamp(self):
+        return (np.concatenate([np.full(s.dms.size, s.downsamp, dtype=np.int64) for s in self.steps])
+                if self.steps else np.empty(0, dtype=np.int64))
+
+    def __len__(self):
+        return sum(s.dms.size for s in self.steps)
+
+    def shard(self, rank, size):
+        """The round-robin share of every step (trials rank, rank + size, ...
+        of each), empty steps dropped; dm_cover is kept."""
+        rank, size = int(rank), int(size)
+        if not 0 <= rank < size:
+            raise ValueError("rank must be in [0, size)")
+        return DMPlan([(s.dms[rank::size], s.downsamp) for s in self.steps], self.tsamp, self.dm_cover)
+
+    def shard_indices(self, rank, size):
+        """Indices into the flat `dms` of the trials shard(rank, size) keeps, in its order."""
+        idx, first = [], 0
+        for s in self.steps:
+            idx.extend(range(first + int(rank), first + s.dms.size, int(size)))
+            first += s.dms.size
+        return idx
+
+    def __repr__(self):
+        return "DMPlan(" + ", ".join(f"{s.dms.size} x f={s.downsamp}" for s in self.steps) + ")"
+
+
+def dm_plan(freqs, tsamp, dm_max, dm_min=0.0, wmin=1.0e-3, oversample=2.0, max_downsamp=64, kdm=KDM):
+    """The DM trials of a band and each one's time decimation (rt_dm_plan; host
+    only, float64): a DMPlan.
+
+    freqs are the channel centre frequencies in MHz (ascending or descending,
+    at least 2).  With cw the channel width, flo / fhi the band edges and fmid
+    the band centre, kdisp = kdm (flo^-2 - fhi^-2), ksmear = kdm ((fmid -
+    cw/2)^-2 - (fmid + cw/2)^-2), the smearing of a trial is s(DM) = max(wmin,
+    ksmear DM) and its coverage radius r(DM) = s(DM) / kdisp -- the quantities
+    of the reference's dmiter.select_dms, which thins an existing set of
+    trials by the same rule.  The first trial is dm_min; each next trial is
+    the DM whose radius touches the previous one's; the last is the first
+    whose radius reaches dm_max.  A trial's decimation f is the largest power
+    of two <= max_downsamp with f * tsamp * oversample <= s(DM), at least 1;
+    consecutive trials of equal f form a DMStep.
+
+    wmin (seconds) is the narrowest pulse searched for.  oversample = 2.0
+    (decimated samples across the smearing time) and max_downsamp = 64 are
+    interface defaults, not tuned values: nothing was measured to choose them.
+
+    Out of scope: factors that are not powers of two (DMPlan.from_steps and
+    the kernels take them).  ValueError for fewer than 2 channels, inputs that
+    are not positive and finite (dm_min may be 0), dm_max < dm_min, and more
+    than 2^20 trials."""
+    freqs = np.ascontiguousarray(np.atleast_1d(freqs), dtype=np.float64)
+    if freqs.ndim != 1:
+        raise ValueError("freqs must be one-dimensional")
+    if int(max_downsamp) != max_downsamp or not 1 <= int(max_downsamp) <= MAX_DOWNSAMP:
+        raise ValueError(f"max_downsamp must be an integer in [1, {MAX_DOWNSAMP}]")
+    args = (_lib.ptr(freqs), freqs.size, float(tsamp), float(dm_min), float(dm_max), float(wmin), float(oversample),
+            int(max_downsamp), float(kdm))
+    n = ctypes.c_size_t(0)
+    _check(_L.rt_dm_plan(*args, None, None, 0, ctypes.byref(n)))
+    dms = np.zeros(n.value, dtype=np.float64)
+    f = np.zeros(n.value, dtype=np.uint32)
+    _check(_L.rt_dm_plan(*args, _lib.ptr(dms), _lib.ptr(f), n.value, ctypes.byref(n)))
+    cuts = np.flatnonzero(np.diff(f.astype(np.int64))) + 1
+    return DMPlan([(part, int(ff[0])) for part, ff in zip(np.split(dms, cuts), np.split(f, cuts))], tsamp)
+
+
+def dedisperse_ds_host(data, delays, max_delay, downsamp, mask=None, nout=None, zero_dm=False, nbits=None,
+                       block_mask=None, t_origin=0):
+    """The specification of a decimated step on the host
+    (rt_dedisperse_ds_host, no device): float32 [ndm, nout],
+
+      z[u, c]   = sum over i < f of x'[f * u + i, c]            u < nsamp // f
+      out[d, u] = sum over unmasked c of z[u + delays[d, c], c]
+
+    both sums float32 additions from 0.0f in index order (8-bit and 1/2/4-bit
+    data without zero_dm: exact integers; refused when vmax * f * nchans >=
+    2^24).  delays are in decimated samples (dispersion_delays at tsamp * f);
+    nout defaults to nsamp // f - max_delay.  block_mask: a (cells uint8
+    [nblocks, nchans], fill, block_len) triple in host memory, with t_origin a
+    multiple of f.  downsamp = 1 is dedisperse_host."""
+    data, code, nsamp, nchans = _host_block(data, nbits)
+    delays = np.ascontiguousarray(delays, dtype=np.int64)
+    if delays.ndim != 2 or delays.shape[1] != nchans:
+        raise ValueError("delays must be [ndm, nchans]")
+    mask = _checked_mask(mask, nchans)
+    f = int(downsamp)
+    if not 1 <= f <= MAX_DOWNSAMP:
+        raise ValueError(f"dedisperse: downsamp {f} is outside [1, {MAX_DOWNSAMP}]")
+    nout = nsamp // f - int(max_delay) if nout is None else int(nout)
+    if nout < 0:
+        raise ValueError(f"max_delay {max_delay} exceeds the {nsamp // f} decimated samples of the input")
+    bm = None
+    if block_mask is not None:
+        cells, fill, block_len = block_mask
+        cells = np.ascontiguousarray(cells, dtype=np.uint8)
+        fill = np.ascontiguousarray(fill)
+        bm = _lib.BlockMaskStruct(cells.ctypes.data, cells.shape[0], int(block_len), int(t_origin), fill.ctypes.data)
+    out = np.zeros((delays.shape[0], nout), dtype=np.float32)
+    _check(_L.rt_dedisperse_ds_host(_lib.ptr(data), code, nsamp, nchans, _lib.ptr(delays),
+                                    None if mask is None else _lib.ptr(mask), delays.shape[0], int(max_delay), f, nout,
+                                    _lib.ptr(out), DEDISP_ZERO_DM if zero_dm else 0,
+                                    None if bm is None else ctypes.byref(bm)))
+    return out
+
+
+def dedisperse_steps(data, delays, steps, out, mask=None, zero_dm=False, nbits=None):
+    """The steps of a step table from host data on the GPU (rt_dedisperse_steps:
+    upload, the kernels of engine.dedisperse_steps_device, download;
+    synchronous), as dedisperse is for one delay table.  data as for
+    dedisperse; delays int64 [rows, nchans] holding every step's table, each
+    entry in [0, its step's max_delay]; steps engine.DEDISP_STEP_DTYPE records
+    (delays_off in elements of delays, out_off in floats of out); out a
+    contiguous one-dimensional float32 array, which is uploaded first, so a
+    float no step writes comes back as it was.  Returns the [ndm, nout] views
+    of out, one per step.  No block mask."""
+    from . import engine
+    data, code, nsamp, nchans = _host_block(data, nbits)
+    delays = np.ascontiguousarray(delays, dtype=np.int64)
+    if delays.ndim != 2 or delays.shape[1] != nchans:
+        raise ValueError("delays must be [rows, nchans]")
+    steps = engine.checked_dedisp_steps(steps)
+    if not isinstance(out, np.ndarray) or out.dtype != np.float32 or out.ndim != 1 or not out.flags.c_contiguous:
+        raise ValueError("out must be a contiguous one-dimensional float32 array")
+    mask = _checked_mask(mask, nchans)
+    _check(_L.rt_dedisperse_steps(_lib.ptr(data), code, nsamp, nchans, _lib.ptr(delays), delays.size,
+                                  None if mask is None else _lib.ptr(mask), _lib.ptr(steps) if steps.size else None,
+                                  steps.size, _lib.ptr(out), out.size, DEDISP_ZERO_DM if zero_dm else 0))
+    return [np.lib.stride_tricks.as_strided(
+        out[int(s["out_off"]) + int(s["out_offset"]):],
+        (int(s["ndm"]), nsamp // int(s["downsamp"]) - int(s["max_delay"])), (int(s["out_stride"]) * 4, 4))
+        for s in steps]
+
+
+def plan_layout(fb, plan, kdm=KDM):
+    """Where dedisperse_filterbank_plan puts the steps of `plan` for file `fb`
+    (host only): a list, one entry per step, of (delays int64 [ndm, nchans] in
+    decimated samples, max_delay, nout).  With D the largest delay at the
+    file's own sampling time of plan.dm_cover and L = nsamp - D, nout = min(L
+    // f, nsamp // f - max_delay): every step covers the same stretch of the
+    observation, whatever share of the plan it is.  ValueError when a step
+    leaves no output, and when the plan was made for another sampling time
+    than the file's (plan.tsamp, where it is set): its factors were chosen
+    against that one."""
+    if plan.tsamp is not None and abs(plan.tsamp - fb.tsamp) > 1e-9 * fb.tsamp:
+        raise ValueError(f"the plan was made for a sampling time of {plan.tsamp} s, the file has {fb.tsamp} s")
+    _, D = dispersion_delays(fb.freqs, [plan.dm_cover], fb.tsamp, kdm)
+    check_max_delay(D, fb.nsamp)
+    L = fb.nsamp - D
+    layout = []
+    for s in plan.steps:
+        delays, md = dispersion_delays(fb.freqs, s.dms, fb.tsamp * s.downsamp, kdm)
+        nout = min(L // s.downsamp, fb.nsamp // s.downsamp - md)
+        if nout < 1:
+            raise ValueError(f"the step at downsamp {s.downsamp} leaves no output: the largest delay ({md} decimated "
+                             f"samples) is not below the {fb.nsamp // s.downsamp} decimated samples of the file")
+        layout.append((delays, md, nout))
+    return layout
+
+
+def _plan_setup(fb, plan, gulp, kdm, zero_dm, block_mask):
+    """What dedisperse_filterbank_plan works out on the host before anything is
+    allocated, as a dict: the layout, the gulp and its overlap, the step table
+    of the first gulp (checked), and the device bytes of the call."""
+    import math
+    from . import engine
+    nchans = fb.nchans
+    nbits = _checked_sample_type(fb)
+    row_elems, dtype = _gulp_layout(fb)
+    layout = plan_layout(fb, plan, kdm)
+    factors = [s.downsamp for s in plan.steps]
+    lcm = 1
+    for f in factors:
+        lcm = lcm * f // math.gcd(lcm, f)
+    # rows the outputs read, a whole number of every step's decimated samples
+    need_in = max((nout + md) * f for (_, md, nout), f in zip(layout, factors))
+    overlap = -(-max(md * f for (_, md, _), f in zip(layout, factors)) // lcm) * lcm
+    row_bytes = row_elems * dtype.itemsize
+    if gulp is None:
+        gulp = max(DEFAULT_GULP_BYTES // row_bytes, 2 * overlap + lcm)
+    gulp = int(gulp) // lcm * lcm
+    if gulp <= overlap:
+        raise ValueError(f"gulp must be a multiple of {lcm} above the overlap of {overlap} samples")
+    if gulp >= need_in:
+        gulp = need_in          # one gulp: it may end inside a decimated sample, whose tail is dropped
+    name = engine._dedisp_name(dtype.name, nbits)
+    # Every gulp writes all the outputs its rows allow, and the rows read end at need_in for every step: a
+    # step's rows are allocated cap = need_in // f - max_delay long, the outputs the last gulp reaches, and
+    # the result is their first nout columns
+    table = np.zeros(len(factors), dtype=engine.DEDISP_STEP_DTYPE)
+    row0 = off = 0
+    for k, ((delays, md, nout), f) in enumerate(zip(layout, factors)):
+        cap = need_in // f - md
+        table[k] = (row0 * nchans, off, cap, 0, delays.shape[0], md, f, 0)
+        row0 += delays.shape[0]
+        off += delays.shape[0] * cap
+    # the table of the first gulp, checked before anything is allocated (the exactness cap among the checks)
+    engine.dedisperse_steps_check(name, gulp, nchans, table, row0 * nchans, off, zero_dm)
+    ws_bytes = engine.dedisperse_steps_workspace_bytes(name, gulp, nchans, factors, zero_dm)
+    total = off * 4 + 2 * gulp * row_bytes + ws_bytes + _block_mask_bytes(fb, block_mask)
+    return dict(layout=layout, factors=factors, need_in=need_in, overlap=overlap, gulp=gulp, nbits=nbits,
+                table=table, out_floats=off, ws_bytes=ws_bytes, total=total)
+
+
+def plan_device_bytes(fb, plan, gulp=None, kdm=KDM, zero_dm=False, block_mask=None):
+    """The device bytes dedisperse_filterbank_plan needs for this plan, what
+    it sets against budget_bytes: every step's rows, the two gulp buffers, the
+    workspace and the block mask (host only; 0 for an empty plan)."""
+    return _plan_setup(fb, plan, gulp, kdm, zero_dm, block_mask)["total"] if plan.steps else 0
+
+
+def plan_slices(fb, plan, budget_bytes=DEFAULT_BUDGET_BYTES, chunk=8, **kwargs):
+    """`plan` cut, in plan order, into the fewest consecutive plans whose
+    dedisperse_filterbank_plan fits budget_bytes each (plan_device_bytes,
+    which takes kwargs), grown `chunk` trials at a time.  Every slice keeps
+    the plan's dm_cover, so its series are the whole plan's.  ValueError when
+    `chunk` trials alone do not fit."""
+    trials = list(zip(plan.dms, plan.downsamp))
+    chunk = max(1, int(chunk))
+
+    def cut(i0, i1):
+        steps = []
+        for dm, f in trials[i0:i1]:
+            if steps and steps[-1][1] == f:
+                steps[-1][0].append(dm)
+            else:
+                steps.append(([dm], int(f)))
+        return DMPlan(steps, plan.tsamp, plan.dm_cover)
+
+    slices, i0 = [], 0
+    while i0 < len(trials):
+        i1 = min(i0 + chunk, len(trials))
+        best = cut(i0, i1)
+        need = plan_device_bytes(fb, best, **kwargs)
+        if need > int(budget_bytes):
+            raise ValueError(f"dedispersing {i1 - i0} DMs of the plan needs {need} bytes of device memory, over the "
+                             f"budget of {int(budget_bytes)}")
+        while i1 < len(trials):
+            nxt = cut(i0, min(i1 + chunk, len(trials)))
+            if plan_device_bytes(fb, nxt, **kwargs) > int(budget_bytes):
+                break
+            best, i1 = nxt, min(i1 + chunk, len(trials))
+        slices.append(best)
+        i0 = i1
+    return slices
+
+
+def dedisperse_filterbank_plan(fb, plan, mask=None, gulp=None, device=None, kdm=KDM,
+                               budget_bytes=DEFAULT_BUDGET_BYTES, zero_dm=False, block_mask=None):
+    """Dedisperse a reading.Filterbank or PackedFilterbank at every trial of a
+    DMPlan, each step decimated in time by its factor f: a list of device
+    tensors, one float32 [ndm_step, nout_step] per step, at the sampling time
+    f * fb.tsamp.  Decimation comes first and the sum second (the
+    specification: dedisperse_ds_host); a step of f = 1 gives
+    dedisperse_filterbank's bits.  nout_step is plan_layout's: every step
+    covers the same stretch of the observation, so the result does not depend
+    on how a plan was sharded.
+
+    The file is streamed once (stream_gulps) for all steps: every gulp goes to
+    channel-major rows once and every step is decimated and summed from those
+    (engine.dedisperse_steps_device).  The gulp is rounded down to a multiple
+    of the least common multiple of the factors and gulps overlap by the
+    largest max_delay * f rounded up to that multiple, so every gulp starts on
+    a decimated sample of every step and the result does not depend on gulp.
+    The step tensors are views of one allocation, rows with unit sample
+    stride and a row stride of at least nout_step.
+
+    mask, zero_dm and block_mask as for dedisperse_filterbank.  Out of scope:
+    bands= (sub-band sums stay at the file's resolution) and pulses.
+    ValueError -- nothing is launched -- for what dedisperse_filterbank
+    refuses, for vmax * f * nchans >= 2^24 of integer data, for a gulp not
+    above the overlap, and when all step outputs plus the gulp buffers and the
+    workspace exceed budget_bytes."""
+    import torch
+    from . import engine
+    from ._args import resolve_device
+    dev = resolve_device(device)
+    if not plan.steps:
+        return []
+    mask = _checked_mask(mask, fb.nchans)
+    setup = _plan_setup(fb, plan, gulp, kdm, zero_dm, block_mask)
+    layout, table, nbits = setup["layout"], setup["table"], setup["nbits"]
+    gulp, need_in, overlap, ws_bytes, off = (setup[k] for k in ("gulp", "need_in", "overlap", "ws_bytes", "out_floats"))
+    if setup["total"] > int(budget_bytes):
+        raise ValueError(f"dedispersing {len(plan)} DMs needs {setup['total']} bytes of device memory ({off * 4} of "
+                         f"output plus the gulp buffers), over the budget of {int(budget_bytes)}: pass fewer DMs per "
+                         "call (plan_slices)")
+    with torch.cuda.device(dev):
+        d_delays = torch.from_numpy(np.concatenate([d for d, _, _ in layout]).astype(np.int32)).to(dev)
+        d_mask = None if mask is None else torch.from_numpy(mask).to(dev)
+        workspace = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        out = torch.empty(off, dtype=torch.float32, device=dev)
+        d_bm = _upload_block_mask(fb, block_mask, dev, need_in)
+
+        def process(block, start):
+            # start is a multiple of every f: step k's outputs of this gulp begin at decimated sample start / f.
+            # A short last gulp may hold no new output of a step (its rows are all inside the overlap)
+            steps = table.copy()
+            steps["out_offset"] = start // steps["downsamp"]
+            live = block.shape[0] // steps["downsamp"].astype(np.int64) > steps["max_delay"]
+            if live.any():
+                engine.dedisperse_steps_device(block, d_delays, steps[live], out, d_mask, workspace, None, zero_dm,
+                                               nbits, d_bm, start)
+
+        stream_gulps(fb, dev, gulp, need_in, overlap, process)
+    return [out.as_strided((int(t["ndm"]), nout), (int(t["out_stride"]), 1), int(t["out_off"]))
+            for t, (_, _, nout) in zip(table, layout)]

@@ -367,6 +367,62 @@ class EngineSearcher:
                           block_mask=block_mask) as (series, metas, _):
             return self.search_device_accel(series, fb.tsamp, metas, accels)
 
+    def search_filterbank_plan(self, fb, plan, mask=None, kdm=None, zero_dm=False, block_mask=None,
+                               budget_bytes=None):
+        """search_filterbank over a dedispersion.DMPlan: the file is
+        dedispersed once at every trial of the plan, each step decimated in
+        time by its factor (dedispersion.dedisperse_filterbank_plan), and
+        every step's series are searched at the step's sampling time, f *
+        fb.tsamp -- plans and peak finders are cached per (length, tsamp), and
+        deredden_params["rmed_width"] is in seconds.  Each step's series go to
+        _enqueue in slices of `batch` DMs, pipelined across steps as the
+        slices of search_filterbank are.  One peak list per DM, in plan order;
+        each trial's metadata is the file's with `dm` and the step's `tsamp`.
+        fb, mask, kdm, zero_dm and block_mask as for search_filterbank; every
+        step covers the stretch of the observation plan.dm_cover leaves.
+
+        A plan whose series do not fit budget_bytes of device memory (default:
+        dedispersion.DEFAULT_BUDGET_BYTES) at once is cut into consecutive
+        slices that do (dedispersion.plan_slices), each dedispersed and
+        searched in turn, one pass over the file per slice; the slices keep
+        dm_cover, so the peaks do not depend on the budget.
+
+        Out of scope: pulses= (event sample indices and
+        single_pulse.cluster_events assume one sampling time), the
+        acceleration axis, and bands= with decimation."""
+        import torch
+        from ._args import resolve_device
+        from .dedispersion import DEFAULT_BUDGET_BYTES, KDM, dedisperse_filterbank_plan, plan_slices
+        kdm = KDM if kdm is None else float(kdm)
+        if not len(plan):
+            return []
+        budget = DEFAULT_BUDGET_BYTES if budget_bytes is None else int(budget_bytes)
+        dev = resolve_device(self.device)
+        per = []
+        with torch.cuda.device(dev):
+            def steps():
+                for part in plan_slices(fb, plan, budget, chunk=self.batch, kdm=kdm, zero_dm=zero_dm,
+                                        block_mask=block_mask):
+                    series = dedisperse_filterbank_plan(fb, part, mask=mask, device=dev, kdm=kdm, zero_dm=zero_dm,
+                                                        block_mask=block_mask, budget_bytes=budget)
+                    yield from slice_steps(part, series)
+                    series = None       # released before the next slice is allocated
+
+            def slice_steps(part, series):
+                for step, rows in zip(part.steps, series):
+                    tsamp = fb.tsamp * step.downsamp
+                    metas = []
+                    for dm in step.dms:
+                        md = fb.metadata(float(dm))
+                        md["tsamp"] = tsamp
+                        metas.append(md)
+                    for b0 in range(0, len(metas), self.batch):
+                        yield b0, self._enqueue(rows[b0:b0 + self.batch], tsamp, metas[b0:b0 + self.batch])
+
+            for _, peaks in _pipelined(steps(), self._detect):
+                per.extend(peaks)
+        return per
+
     def __call__(self, trials):
         return self.search_samples([t.data for t in trials], [t.tsamp for t in trials],
                                    [t.metadata for t in trials])
@@ -534,3 +590,38 @@ def search_filterbank_accel(fb_or_fname, dms, accels, searcher, group=None, mask
         local = searcher.search_filterbank_accel(fb, [dms[i] for i in mine], accels, mask=mask, nout=nout, kdm=kdm,
                                                  zero_dm=zero_dm, block_mask=block_mask)
     return _gather_per_dm(mine, local, group, world, make=AccelPeak)
+
+
+def search_filterbank_plan(fb_or_fname, plan, searcher, group=None, mask=None, kdm=None, zero_dm=False,
+                           block_mask=None, budget_bytes=None):
+    """search_filterbank over a dedispersion.DMPlan (dedispersion.dm_plan):
+    each rank takes the round-robin share of every step of the plan
+    (plan.shard), dedisperses it from the one file with every step decimated
+    in time by its factor, and searches each step at its own sampling time
+    (searcher.search_filterbank_plan, an EngineSearcher); one gather of the
+    tagged peak lists.  Returns the full peak list on every rank, in plan
+    order (then range order within a DM): the search_trials contract.  A
+    shard keeps the plan's dm_cover, so every rank's series cover the stretch
+    of the observation the whole plan leaves and the result does not depend on
+    the sharding.  fb_or_fname, mask, kdm, zero_dm and block_mask as for
+    search_filterbank; budget_bytes is each rank's device memory for the
+    series of one slice of its share (EngineSearcher.search_filterbank_plan).
+
+    Out of scope: pulses= and the acceleration axis with a plan (their events
+    and stretches assume one sampling time), and bands= with decimation;
+    build_candidates_filterbank folds peaks found on a decimated trial at the
+    file's resolution, which works since periods are in seconds."""
+    from .reading import Filterbank, open_filterbank
+    fb = fb_or_fname if isinstance(fb_or_fname, Filterbank) else open_filterbank(fb_or_fname)
+    rank, world = _rank_world(group)
+    mine = plan.shard_indices(rank, world)
+    local = []
+    if mine:
+        # set arguments only: a searcher without them keeps working
+        extra = {"zero_dm": True} if zero_dm else {}
+        if block_mask is not None:
+            extra["block_mask"] = block_mask
+        if budget_bytes is not None:
+            extra["budget_bytes"] = budget_bytes
+        local = searcher.search_filterbank_plan(fb, plan.shard(rank, world), mask=mask, kdm=kdm, **extra)
+    return _gather_per_dm(mine, local, group, world)

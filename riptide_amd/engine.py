@@ -783,6 +783,108 @@ def dedisperse_bands_device(block, delays, max_delay, bands, mask=None, out=None
                               block_mask, t_origin)
 
 
+# rt_dedisp_step (include/riptide_amd.h)
+DEDISP_STEP_DTYPE = np.dtype([("delays_off", np.uint64), ("out_off", np.uint64), ("out_stride", np.uint64),
+                              ("out_offset", np.uint64), ("ndm", np.uint32), ("max_delay", np.uint32),
+                              ("downsamp", np.uint32), ("reserved", np.uint32)])
+DEDISP_MAX_DOWNSAMP = 256    # RT_DEDISP_MAX_DOWNSAMP
+
+
+def checked_dedisp_steps(steps):
+    """steps as a contiguous one-dimensional DEDISP_STEP_DTYPE array;
+    ValueError for anything else."""
+    steps = np.asarray(steps)
+    if steps.dtype != DEDISP_STEP_DTYPE or steps.ndim != 1:
+        raise ValueError("steps must be a one-dimensional array of engine.DEDISP_STEP_DTYPE records")
+    return np.ascontiguousarray(steps)
+
+
+def dedisperse_steps_workspace_bytes(dtype, nsamp_blk, nchans, factors, zero_dm=False, nbits=None):
+    """Device workspace bytes of dedisperse_steps_device for a block of this
+    shape and steps of these downsampling factors: the rows of
+    dedisperse_workspace_bytes, then one float32 area of nchans rows of
+    nsamp_blk // f samples for the smallest f > 1, which every decimated step
+    reuses."""
+    f = np.ascontiguousarray(np.atleast_1d(factors), dtype=np.int64)
+    if f.ndim != 1 or (f.size and (f.min() < 1 or f.max() > DEDISP_MAX_DOWNSAMP)):
+        raise ValueError(f"every downsamp must be in [1, {DEDISP_MAX_DOWNSAMP}]")
+    f = f.astype(np.uint32)
+    return _size(_L.rt_dedisperse_steps_workspace_bytes, DEDISP_DTYPES[_dedisp_name(dtype, nbits)], int(nsamp_blk),
+                 int(nchans), _lib.ptr(f) if f.size else None, f.size, DEDISP_ZERO_DM if zero_dm else 0)
+
+
+def dedisperse_steps_check(dtype, nsamp_blk, nchans, steps, delays_len, out_floats, zero_dm=False, nbits=None,
+                           t_origin=None):
+    """The checks of dedisperse_steps_device on a step table, on the host
+    (rt_dedisperse_steps_check; no device): ValueError with the entry point's
+    message for what it refuses.  t_origin: the absolute sample of row 0 under
+    a block mask that covers the rows (None: no block mask)."""
+    steps = checked_dedisp_steps(steps)
+    bm = None
+    if t_origin is not None:
+        cells, fill = np.zeros(1, dtype=np.uint8), np.zeros(8, dtype=np.uint8)
+        bm = _lib.BlockMaskStruct(cells.ctypes.data, 1, int(t_origin) + int(nsamp_blk), int(t_origin),
+                                  fill.ctypes.data)
+    _check(_L.rt_dedisperse_steps_check(DEDISP_DTYPES[_dedisp_name(dtype, nbits)], int(nsamp_blk), int(nchans),
+                                        _lib.ptr(steps) if steps.size else None, steps.size, int(delays_len),
+                                        int(out_floats), DEDISP_ZERO_DM if zero_dm else 0,
+                                        None if bm is None else ctypes.byref(bm)))
+
+
+def dedisperse_steps_device(block, delays, steps, out, mask=None, workspace=None, stream=None, zero_dm=False,
+                            nbits=None, block_mask=None, t_origin=0):
+    """Every step of a DM plan from one resident block
+    (rt_dedisperse_steps_device): the block goes to channel-major rows once;
+    a step of downsamp f > 1 first sums f consecutive samples of every row
+    (dedisp_decimate_kernel), then the rows are summed along the step's
+    delays, which are in decimated samples (dispersion_delays at tsamp * f):
+
+      z[u, c]   = sum over i < f of block[f * u + i, c]      u < nsamp_blk // f
+      out[d, u] = sum over unmasked c of z[u + delay[d, c], c]
+
+    A step of downsamp 1 gives dedisperse_device's bits.  8-bit and 1/2/4-bit
+    results without zero_dm are exact integers (vmax * f * nchans must be
+    below 2^24); everything else is float32 additions in index order, the
+    bits of dedispersion.dedisperse_ds_host.
+
+    delays: one contiguous int32 [rows, nchans] tensor on the block's device
+    holding every step's table; steps: DEDISP_STEP_DTYPE records, delays_off
+    in int32 elements of `delays`, out_off in floats of `out`, a contiguous
+    one-dimensional float32 tensor.  Step k writes out[out_off + d * out_stride
+    + out_offset + u] for u < nsamp_blk // downsamp - max_delay; returns the
+    list of those [ndm, nout] views of out.  block, mask, nbits, zero_dm,
+    block_mask and t_origin (a multiple of every downsamp) as for
+    dedisperse_device; the workspace is that of
+    dedisperse_steps_workspace_bytes.  Stream-ordered, no host
+    synchronisation; ValueError, nothing launched, for what
+    rt_dedisperse_steps_check refuses and for a short workspace."""
+    import torch
+    name, nsamp_blk, nchans = _dedisp_block(block, nbits)
+    bm = _block_mask_struct(block_mask, t_origin, block, name, nchans)
+    steps = checked_dedisp_steps(steps)
+    if (delays.dim() != 2 or delays.dtype != torch.int32 or delays.device != block.device
+            or not delays.is_contiguous() or delays.shape[1] != nchans):
+        raise ValueError("delays must be a contiguous int32 [ndm, nchans] tensor on the block's device")
+    if out.dim() != 1 or out.dtype != torch.float32 or out.device != block.device or not out.is_contiguous():
+        raise ValueError("out must be a contiguous one-dimensional float32 tensor on the block's device")
+    _check_device_mask(mask, block, nchans)
+    flags = DEDISP_ZERO_DM if zero_dm else 0
+    with stream_scope(block.device, stream) as (_, handle):
+        # the table's own checks, before anything is allocated
+        _check(_L.rt_dedisperse_steps_check(DEDISP_DTYPES[name], nsamp_blk, nchans,
+                                            _lib.ptr(steps) if steps.size else None, steps.size, delays.numel(),
+                                            out.numel(), flags, None if bm is None else ctypes.byref(bm)))
+        need = dedisperse_steps_workspace_bytes(name, nsamp_blk, nchans, steps["downsamp"], zero_dm)
+        workspace = checked_workspace(workspace, need, block.device, "block", floor=16)
+        _check(_L.rt_dedisperse_steps_device(_lib.ptr(block), DEDISP_DTYPES[name], nsamp_blk, nchans,
+                                             _lib.ptr(delays), delays.numel(),
+                                             None if mask is None else _lib.ptr(mask), _lib.ptr(steps), steps.size,
+                                             _lib.ptr(out), out.numel(), _lib.ptr(workspace), workspace.numel(),
+                                             handle, flags, None if bm is None else ctypes.byref(bm)))
+    return [out.as_strided((int(s["ndm"]), nsamp_blk // int(s["downsamp"]) - int(s["max_delay"])),
+                           (int(s["out_stride"]), 1), int(s["out_off"]) + int(s["out_offset"])) for s in steps]
+
+
 # rt_cutout_spec (include/riptide_amd.h)
 CUTOUT_JOB_DTYPE = np.dtype([("start", np.int64), ("out_off", np.uint64), ("factor", np.uint32),
                              ("nbins", np.uint32), ("delay_row", np.uint32), ("band_lo", np.uint32),
