@@ -1058,6 +1058,98 @@ int rt_pulse_cutouts_device(const void* d_block, int dtype, size_t nsamp_blk, si
  * directly.  Both paths give the same bits. */
 int rt_pulse_cutouts_plan(size_t esize, int64_t lo, int64_t hi, size_t* tile, size_t* ndw, int* staged);
 
+/* ---------------------------- signal injection ----------------------------- */
+/* Synthetic pulsars and single pulses added, in place, to a time-major block
+ * x[nsamp][nchans] of RT_DEDISP_U8, RT_DEDISP_I8 or RT_DEDISP_F32 samples
+ * (contiguous rows) whose row 0 is absolute sample t_origin of the
+ * observation.  The packed types are refused.  K signals, one rt_inject_spec
+ * each, name their arrays by offsets into three packed arrays: tmpl (float32),
+ * amp (float32, nchans per signal) and delay (int32, nchans per signal, the
+ * table of rt_dedisperse_delays at the signal's DM).
+ *
+ * For absolute sample t = t_origin + row, channel c and signal k -- 64-bit
+ * two's-complement integers that wrap, unless said otherwise:
+ *   u    = t - delay[k][c]
+ *   s    = 0 when factor == 0, otherwise
+ *          (int64) rint(factor * (double)(u * ((int64)span - u)))
+ *          (int64 -> double rounds to nearest even; one IEEE multiply;
+ *          rint rounds half to even)
+ *   ue   = u + s
+ *   kind 0:  ph  = phase0 + (uint64)ue * step                    (mod 2^64)
+ *            v_k = amp[k][c] * tmpl[k][ph >> (64 - log2bins)]
+ *   kind 1:  i   = ue - t0
+ *            v_k = amp[k][c] * tmpl[k][i] when 0 <= i < length, otherwise 0.0f
+ * v_k is a float32 product, rounded before any addition; acc = (((0.0f + v_0)
+ * + v_1) + ...) in signal order, float32 additions.  Then
+ *   F32:      x = x + acc
+ *   U8 / I8:  x = clamp(x + (int32) floorf(clampf(acc + r)), lo, hi)
+ * with clampf(v) = fminf(fmaxf(v, -65536.0f), 65536.0f) (a NaN becomes
+ * -65536), [lo, hi] the type's range and the dither
+ *   r = (float)(z >> 40) * 2^-24, z = mix(t * nchans + c + seed * 0x9E3779B97F4A7C15)
+ *   mix: z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27;
+ *        z *= 0x94D049BB133111EB; z ^= z >> 31        (the splitmix64 finaliser)
+ * a stochastic rounding that is unbiased, reproducible, and a function of the
+ * absolute sample alone: the result does not depend on how an observation is
+ * cut into blocks.  With K == 0 nothing is touched; where acc == 0 a sample is
+ * unchanged.  Host and device results have the same bits.
+ *
+ * step = round(2^64 * tsamp / P) and phase0 count 2^-64 turns.  factor is the
+ * f of the resampling above (accel * tsamp / (2 c)) and span its N: u + s is
+ * the first-order inverse of out[j] = x[j - s_j], so the search's resampling
+ * at the same f maps the injected train back to a periodic one up to the
+ * residual s_j - s_(j - s_j), the change of s over a distance of |s| samples:
+ * at most (|f| * span)^2 * span / 4 + 1 samples, since |ds/dj| <= |f| * span
+ * and |s| <= |f| * span^2 / 4.  The inverse is first
+ * order, not exact.  One template per signal: no per-channel smearing.
+ *
+ * RT_EINVAL (nothing is written or launched) for a sample type other than the
+ * three, nchans above RT_INJECT_MAX_CHANS, t_origin + nsamp >= 2^31, and for a
+ * signal with: a kind other than 0 or 1, kind 0 with log2bins outside [1, 16],
+ * kind 1 with length == 0, span above RT_RESAMPLE_MAX_SAMPLES, a factor that
+ * is not finite, has fabs(factor) * (double)span >= 1.0 or is not zero while
+ * span is, a non-zero reserved, a template, amplitude or delay range that runs
+ * past its array, or -- where the arrays are host memory -- an amplitude or a
+ * template value that is not finite. */
+#define RT_INJECT_MAX_CHANS 16777216
+typedef struct rt_inject_spec {
+    uint64_t tmpl_off;   /* float offset of the template in tmpl: 2^log2bins (kind 0) or length (kind 1) entries */
+    uint64_t amp_off;    /* float offset of the nchans amplitudes in amp */
+    uint64_t delay_off;  /* int32 offset of the nchans delays in delay */
+    uint64_t step;       /* kind 0: phase per sample, 2^-64 turns */
+    uint64_t phase0;     /* kind 0: phase at ue = 0 */
+    int64_t  t0;         /* kind 1: the sample of template entry 0 at zero delay */
+    double   factor;     /* f of the acceleration map; 0: none */
+    uint64_t span;       /* N of the acceleration map */
+    uint32_t kind;       /* 0 periodic, 1 single pulse */
+    uint32_t log2bins;   /* kind 0: 1 .. 16 */
+    uint32_t length;     /* kind 1: >= 1 */
+    uint32_t reserved;   /* 0 */
+} rt_inject_spec;
+/* Host only, no device: every check above on arrays in host memory. */
+int rt_inject_check(int dtype, size_t nsamp, size_t nchans, uint64_t t_origin, const rt_inject_spec* specs,
+                    size_t nspecs, const float* tmpl, size_t tmpl_len, const float* amp, size_t amp_len,
+                    const int32_t* delay, size_t delay_len);
+/* Host only, no device: the specification, sequential, in place on x. */
+int rt_inject_host(void* x, int dtype, size_t nsamp, size_t nchans, uint64_t t_origin, uint64_t seed,
+                   const rt_inject_spec* specs, size_t nspecs, const float* tmpl, size_t tmpl_len, const float* amp,
+                   size_t amp_len, const int32_t* delay, size_t delay_len);
+/* The same, in place on a device-resident block (any byte alignment for the
+ * 8-bit types, 4 bytes for F32).  Stream-ordered: one launch, no host
+ * synchronisation, no device allocation and no workspace.  specs is host
+ * memory and is checked there; d_specs is the same table in device memory
+ * (8-byte aligned), d_tmpl, d_amp and d_delay the packed arrays in device
+ * memory, which the caller uploads once for as many blocks as it likes and
+ * whose values it has put through rt_inject_check. */
+int rt_inject_device(void* d_block, int dtype, size_t nsamp_blk, size_t nchans, uint64_t t_origin, uint64_t seed,
+                     const rt_inject_spec* specs, size_t nspecs, const rt_inject_spec* d_specs, const float* d_tmpl,
+                     size_t tmpl_len, const float* d_amp, size_t amp_len, const int32_t* d_delay, size_t delay_len,
+                     void* stream);
+/* Host-buffer form: rt_inject_check, then the block and the tables are
+ * uploaded, rt_inject_device runs and the block is copied back.  Synchronous. */
+int rt_inject(void* x, int dtype, size_t nsamp, size_t nchans, uint64_t t_origin, uint64_t seed,
+              const rt_inject_spec* specs, size_t nspecs, const float* tmpl, size_t tmpl_len, const float* amp,
+              size_t amp_len, const int32_t* delay, size_t delay_len);
+
 /* --------------------------- file input (device) --------------------------- */
 /* 8-bit SIGPROC samples (riptide/time_series.py:352-357) to float32 in device
  * memory: d_raw holds n bytes, int8 when is_signed else uint8; exact as

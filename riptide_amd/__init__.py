@@ -27,7 +27,8 @@ from .dedispersion import DMPlan, dm_plan
 from .refine import Refinement, refine_candidates, refine_cube
 from .single_pulse import SinglePulse, search_filterbank_pulses
 from .pulse_candidates import PulseCandidate, build_pulse_candidates
-from . import acceleration, dedispersion, pulse_candidates, rfi, single_pulse
+from .injection import InjectionTables, PulsarSignal, PulseSignal, inject_filterbank, injection_tables
+from . import acceleration, dedispersion, injection, pulse_candidates, rfi, single_pulse
 
 __all__ = [
     "Candidate", "PeakCluster", "build_candidates", "build_candidates_filterbank", "flag_harmonics",
@@ -41,4 +42,5 @@ __all__ = [
     "PulseCandidate", "build_pulse_candidates", "pulse_candidates",
     "acceleration", "search_filterbank_accel",
     "dm_plan", "DMPlan", "search_filterbank_plan",
+    "injection", "PulsarSignal", "PulseSignal", "InjectionTables", "injection_tables", "inject_filterbank",
 ]

@@ -198,6 +198,18 @@ _SIGNATURES = {
                                        _c_sz, _vp, _c_sz, _vp, ctypes.c_uint32, _vp]),
     # esize, lo, hi, tile, ndw, staged
     "rt_pulse_cutouts_plan": (_c_i, [_c_sz, ctypes.c_int64, ctypes.c_int64, _psz, _psz, ctypes.POINTER(_c_i)]),
+    # the injection: `specs` is a numpy array of engine.INJECT_SPEC_DTYPE (rt_inject_spec) in host memory
+    # dtype, nsamp, nchans, t_origin, specs, nspecs, tmpl, tmpl_len, amp, amp_len, delay (int32), delay_len
+    "rt_inject_check": (_c_i, [_c_i, _c_sz, _c_sz, ctypes.c_uint64, _vp, _c_sz, _vp, _c_sz, _vp, _c_sz, _vp, _c_sz]),
+    # x, dtype, nsamp, nchans, t_origin, seed, then as above from specs
+    "rt_inject_host": (_c_i, [_vp, _c_i, _c_sz, _c_sz, ctypes.c_uint64, ctypes.c_uint64, _vp, _c_sz, _vp, _c_sz, _vp,
+                              _c_sz, _vp, _c_sz]),
+    "rt_inject": (_c_i, [_vp, _c_i, _c_sz, _c_sz, ctypes.c_uint64, ctypes.c_uint64, _vp, _c_sz, _vp, _c_sz, _vp,
+                         _c_sz, _vp, _c_sz]),
+    # block, dtype, nsamp_blk, nchans, t_origin, seed, specs (host), nspecs, then device: specs, tmpl, tmpl_len, amp,
+    # amp_len, delay, delay_len; stream
+    "rt_inject_device": (_c_i, [_vp, _c_i, _c_sz, _c_sz, ctypes.c_uint64, ctypes.c_uint64, _vp, _c_sz, _vp, _vp,
+                                _c_sz, _vp, _c_sz, _vp, _c_sz, _vp]),
 }
 
 

@@ -6,6 +6,7 @@
 #include "dered_host.hpp"
 #include "fold_host.hpp"
 #include "harmonic.hpp"
+#include "inject_host.hpp"
 #include "refine_host.hpp"
 #include "resample_host.hpp"
 #include "riptide_amd.h"
@@ -179,6 +180,11 @@ hipError_t launch_pulse_cutouts(const void* ws, int dtype, uint32_t flags, uint3
 // (resample_check_args of resample_host.hpp)
 hipError_t launch_resample(const float* x, uint64_t ldx, uint32_t N, const ResampleRows& T, uint32_t rows,
                            float* out, uint64_t ldo, hipStream_t s);
+
+// inject_kernels.hip
+// the specification of inject_host.hpp in place on the block A.x + A.m; A and
+// blocks are inject_shape's, the table has passed inject_check_table
+hipError_t launch_inject(int dtype, const InjectArgs& A, uint32_t blocks, hipStream_t s);
 
 // harmonic_kernels.hip
 // One tile of the harmonic pair matrix: rows [i0, i0 + rows) of the n ranked

@@ -280,6 +280,16 @@ def _upload_block_mask(fb, block_mask, dev, nrows):
     return engine.DeviceBlockMask(d_cells, torch.from_numpy(fill).to(dev), block_len)
 
 
+def _resolve_inject(inject, fb):
+    """(tables, seed) of an inject= argument checked against `fb`, None for
+    None (injection.resolve_inject, imported on first use: that module imports
+    this one)."""
+    if inject is None:
+        return None
+    from .injection import resolve_inject
+    return resolve_inject(inject, fb)
+
+
 def stream_gulps(fb, dev, gulp, nrows, overlap, process):
     """Stream rows [0, nrows) of a reading.Filterbank's memory map to `dev` in
     gulps of `gulp` time samples that overlap by `overlap`, through two
@@ -332,7 +342,7 @@ def stream_gulps(fb, dev, gulp, nrows, overlap, process):
 
 
 def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, nout=None,
-                          budget_bytes=DEFAULT_BUDGET_BYTES, zero_dm=False, bands=None, block_mask=None):
+                          budget_bytes=DEFAULT_BUDGET_BYTES, zero_dm=False, bands=None, block_mask=None, inject=None):
     """Dedisperse a reading.Filterbank (or PackedFilterbank: the rows are
     uploaded packed) at the trial DMs into one device tensor
     float32 [ndm, nout], nout = nsamp - max_delay (or a smaller `nout`: the
@@ -363,6 +373,17 @@ def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, n
     depend on gulp.  The cells and the fill are uploaded once and count
     against the budget.
 
+    inject (an injection.InjectionTables, or (tables, seed)): synthetic
+    signals are added to every gulp's block in place as it arrives on the
+    device (engine.inject_device), in front of the block mask and everything
+    behind it: the result is that of the same call on a file holding
+    injection.inject_host's samples, bit for bit, and does not depend on gulp
+    (overlap rows are uploaded afresh with every gulp and the injected value
+    depends on the absolute sample alone).  Packed files are refused.  The
+    tables (a few KiB per signal, uploaded once and kept with the
+    InjectionTables) are not counted against the budget, so a call fits it
+    with inject= exactly when it fits without.
+
     ValueError -- nothing is launched -- when max_delay >= nsamp, for 8-bit
     data of more than 65793 channels, for a block mask of another channel
     count or one that does not cover the rows read, and when the output (ndm *
@@ -371,6 +392,7 @@ def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, n
     import torch
     from . import engine
     from ._args import resolve_device
+    inject = _resolve_inject(inject, fb)
     dev = resolve_device(device)
     nsamp, nchans = fb.nsamp, fb.nchans
     nbits = _checked_sample_type(fb)
@@ -412,6 +434,8 @@ def dedisperse_filterbank(fb, dms, mask=None, gulp=None, device=None, kdm=KDM, n
         d_bm = _upload_block_mask(fb, block_mask, dev, need_in)
 
         def process(block, start):
+            if inject is not None:
+                engine.inject_device(block, inject[0], start, inject[1])
             # dedisperse_device, or with a table dedisperse_bands_device
             engine._dedisperse_device(block, d_delays, max_delay, d_bands, d_mask, out, start, workspace, None,
                                       zero_dm, nbits, d_bm, start)
@@ -749,7 +773,7 @@ def plan_slices(fb, plan, budget_bytes=DEFAULT_BUDGET_BYTES, chunk=8, **kwargs):
 
 
 def dedisperse_filterbank_plan(fb, plan, mask=None, gulp=None, device=None, kdm=KDM,
-                               budget_bytes=DEFAULT_BUDGET_BYTES, zero_dm=False, block_mask=None):
+                               budget_bytes=DEFAULT_BUDGET_BYTES, zero_dm=False, block_mask=None, inject=None):
     """Dedisperse a reading.Filterbank or PackedFilterbank at every trial of a
     DMPlan, each step decimated in time by its factor f: a list of device
     tensors, one float32 [ndm_step, nout_step] per step, at the sampling time
@@ -768,7 +792,8 @@ def dedisperse_filterbank_plan(fb, plan, mask=None, gulp=None, device=None, kdm=
     The step tensors are views of one allocation, rows with unit sample
     stride and a row stride of at least nout_step.
 
-    mask, zero_dm and block_mask as for dedisperse_filterbank.  Out of scope:
+    mask, zero_dm, block_mask and inject as for dedisperse_filterbank (the
+    injection comes first, at the file's resolution).  Out of scope:
     bands= (sub-band sums stay at the file's resolution) and pulses.
     ValueError -- nothing is launched -- for what dedisperse_filterbank
     refuses, for vmax * f * nchans >= 2^24 of integer data, for a gulp not
@@ -777,6 +802,7 @@ def dedisperse_filterbank_plan(fb, plan, mask=None, gulp=None, device=None, kdm=
     import torch
     from . import engine
     from ._args import resolve_device
+    inject = _resolve_inject(inject, fb)
     dev = resolve_device(device)
     if not plan.steps:
         return []
@@ -798,6 +824,8 @@ def dedisperse_filterbank_plan(fb, plan, mask=None, gulp=None, device=None, kdm=
         def process(block, start):
             # start is a multiple of every f: step k's outputs of this gulp begin at decimated sample start / f.
             # A short last gulp may hold no new output of a step (its rows are all inside the overlap)
+            if inject is not None:
+                engine.inject_device(block, inject[0], start, inject[1])
             steps = table.copy()
             steps["out_offset"] = start // steps["downsamp"]
             live = block.shape[0] // steps["downsamp"].astype(np.int64) > steps["max_delay"]

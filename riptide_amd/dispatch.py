@@ -252,7 +252,7 @@ class EngineSearcher:
         return self.submit_samples(samples, tsamps, metadatas)()
 
     def search_filterbank(self, fb, dms, mask=None, nout=None, kdm=None, zero_dm=False, pulses=None,
-                          block_mask=None):
+                          block_mask=None, inject=None):
         """Dedisperse a reading.Filterbank or PackedFilterbank at the trial DMs on the device
         (dedispersion.dedisperse_filterbank) and search every series: one peak
         list per DM, in the order given (the __call__ contract).  The series
@@ -267,7 +267,9 @@ class EngineSearcher:
         `mask` from the file's channel statistics); `block_mask` (a
         rfi.BlockMask, from rfi.block_mask(rfi.block_stats(fb))) replaces the
         samples of its flagged (time block, channel) cells by the channel's
-        fill as the file is read.
+        fill as the file is read; `inject` (an injection.InjectionTables, or
+        (tables, seed)) adds synthetic signals to the samples in front of all
+        of that (dedispersion.dedisperse_filterbank).
 
         pulses: None, or a dict of single_pulse.search_pulses parameters
         (widths, threshold, radius, time_radius, dm_gap, max_events): every
@@ -290,7 +292,7 @@ class EngineSearcher:
             return [] if kw is None else ([], [])
         per, parts = [], []
         with _dedispersed(fb, dms, self.device, self.batch, mask=mask, nout=nout, kdm=kdm, zero_dm=zero_dm,
-                          block_mask=block_mask) as (series, metas, slices):
+                          block_mask=block_mask, inject=inject) as (series, metas, slices):
             each = None
             if kw is not None:
                 widths = single_pulse._default_widths(kw.get("widths"), series.shape[1])
@@ -351,11 +353,11 @@ class EngineSearcher:
         return out
 
     def search_filterbank_accel(self, fb, dms, accels, mask=None, nout=None, kdm=None, zero_dm=False,
-                                block_mask=None):
+                                block_mask=None, inject=None):
         """search_filterbank with an acceleration axis: the file dedispersed at
         the trial DMs on the device, then search_device_accel of the series.
         One list of acceleration.AccelPeak per DM, in the order given; fb, mask,
-        nout, kdm, zero_dm and block_mask as for search_filterbank.  With
+        nout, kdm, zero_dm, block_mask and inject as for search_filterbank.  With
         accels = [0.0] the peaks are search_filterbank's.  The single-pulse
         search (pulses=) is not combined with it."""
         from .dedispersion import KDM
@@ -364,11 +366,11 @@ class EngineSearcher:
         if not dms:
             return []
         with _dedispersed(fb, dms, self.device, self.batch, mask=mask, nout=nout, kdm=kdm, zero_dm=zero_dm,
-                          block_mask=block_mask) as (series, metas, _):
+                          block_mask=block_mask, inject=inject) as (series, metas, _):
             return self.search_device_accel(series, fb.tsamp, metas, accels)
 
     def search_filterbank_plan(self, fb, plan, mask=None, kdm=None, zero_dm=False, block_mask=None,
-                               budget_bytes=None):
+                               budget_bytes=None, inject=None):
         """search_filterbank over a dedispersion.DMPlan: the file is
         dedispersed once at every trial of the plan, each step decimated in
         time by its factor (dedispersion.dedisperse_filterbank_plan), and
@@ -378,7 +380,7 @@ class EngineSearcher:
         _enqueue in slices of `batch` DMs, pipelined across steps as the
         slices of search_filterbank are.  One peak list per DM, in plan order;
         each trial's metadata is the file's with `dm` and the step's `tsamp`.
-        fb, mask, kdm, zero_dm and block_mask as for search_filterbank; every
+        fb, mask, kdm, zero_dm, block_mask and inject as for search_filterbank; every
         step covers the stretch of the observation plan.dm_cover leaves.
 
         A plan whose series do not fit budget_bytes of device memory (default:
@@ -404,7 +406,7 @@ class EngineSearcher:
                 for part in plan_slices(fb, plan, budget, chunk=self.batch, kdm=kdm, zero_dm=zero_dm,
                                         block_mask=block_mask):
                     series = dedisperse_filterbank_plan(fb, part, mask=mask, device=dev, kdm=kdm, zero_dm=zero_dm,
-                                                        block_mask=block_mask, budget_bytes=budget)
+                                                        block_mask=block_mask, budget_bytes=budget, inject=inject)
                     yield from slice_steps(part, series)
                     series = None       # released before the next slice is allocated
 
@@ -517,7 +519,7 @@ def search_files(fnames, pool, group=None, chunksize=None):
 
 
 def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=None, zero_dm=False, pulses=None,
-                      block_mask=None):
+                      block_mask=None, inject=None):
     """Search a channelised SIGPROC file (a file name, opened by
     reading.open_filterbank: 1-, 2-, 4-, 8-, 16- or 32-bit samples; or a
     Filterbank / PackedFilterbank) at the trial DMs without leaving the
@@ -532,7 +534,9 @@ def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=Non
     (default: dedispersion.KDM); `zero_dm` subtracts every time sample's mean
     over the unmasked channels before the sum (the zero-DM filter);
     `block_mask` (a rfi.BlockMask) replaces the samples of its flagged (time
-    block, channel) cells by the channel's fill in front of both.
+    block, channel) cells by the channel's fill in front of both; `inject` (an
+    injection.InjectionTables, or (tables, seed)) adds synthetic signals to the
+    samples in front of all three, the same on every rank.
 
     pulses: None, or a dict of single_pulse.search_pulses parameters: every
     rank then also runs the single-pulse search on its normalised series
@@ -548,6 +552,8 @@ def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=Non
             extra["pulses"] = pulses
         if block_mask is not None:    # as zero_dm: only when set
             extra["block_mask"] = block_mask
+        if inject is not None:
+            extra["inject"] = inject
         local = searcher.search_filterbank(fb, [dms[i] for i in mine], mask=mask, nout=nout, kdm=kdm, **extra)
         if pulses is not None:
             local = local[0]
@@ -571,7 +577,7 @@ def search_filterbank(fb_or_fname, dms, searcher, group=None, mask=None, kdm=Non
 
 
 def search_filterbank_accel(fb_or_fname, dms, accels, searcher, group=None, mask=None, kdm=None, zero_dm=False,
-                            block_mask=None):
+                            block_mask=None, inject=None):
     """search_filterbank with an acceleration axis: each rank dedisperses its
     round-robin share of `dms` from the one file, searches every series at
     every trial acceleration of `accels` (m/s^2;
@@ -580,20 +586,21 @@ def search_filterbank_accel(fb_or_fname, dms, accels, searcher, group=None, mask
     on every rank, in the order of `dms`, then of `accels`, then range order.
     Every rank cuts its series to the length the whole DM list leaves, so the
     result does not depend on the sharding -- the stretch is defined on that
-    common length.  fb_or_fname, mask, kdm, zero_dm and block_mask as for
+    common length.  fb_or_fname, mask, kdm, zero_dm, block_mask and inject as for
     search_filterbank; the single-pulse search is not combined with it."""
     from .acceleration import AccelPeak
     fb, dms, kdm, world, mine, nout = _filterbank_shard(fb_or_fname, dms, kdm, group)
     accels = [float(a) for a in accels]
     local = []
     if dms:
+        extra = {} if inject is None else {"inject": inject}    # only when set
         local = searcher.search_filterbank_accel(fb, [dms[i] for i in mine], accels, mask=mask, nout=nout, kdm=kdm,
-                                                 zero_dm=zero_dm, block_mask=block_mask)
+                                                 zero_dm=zero_dm, block_mask=block_mask, **extra)
     return _gather_per_dm(mine, local, group, world, make=AccelPeak)
 
 
 def search_filterbank_plan(fb_or_fname, plan, searcher, group=None, mask=None, kdm=None, zero_dm=False,
-                           block_mask=None, budget_bytes=None):
+                           block_mask=None, budget_bytes=None, inject=None):
     """search_filterbank over a dedispersion.DMPlan (dedispersion.dm_plan):
     each rank takes the round-robin share of every step of the plan
     (plan.shard), dedisperses it from the one file with every step decimated
@@ -603,7 +610,7 @@ def search_filterbank_plan(fb_or_fname, plan, searcher, group=None, mask=None, k
     order (then range order within a DM): the search_trials contract.  A
     shard keeps the plan's dm_cover, so every rank's series cover the stretch
     of the observation the whole plan leaves and the result does not depend on
-    the sharding.  fb_or_fname, mask, kdm, zero_dm and block_mask as for
+    the sharding.  fb_or_fname, mask, kdm, zero_dm, block_mask and inject as for
     search_filterbank; budget_bytes is each rank's device memory for the
     series of one slice of its share (EngineSearcher.search_filterbank_plan).
 
@@ -623,5 +630,7 @@ def search_filterbank_plan(fb_or_fname, plan, searcher, group=None, mask=None, k
             extra["block_mask"] = block_mask
         if budget_bytes is not None:
             extra["budget_bytes"] = budget_bytes
+        if inject is not None:
+            extra["inject"] = inject
         local = searcher.search_filterbank_plan(fb, plan.shard(rank, world), mask=mask, kdm=kdm, **extra)
     return _gather_per_dm(mine, local, group, world)

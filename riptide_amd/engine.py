@@ -961,6 +961,43 @@ def pulse_cutouts_device(block, jobs, delays, max_delay, mask=None, out=None, wo
     return out
 
 
+# rt_inject_spec (include/riptide_amd.h)
+INJECT_SPEC_DTYPE = np.dtype([("tmpl_off", np.uint64), ("amp_off", np.uint64), ("delay_off", np.uint64),
+                              ("step", np.uint64), ("phase0", np.uint64), ("t0", np.int64), ("factor", np.float64),
+                              ("span", np.uint64), ("kind", np.uint32), ("log2bins", np.uint32),
+                              ("length", np.uint32), ("reserved", np.uint32)])
+
+
+def inject_device(block, tables, t_origin=0, seed=0, stream=None):
+    """Add the signals of an injection.InjectionTables to one resident block,
+    in place (rt_inject_device; the specification: injection.inject_host, bit
+    for bit): block uint8 / int8 / float32 [nsamp_blk, nchans] (time-major,
+    contiguous; a row slice of a larger tensor is fine), whose row 0 is
+    absolute sample t_origin of the observation; seed picks the dither of
+    8-bit samples.  The tables are uploaded once per InjectionTables and
+    device and kept with it.  One launch, stream-ordered, no host
+    synchronisation, no workspace.  Packed rows cannot be passed: they are
+    uint8 here and would be taken for 8-bit samples (the file-level entry
+    points refuse packed files).  ValueError, nothing launched, for a block of
+    another channel count than the tables', t_origin + nsamp_blk >= 2^31, and
+    a table rt_inject_check refuses.  Returns block."""
+    import torch
+    name, nsamp_blk, nchans = _dedisp_block(block)
+    if nchans != tables.nchans:
+        raise ValueError(f"the injection tables have {tables.nchans} channels, the block {nchans}")
+    t_origin, seed = int(t_origin), int(seed)
+    if t_origin < 0 or not 0 <= seed < 1 << 64:
+        raise ValueError("inject: t_origin must not be negative and seed must be in [0, 2^64)")
+    # uploaded on the device's current stream, not on `stream`: the tables outlive the call
+    d = tables.on_device(block.device)
+    with stream_scope(block.device, stream) as (_, handle):
+        _check(_L.rt_inject_device(_lib.ptr(block), DEDISP_DTYPES[name], nsamp_blk, nchans, t_origin, seed,
+                                   _lib.ptr(tables.specs), tables.specs.size, _lib.ptr(d[0]), _lib.ptr(d[1]),
+                                   tables.tmpl.size, _lib.ptr(d[2]), tables.amp.size, _lib.ptr(d[3]),
+                                   tables.delay.size, handle))
+    return block
+
+
 def profile_enable(on=True):
     _check(_L.rt_profile_enable(int(bool(on))))
 

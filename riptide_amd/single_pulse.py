@@ -183,14 +183,16 @@ def search_pulses(series, tsamp, dms, widths=None, threshold=8.0, radius=None, t
 
 def search_filterbank_pulses(fb_or_fname, dms, deredden_params, widths=None, threshold=8.0, mask=None, zero_dm=False,
                              kdm=None, nout=None, batch=8, device=None, radius=None, time_radius=None, dm_gap=1,
-                             max_events=1 << 20, block_mask=None, cutouts=None):
+                             max_events=1 << 20, block_mask=None, cutouts=None, inject=None):
     """Single-pulse search of a channelised SIGPROC file (a file name, a
     reading.Filterbank or PackedFilterbank) at the trial DMs without leaving
     the device: dedispersion.dedisperse_filterbank, then slices of `batch` DMs
     through engine.deredden_normalise (deredden_params: rmed_width in
     seconds, rmed_minpts) and engine.single_pulse_device, one download of the
-    events and cluster_events.  mask, zero_dm, kdm, nout, block_mask: as for
-    dispatch.search_filterbank.  Returns (pulses, events); `series` of an
+    events and cluster_events.  mask, zero_dm, kdm, nout, block_mask, inject:
+    as for dispatch.search_filterbank (cutouts are read back from the file as
+    it is, without the injected signals: injection.inject_filterbank writes a
+    file that has them).  Returns (pulses, events); `series` of an
     event is its index into dms.
 
     cutouts: None, or a dict of keyword arguments of
@@ -211,7 +213,7 @@ def search_filterbank_pulses(fb_or_fname, dms, deredden_params, widths=None, thr
         return none if cutouts is None else none + ([],)
     parts = []
     with _dedispersed(fb, dms, device, max(1, int(batch)), mask=mask, nout=nout, kdm=kdm, zero_dm=zero_dm,
-                      block_mask=block_mask) as (series, _, slices):
+                      block_mask=block_mask, inject=inject) as (series, _, slices):
         w = _default_widths(widths, series.shape[1])
         ws = int(round(deredden_params["rmed_width"] / fb.tsamp))
         for b0, b1 in slices:
